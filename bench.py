@@ -16,15 +16,19 @@ One GPU (default `--hip-graph auto`): after the warm-up ONE step is captured int
 three replays are timed (still warm-up), and the timed region runs the faster form: K replays (0.3 ms of host time per
 step) where the host is the longer pole - slow-CPU boxes, the 24-block presets - or the eager loop where the GPU is (it
 overlaps the weight-gradient GEMMs on a side stream, a captured graph does not).  HIP events cannot be read back from
-inside a graph, so after a replayed region the per-kernel rows are taken from K more EAGER steps of the same process
+inside a graph, so after a replayed region `--full` takes the per-kernel rows from K more EAGER steps of the same process
 (`config.hip_graph`, `config.hip_graph_probe`, `config.kernel_rows`).  N > 1 (round 3): the same - the captured step then
 holds the gradient all-reduce (`--dp-mode flat`, default: ONE flat all-reduce after the backward; `ddp`: torch DDP's buckets,
 constructed and warmed up for 11 steps on the side stream as torch asks) and the SyncBatchNorm statistics all-reduces (RCCL
 collectives are capturable); the ranks agree before the first replay, so a
-rank whose capture failed sends everyone to the eager loop.  `--hip-graph off` / `VAH_DP_GRAPH=0` time the eager loop with
-the events inside the timed region.
+rank whose capture failed sends everyone to the eager loop.  `--hip-graph off` / `VAH_DP_GRAPH=0` time the eager loop (with
+`--full`, with the events inside the timed region).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run does only what the headline needs: set-up, warm-up (with the replay probe above), the K timed steps, and
+rank 0's ONE JSON line with the contract fields (`metric`, `value` in images/sec, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = wall time of the timed region / K) and `config`.  `--dump-outputs DIR` then also writes what the timed path
+computed in its last step as DIR/<name>.npy (see dump_outputs).  `--full` adds, with HIP events and runs of their own
+after the timed region (with `--hip-graph off` or an eager pick, the MSDA / attention events sit inside it):
   "roofline":     the MSDA entry point with the largest total time in the timed region: bytes the
                   launch must move FOR THE DTYPES IT RUNS WITH / mean launch duration (HIP events
                   recorded by the library on the launch stream during the timed steps) against the
@@ -58,6 +62,9 @@ HBM_PEAK = 8.0e12     # B/s, MI355X_MICROARCH.md "HBM3E peak BW" (spec)
 MFMA_PEAK = 2.5e15    # flop/s, dense bf16 MFMA (same guide; the 5 PF headline includes 2:1 sparsity)
 
 
+FULL_ONLY = ('cpu_baseline', 'family_steps', 'profile_kernels', 'boundary_iters', 'consumer_iters')
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -69,7 +76,7 @@ def parse():
                     help='capture one whole step (zero_grad, forward, backward, AdamW - and, with a process group, DDP\'s bucketed '
                          'all-reduces and the SyncBatchNorm statistics all-reduces: RCCL collectives are capturable) into a HIP '
                          'graph after the warm-up and time K replays of it (0.3 ms of host time per step instead of 20-70 ms); the '
-                         'per-kernel rows then come from K more EAGER steps right after the timed region, because HIP events '
+                         '--full per-kernel rows then come from K more EAGER steps right after the timed region, because HIP events '
                          'cannot be read back from inside a graph.  auto: replay if the capture succeeds ON EVERY RANK and three '
                          'replays beat three eager steps (maximum over the ranks) during the warm-up, else the eager loop; '
                          'VAH_DP_GRAPH=0 keeps steps with collectives eager; off: always the eager loop with the events inside '
@@ -79,8 +86,16 @@ def parse():
                          'cards): keep the activations instead - 288 GB of HBM holds them, same arithmetic')
     ap.add_argument('--batch', type=int, default=2, help='per-GPU batch')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: per-kernel HIP-event rows and the roofline, operator '
+                         'family rows, fp32 boundary kernels, consumer rows and the CPU baseline (the options below marked '
+                         '--full); off: set-up, warm-up, the timed steps and the result line only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy '
+                         '(float32, ~48 MB: loss, the four feature maps, gradients and updated parameters; seeded samples of '
+                         'the large ones)')
     ap.add_argument('--cpu-baseline', default='auto', choices=['auto', 'full', 'small', 'none'],
-                    help="auto: 'full' (one 1024^2 image) at N=1 on rank 0, none otherwise")
+                    help="--full: auto: 'full' (one 1024^2 image) at N=1 on rank 0, none otherwise")
     ap.add_argument('--no-optimizer', action='store_true', help='diagnostic only: skip AdamW')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help="'gloo' lets several ranks share one GPU for a functional rehearsal of the "
@@ -90,16 +105,16 @@ def parse():
                          'for point-to-point xGMI, no per-gradient bucket copies, a captured step with one collective on a side '
                          'stream instead of one per bucket) or torch DDP with 64 MB buckets overlapped with the backward')
     ap.add_argument('--family-steps', type=int, default=5,
-                    help='untimed eager steps after the timed region that put every library entry point on the `kernels` list '
+                    help='--full: untimed eager steps after the timed region that put every library entry point on the `kernels` list '
                          '(GEMMs by role with MFMA fractions, LayerNorm / residual / column-sum / conv / BatchNorm-tail rows); 0: off')
     ap.add_argument('--profile-kernels', default='msda_,attn_',
-                    help='HIP-event timing inside the timed region for the library entry points whose name '
+                    help='--full: HIP-event timing of the library entry points whose name '
                          'starts with one of these comma-separated prefixes ("" = all of them, costs ~2 %%; '
                          '"none" = no events)')
     ap.add_argument('--boundary-iters', type=int, default=20,
-                    help='iterations of the fp32 boundary-kernel measurement after the timed region (0 = skip)')
+                    help='--full: iterations of the fp32 boundary-kernel measurement after the timed region (0 = skip)')
     ap.add_argument('--consumer-iters', type=int, default=5,
-                    help='iterations of the pixel-decoder encoder / UPerHead rows after the timed region (0 = skip)')
+                    help='--full: iterations of the pixel-decoder encoder / UPerHead rows after the timed region (0 = skip)')
     ap.add_argument('--mock-step', action='store_true',
                     help='CPU rehearsal of the launch path only (rank spawn, process group over gloo, barrier, '
                          'max-over-ranks, the one JSON line) around a toy step; used by tests/test_bench_launch_cpu.py, '
@@ -107,7 +122,18 @@ def parse():
     ap.add_argument('--gemm-tuning', default='file', choices=['file', 'off', 'tune'],
                     help="hipBLASLt/rocBLAS solution selection through torch TunableOp: 'file' loads the "
                          "committed selections (no tuning at run time), 'tune' re-tunes and rewrites them")
-    return ap.parse_args()
+    # options of the --full measurements: a sentinel tells which ones the command line set
+    args = ap.parse_args(namespace=argparse.Namespace(**{d: None for d in FULL_ONLY}))
+    given = [d for d in FULL_ONLY if getattr(args, d) is not None]
+    for d in FULL_ONLY:
+        if getattr(args, d) is None:
+            setattr(args, d, ap.get_default(d))
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if given and not args.full and not args.mock_step:
+        print('bench.py: %s only take(s) effect with --full; this run measures the headline alone (no kernels, roofline or '
+              'cpu_baseline)' % ', '.join('--' + d.replace('_', '-') for d in given), file=sys.stderr)
+    return args
 
 
 def host_cores():
@@ -338,6 +364,30 @@ def kernel_row(r, steps):
     return row
 
 
+DUMP_SAMPLE = 1 << 21      # elements: larger arrays are dumped as a fixed, seeded sample of this many
+
+
+def dump_outputs(out_dir, loss, feats, params):
+    """--dump-outputs: what the timed path computed in its last step, as float32 .npy files in `out_dir` (~48 MB):
+    loss.npy (1,), feat1.npy .. featK.npy (the backbone's maps), grad.npy and param.npy (every parameter's gradient and its
+    value after the optimizer step, flattened and concatenated in model.parameters() order; a missing gradient as zeros).
+    An array of more than DUMP_SAMPLE elements is written as the 1-D sample of the elements at DUMP_SAMPLE flat indices drawn
+    uniformly WITH replacement (an index can repeat) and sorted, by a CPU generator seeded with the file's position: the
+    same indices in every run and every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [('loss', loss.detach().reshape(1))]
+    arrays += [('feat%d' % (k + 1), f.detach()) for k, f in enumerate(feats)]
+    arrays.append(('grad', torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                      for p in params])))
+    arrays.append(('param', torch.cat([p.detach().reshape(-1).float() for p in params])))
+    for seed, (name, t) in enumerate(arrays):
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort()[0]
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
+
+
 def cpu_baseline(args, preset_kw):
     """Oracle (CPU port of the reference) on the host cores; bounded sample, same workload."""
     from oracle import cases, msda as oracle_msda, seeded, vit_adapter_ref as ref
@@ -487,10 +537,31 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
     x = torch.randn(args.batch, 3, H, W, device=dev, generator=gen)
 
-    def step():
+    last = {}       # --dump-outputs: the feature maps of the last timed step (of the captured step, which replays write)
+    # --dump-outputs: the weights and buffers as built, which every loop's timed steps start from (restart below)
+    initial = [t.detach().clone() for t in (*model.parameters(), *model.buffers())] if args.dump_outputs else None
+
+    def restart():
+        """--dump-outputs, right before the timed steps: put back the initial weights and buffers, empty the AdamW state in
+        place and reseed the CUDA generator (a replay reads its seed and offset when launched).  Whichever loop runs - replay
+        or eager, picked by the probe or pinned by --hip-graph - and however many warm-up steps it took, the timed steps
+        then compute the same thing, so two builds' dumps compare output for output."""
+        with torch.no_grad():
+            for t, t_init in zip((*model.parameters(), *model.buffers()), initial):
+                t.copy_(t_init)
+            for st in opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+        torch.manual_seed(0)
+        fence()
+
+    def step(keep=False):
         opt.zero_grad(set_to_none=True)
         with torch.autocast('cuda', dtype=amp, enabled=amp is not None):
             feats = net(x)
+        if keep:
+            last['feats'] = feats
         loss = sum(f.float().mean() for f in feats)
         loss.backward()
         if sync is not None:
@@ -555,7 +626,7 @@ def main():
                 mode = 'thread_local'
             try:
                 with torch.cuda.graph(graph, capture_error_mode=mode):
-                    graph_loss = step()
+                    graph_loss = step(keep=bool(args.dump_outputs))
             except Exception as exc:                   # noqa: BLE001 - told to the other ranks below, then handled
                 captured, why = False, exc
             torch.cuda.synchronize()
@@ -575,6 +646,8 @@ def main():
             torch.cuda.synchronize()
     if graph is not None:
         fence()
+        if args.dump_outputs:
+            restart()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             graph.replay()
@@ -582,31 +655,40 @@ def main():
         fence()
         dt = time.perf_counter() - t0
         loss = graph_loss
-        # per-kernel rows: HIP events cannot be read back from inside a graph, so K eager steps, untimed
-        _vah.prof_enable(True, args.profile_kernels)
-        for _ in range(args.steps):
-            step()
-        fence()
-        _vah.prof_enable(False)
     else:
         for _ in range(args.warmup):
             step()
         fence()
-        _vah.prof_enable(True, args.profile_kernels)
+        if args.dump_outputs:
+            restart()
+        if args.full:
+            _vah.prof_enable(True, args.profile_kernels)
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss = step()
+        for i in range(args.steps):
+            loss = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         host_dt = time.perf_counter() - t0           # the host has enqueued every step; the GPU may still be running
         fence()
         dt = time.perf_counter() - t0
-        _vah.prof_enable(False)
-    prof = _vah.prof_report()
+        if args.full:
+            _vah.prof_enable(False)
     assert torch.isfinite(loss).item(), 'loss is not finite'
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last.pop('feats'), list(model.parameters()))
+    prof = {}
+    if args.full:
+        if graph is not None:
+            # per-kernel rows: HIP events cannot be read back from inside a graph, so K eager steps, untimed
+            _vah.prof_enable(True, args.profile_kernels)
+            for _ in range(args.steps):
+                step()
+            fence()
+            _vah.prof_enable(False)
+        prof = _vah.prof_report()
     # the rest of the step by operator family (55 % of the step had no row): a few more eager steps, untimed,
     # with HIP events on every library entry point of the families below (event pairs on ~900 launches per step cost
     # host time, so never inside the timed region)
     fam_prof = {}
-    if args.family_steps > 0 and world == 1:
+    if args.full and args.family_steps > 0 and world == 1:
         _vah.prof_enable(True, FAMILY_PREFIXES)
         for _ in range(args.family_steps):
             step()
@@ -643,10 +725,14 @@ def main():
                                       'ms_per_step': round(ms / args.family_steps, 3), 'bound': 'mfma',
                                       'achieved_TFLOPs': round(fl / (ms * 1e-3) / 1e12, 1),
                                       'frac_of_mfma_peak': round(fl / (ms * 1e-3) / MFMA_PEAK, 4)}
-        if args.boundary_iters > 0 and world == 1:
+        if args.full and args.boundary_iters > 0 and world == 1:
             kernels.update(boundary_kernels(dev, args.boundary_iters))
             if args.consumer_iters > 0:
                 kernels.update(consumer_rows(dev, args.consumer_iters))
+        kernel_rows = None                              # a plain run times no kernels
+        if args.full:
+            kernel_rows = ('HIP events over %d eager steps right after the timed region (events cannot be read back from '
+                           'inside a graph)' % args.steps) if use_graph else 'HIP events inside the timed region'
         line = {
             'metric': ('images/sec ViT-Adapter-B 1024x1024 fwd+bwd (+AdamW step)' if (args.preset, H, W) == ('base_det', 1024, 1024)
                        else 'images/sec %s %dx%d fwd+bwd (+AdamW step)' % (args.preset, H, W)),
@@ -664,21 +750,20 @@ def main():
                        'global_batch': world * args.batch, 'params_M': round(n_params / 1e6, 2),
                        'parallelism': 'dp%d' % world, 'dp_mode': (args.dp_mode if dist.is_initialized() else None),
                        'hip_graph': use_graph, 'hip_graph_probe': probe,
-                       'kernel_rows': ('HIP events over %d eager steps right after the timed region (events cannot be read '
-                                       'back from inside a graph)' % args.steps) if use_graph else 'HIP events inside the timed region',
+                       'kernel_rows': kernel_rows,
                        'rccl_ranks': dist.get_world_size() if dist.is_initialized() else 1,
                        'backend': args.backend if dist.is_initialized() else None,
                        # hipBLASLt algorithms the dispatcher's whole-output check refused (csrc/gemm.hip)
                        'gemm_candidates_rejected': int(_vah.lib.vah_gemm_rejected_candidates())},
-            'roofline': roofline,
-            'kernels': kernels,
         }
-        mode = args.cpu_baseline
-        if mode == 'auto':
-            mode = 'full' if world == 1 else 'none'
-        if mode != 'none':
-            args.cpu_baseline = mode
-            line['cpu_baseline'] = cpu_baseline(args, preset_kw)
+        if args.full:
+            line.update(roofline=roofline, kernels=kernels)
+            mode = args.cpu_baseline
+            if mode == 'auto':
+                mode = 'full' if world == 1 else 'none'
+            if mode != 'none':
+                args.cpu_baseline = mode
+                line['cpu_baseline'] = cpu_baseline(args, preset_kw)
         print(json.dumps(line), flush=True)
     if world > 1:
         dp.barrier()

@@ -20,7 +20,7 @@ for c in cfg3_inj cfg3_ext cfg1 cfg5_pixdec; do
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats/plain_$c -- python $R/tools/prof_msda_plain.py $c 5 > $OUT/stats_plain_$c.log 2>&1 || exit 1
 done
 echo "stats done"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats/bench -- python $R/bench.py --steps 10 --warmup 3 --cpu-baseline none --boundary-iters 0 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats/bench -- python $R/bench.py --full --steps 10 --warmup 3 --cpu-baseline none --boundary-iters 0 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || exit 1
 cd $R
 python tools/pmc_msda_summary.py $OUT/pmc 3 > $OUT/r03_msda_pmc.json
 python tools/kstats.py $OUT/stats msda > $OUT/r03_msda_kernel_stats.txt
