@@ -190,7 +190,7 @@ int vah_msda_fused_backward_tiled(const void *value, int value_dtype, const int6
                                   void *ws, int64_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
- * Softmax attention of the ViT blocks, bf16, head_dim 64  
+ * Softmax attention of the ViT blocks, bf16 (fp16 twins: *_f16, below), head_dim 64  
  *
  * Replaces the score / softmax / value products of the reference's Attention and
  * WindowedAttention (/root/reference/detection/mmdet_custom/models/backbones/base/vit.py:83-88
@@ -238,7 +238,8 @@ int vah_attn_bwd_bf16(const void *q, const void *k, const void *v, int64_t ld, i
  * bias: bf16 (heads, N, ldb), the bias TIMES log2(e), ldb a multiple of 64 >= N (columns beyond N ignored);
  * bias_t: the same matrix transposed per head ((heads, N keys, ldb queries)); ds_out (B, heads, N, ldb) bf16 receives
  * d loss / d bias of every image (sum over B = the bias gradient; columns beyond N undefined);
- * delta_ws: B * heads * N floats.  Same kernels as vah_attn_*_bf16 (csrc/attn_flash.hip). */
+ * delta_ws: B * heads * N floats.  Same kernels as vah_attn_*_bf16 (csrc/attn_flash.hip).  Profiler rows
+ * "attn_bias_fwd_bf16" and "attn_bias_bwd_bf16" (the latter encloses its kernels' attn_bwd_dq_bf16 / attn_bwd_dkdv_bf16 rows). */
 int vah_attn_bias_fwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, int64_t B, int64_t H,
                            int64_t N, float scale, const void *bias, int64_t ldb, void *out, int64_t ld_out, float *lse,
                            void *stream);
@@ -262,6 +263,40 @@ int vah_attn_win_bwd_bf16(const void *q, const void *k, const void *v, int64_t l
                           const void *out, const void *dout, int64_t ld_out, const float *lse,
                           int64_t B, int64_t grid_h, int64_t grid_w, int64_t win, int64_t H, float scale,
                           void *ws, void *dq, void *dk, void *dv, int64_t ld_d, void *stream);
+
+/* fp16 twins of the attention entry points above, for fp16 autocast (the reference configs' fp16 AMP): q, k, v, out,
+ * dout, dq, dk, dv and - in the bias / relpos calls - bias, bias_t and ds_out are IEEE fp16 instead of bf16.  Same
+ * kernels instantiated on _Float16 (v_mfma_f32_32x32x16_f16), same signatures, argument checks, error codes and
+ * workspace sizes (vah_attn_padded_len, vah_attn_bwd_workspace_bytes, vah_relpos_bias_grad_ws_floats are shared).
+ * Scores, softmax statistics, lse, delta and accumulators stay fp32; only P (forward) and dS (backward) are rounded to
+ * fp16 as MFMA operands, so no score can overflow fp16's range.  Profiler rows carry an _f16 suffix
+ * ("attn_fwd_f16", "attn_win_bwd_f16", "relpos_bias_build_f16", ...). */
+int vah_attn_fwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
+                     int64_t B, int64_t H, int64_t N, float scale, void *vt_ws,
+                     void *out, int64_t ld_out, float *lse, void *stream);
+int vah_attn_bwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
+                     const void *out, const void *dout, int64_t ld_out, const float *lse,
+                     int64_t B, int64_t H, int64_t N, float scale, void *ws,
+                     void *dq, void *dk, void *dv, int64_t ld_d, int64_t batch_stride_d,
+                     void *stream);
+int vah_attn_win_fwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t B,
+                         int64_t grid_h, int64_t grid_w, int64_t win, int64_t H, float scale,
+                         void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream);
+int vah_attn_win_bwd_f16(const void *q, const void *k, const void *v, int64_t ld,
+                         const void *out, const void *dout, int64_t ld_out, const float *lse,
+                         int64_t B, int64_t grid_h, int64_t grid_w, int64_t win, int64_t H, float scale,
+                         void *ws, void *dq, void *dk, void *dv, int64_t ld_d, void *stream);
+int vah_attn_bias_fwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, int64_t B, int64_t H,
+                          int64_t N, float scale, const void *bias, int64_t ldb, void *out, int64_t ld_out, float *lse,
+                          void *stream);
+int vah_attn_bias_bwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, const void *out,
+                          const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t H, int64_t N, float scale,
+                          const void *bias, const void *bias_t, int64_t ldb, void *ds_out, float *delta_ws, void *dq, void *dk,
+                          void *dv, int64_t ld_d, int64_t batch_stride_d, void *stream);
+int vah_relpos_bias_build_f16(const float *table, const int64_t *index, int64_t T, int64_t H, int64_t N, int64_t ldb, void *bias,
+                              void *bias_t, void *stream);
+int vah_relpos_bias_grad_f16(const void *ds, const int64_t *index, int64_t B, int64_t H, int64_t N, int64_t ldb, int64_t T, float *ws,
+                             float *dtable, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused memory-bound operators of the blocks.  They replace

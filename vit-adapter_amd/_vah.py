@@ -14,7 +14,7 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libvitadapter_hip.so')
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -65,6 +65,12 @@ lib.vah_attn_win_fwd_bf16.restype = ctypes.c_int
 lib.vah_attn_win_bwd_bf16.argtypes = [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, ctypes.c_float,
                                       _p, _p, _p, _p, _i64, _p]
 lib.vah_attn_win_bwd_bf16.restype = ctypes.c_int
+# fp16 twins of the attention entry points: the bf16 signatures with the element type of the 16-bit operands changed
+for _n in ('vah_attn_fwd', 'vah_attn_bwd', 'vah_attn_win_fwd', 'vah_attn_win_bwd', 'vah_attn_bias_fwd', 'vah_attn_bias_bwd'):
+    _b16, _f16 = getattr(lib, _n + '_bf16'), getattr(lib, _n + '_f16')
+    _f16.argtypes, _f16.restype = _b16.argtypes, ctypes.c_int
+for _n in ('vah_relpos_bias_build', 'vah_relpos_bias_grad'):
+    getattr(lib, _n + '_f16').argtypes, getattr(lib, _n + '_f16').restype = getattr(lib, _n).argtypes, ctypes.c_int
 _ci = ctypes.c_int
 lib.vah_msda_fused_supported.argtypes = [_i64, _i64, _i64]
 lib.vah_msda_fused_supported.restype = ctypes.c_int
@@ -164,6 +170,8 @@ EXPORTS = (
     'vah_pixel_shuffle2_bf16', 'vah_patchify_bf16', 'vah_attn_bias_fwd_bf16', 'vah_attn_bias_bwd_bf16', 'vah_relpos_bias_build', 'vah_relpos_bias_grad_ws_floats',
     'vah_relpos_bias_grad', 'vah_attn_padded_len', 'vah_attn_fwd_bf16', 'vah_attn_bwd_workspace_bytes', 'vah_attn_bwd_bf16',
     'vah_attn_win_fwd_bf16', 'vah_attn_win_bwd_bf16',
+    'vah_attn_fwd_f16', 'vah_attn_bwd_f16', 'vah_attn_win_fwd_f16', 'vah_attn_win_bwd_f16', 'vah_attn_bias_fwd_f16',
+    'vah_attn_bias_bwd_f16', 'vah_relpos_bias_build_f16', 'vah_relpos_bias_grad_f16',
     'vah_reduce_ws_floats', 'vah_layernorm_fwd_f32_bf16', 'vah_layernorm_bwd_f32_bf16', 'vah_scale_residual_fwd',
     'vah_scale_residual_bwd', 'vah_dwconv3x3_tokens_bf16', 'vah_dwconv3x3_tokens_wgrad_bf16', 'vah_colsum_bf16', 'vah_colsum_f32',
     'vah_layernorm_dual_fwd', 'vah_layernorm_dual_bwd',

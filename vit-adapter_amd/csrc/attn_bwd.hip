@@ -1,4 +1,4 @@
-// Fused softmax attention backward for gfx950 (bf16, head_dim 64): gradients of
+// Fused softmax attention backward for gfx950 (bf16 or fp16: T, attn_common.h; head_dim 64): gradients of
 //   out = softmax(q k^T * scale) v
 // w.r.t. q, k, v, written straight into a packed (B, N, 3, heads, 64) gradient buffer.
 //
@@ -25,11 +25,12 @@ namespace {
 // Backward prologue in ONE launch: K^T, Q^T, dO^T (64-token tiles) and, from the dO tile it already
 // holds, delta = rowsum(dO * O).  Four small launches before (3 transposes + delta): on the 196-token
 // windows they cost as much as the dQ kernel itself.
+template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd_prologue_kernel(
-    const __bf16 *__restrict__ q, const __bf16 *__restrict__ k, int64_t ld, const __bf16 *__restrict__ o,
-    const __bf16 *__restrict__ d_o, int64_t ld_out, RowMap rm, int N, int Np, int H, __bf16 *__restrict__ kt,
-    __bf16 *__restrict__ qt, __bf16 *__restrict__ dot, float *__restrict__ delta) {
-    __shared__ __attribute__((aligned(16))) __bf16 tile[64 * kPadRow];
+    const T *__restrict__ q, const T *__restrict__ k, int64_t ld, const T *__restrict__ o,
+    const T *__restrict__ d_o, int64_t ld_out, RowMap rm, int N, int Np, int H, T *__restrict__ kt,
+    T *__restrict__ qt, T *__restrict__ dot, float *__restrict__ delta) {
+    __shared__ __attribute__((aligned(16))) T tile[64 * kPadRow];
     const int ntile = Np / 64;
     const int which = blockIdx.x / ntile, n0 = (blockIdx.x - which * ntile) * 64;
     const int h = blockIdx.y, b = blockIdx.z;
@@ -45,12 +46,12 @@ __global__ __launch_bounds__(256) void attn_bwd_prologue_kernel(
         float acc = 0.f;
         const int64_t gr = n < N ? grow(rm, b, n, N) : -1;
         if (gr >= 0) {
-            const __bf16 *po = o + gr * ld_out + (int64_t)h * kHD + part * 16;
-            const __bf16 *pd = tile + row * kPadRow + part * 16;
+            const T *po = o + gr * ld_out + (int64_t)h * kHD + part * 16;
+            const T *pd = tile + row * kPadRow + part * 16;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8 *>(po + 8 * c);
-                const bf16x8 g = *reinterpret_cast<const bf16x8 *>(pd + 8 * c);
+                const vec8<T> a = *reinterpret_cast<const vec8<T> *>(po + 8 * c);
+                const vec8<T> g = *reinterpret_cast<const vec8<T> *>(pd + 8 * c);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc += (float)a[j] * (float)g[j];
             }
@@ -64,15 +65,16 @@ __global__ __launch_bounds__(256) void attn_bwd_prologue_kernel(
 // ---------------------------------------------------------------------------------------
 // dQ: workgroup = 128 queries, loop over key tiles of 64
 // ---------------------------------------------------------------------------------------
+template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
-    const __bf16 *__restrict__ q, const __bf16 *__restrict__ k, const __bf16 *__restrict__ v,
-    const __bf16 *__restrict__ kt, const __bf16 *__restrict__ d_o, int64_t ld, RowMap rm,
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
+    const T *__restrict__ kt, const T *__restrict__ d_o, int64_t ld, RowMap rm,
     int64_t ld_out, const float *__restrict__ lse, const float *__restrict__ delta, int N, int Np,
-    int H, float scale, float scale_log2, __bf16 *__restrict__ dq, int64_t ld_d) {
+    int H, float scale, float scale_log2, T *__restrict__ dq, int64_t ld_d) {
     // double buffered (one barrier per key tile)
-    __shared__ __attribute__((aligned(16))) __bf16 s_k2[2][64 * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_v2[2][64 * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_kt2[2][kHD * kPadT];
+    __shared__ __attribute__((aligned(16))) T s_k2[2][64 * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_v2[2][64 * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_kt2[2][kHD * kPadT];
 
     const int h = blockIdx.y, b = blockIdx.z;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -80,21 +82,21 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
     const int qrow = blockIdx.x * 128 + wave * 32 + r;
     const int qload = min(qrow, N - 1);
 
-    const __bf16 *qb = q + (int64_t)h * kHD;
-    const __bf16 *kb = k + (int64_t)h * kHD;
-    const __bf16 *vb = v + (int64_t)h * kHD;
-    const __bf16 *ktb = kt + ((int64_t)(b * H + h) * kHD) * Np;
-    const __bf16 *dob = d_o + (int64_t)h * kHD;
+    const T *qb = q + (int64_t)h * kHD;
+    const T *kb = k + (int64_t)h * kHD;
+    const T *vb = v + (int64_t)h * kHD;
+    const T *ktb = kt + ((int64_t)(b * H + h) * kHD) * Np;
+    const T *dob = d_o + (int64_t)h * kHD;
     const int64_t gq = grow(rm, b, qload, N);
 
-    bf16x8 qf[4], dof[4];
+    vec8<T> qf[4], dof[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) qf[kk][j] = dof[kk][j] = (__bf16)0.f;
+        for (int j = 0; j < 8; ++j) qf[kk][j] = dof[kk][j] = (T)0.f;
         if (gq >= 0) {
-            qf[kk] = *reinterpret_cast<const bf16x8 *>(qb + gq * ld + 16 * kk + 8 * hf);
-            dof[kk] = *reinterpret_cast<const bf16x8 *>(dob + gq * ld_out + 16 * kk + 8 * hf);
+            qf[kk] = *reinterpret_cast<const vec8<T> *>(qb + gq * ld + 16 * kk + 8 * hf);
+            dof[kk] = *reinterpret_cast<const vec8<T> *>(dob + gq * ld_out + 16 * kk + 8 * hf);
         }
     }
     const float lse_q = lse[((int64_t)b * H + h) * N + qload];
@@ -103,34 +105,34 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
 
     const int c0 = threadIdx.x, c1 = threadIdx.x + 256;
     const int r0 = c0 >> 3, x0 = (c0 & 7) * 8, r1 = c1 >> 3, x1 = (c1 & 7) * 8;
-    bf16x8 pk0, pk1, pv0, pv1, pt0, pt1;
+    vec8<T> pk0, pk1, pv0, pv1, pt0, pt1;
     auto fetch = [&](int key0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) pk0[j] = pk1[j] = pv0[j] = pv1[j] = (__bf16)0.f;
+        for (int j = 0; j < 8; ++j) pk0[j] = pk1[j] = pv0[j] = pv1[j] = (T)0.f;
         const int64_t g0 = key0 + r0 < N ? grow(rm, b, key0 + r0, N) : -1;
         const int64_t g1 = key0 + r1 < N ? grow(rm, b, key0 + r1, N) : -1;
         if (g0 >= 0) {
-            pk0 = *reinterpret_cast<const bf16x8 *>(kb + g0 * ld + x0);
-            pv0 = *reinterpret_cast<const bf16x8 *>(vb + g0 * ld + x0);
+            pk0 = *reinterpret_cast<const vec8<T> *>(kb + g0 * ld + x0);
+            pv0 = *reinterpret_cast<const vec8<T> *>(vb + g0 * ld + x0);
         }
         if (g1 >= 0) {
-            pk1 = *reinterpret_cast<const bf16x8 *>(kb + g1 * ld + x1);
-            pv1 = *reinterpret_cast<const bf16x8 *>(vb + g1 * ld + x1);
+            pk1 = *reinterpret_cast<const vec8<T> *>(kb + g1 * ld + x1);
+            pv1 = *reinterpret_cast<const vec8<T> *>(vb + g1 * ld + x1);
         }
-        pt0 = *reinterpret_cast<const bf16x8 *>(ktb + (int64_t)r0 * Np + key0 + x0);
-        pt1 = *reinterpret_cast<const bf16x8 *>(ktb + (int64_t)r1 * Np + key0 + x1);
+        pt0 = *reinterpret_cast<const vec8<T> *>(ktb + (int64_t)r0 * Np + key0 + x0);
+        pt1 = *reinterpret_cast<const vec8<T> *>(ktb + (int64_t)r1 * Np + key0 + x1);
     };
     auto commit = [&](int buf) {
-        __bf16 *s_k = s_k2[buf], *s_v = s_v2[buf], *s_kt = s_kt2[buf];
-        *reinterpret_cast<bf16x8 *>(s_k + r0 * kPadRow + x0) = pk0;
-        *reinterpret_cast<bf16x8 *>(s_k + r1 * kPadRow + x1) = pk1;
-        *reinterpret_cast<bf16x8 *>(s_v + r0 * kPadRow + x0) = pv0;
-        *reinterpret_cast<bf16x8 *>(s_v + r1 * kPadRow + x1) = pv1;
-        const bf16x4 *a0 = reinterpret_cast<const bf16x4 *>(&pt0), *a1 = reinterpret_cast<const bf16x4 *>(&pt1);
-        *reinterpret_cast<bf16x4 *>(s_kt + r0 * kPadT + x0) = a0[0];
-        *reinterpret_cast<bf16x4 *>(s_kt + r0 * kPadT + x0 + 4) = a0[1];
-        *reinterpret_cast<bf16x4 *>(s_kt + r1 * kPadT + x1) = a1[0];
-        *reinterpret_cast<bf16x4 *>(s_kt + r1 * kPadT + x1 + 4) = a1[1];
+        T *s_k = s_k2[buf], *s_v = s_v2[buf], *s_kt = s_kt2[buf];
+        *reinterpret_cast<vec8<T> *>(s_k + r0 * kPadRow + x0) = pk0;
+        *reinterpret_cast<vec8<T> *>(s_k + r1 * kPadRow + x1) = pk1;
+        *reinterpret_cast<vec8<T> *>(s_v + r0 * kPadRow + x0) = pv0;
+        *reinterpret_cast<vec8<T> *>(s_v + r1 * kPadRow + x1) = pv1;
+        const vec4<T> *a0 = reinterpret_cast<const vec4<T> *>(&pt0), *a1 = reinterpret_cast<const vec4<T> *>(&pt1);
+        *reinterpret_cast<vec4<T> *>(s_kt + r0 * kPadT + x0) = a0[0];
+        *reinterpret_cast<vec4<T> *>(s_kt + r0 * kPadT + x0 + 4) = a0[1];
+        *reinterpret_cast<vec4<T> *>(s_kt + r1 * kPadT + x1) = a1[0];
+        *reinterpret_cast<vec4<T> *>(s_kt + r1 * kPadT + x1 + 4) = a1[1];
     };
 
     const int ntiles = (N + 63) / 64;
@@ -143,15 +145,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
             commit((t + 1) & 1);
             if (t + 2 < ntiles) fetch((t + 2) * 64);
         }
-        const __bf16 *s_k = s_k2[t & 1], *s_v = s_v2[t & 1], *s_kt = s_kt2[t & 1];
+        const T *s_k = s_k2[t & 1], *s_v = s_v2[t & 1], *s_kt = s_kt2[t & 1];
         const int key0 = t * 64;
 #pragma unroll
         for (int kbk = 0; kbk < 2; ++kbk) {
             f32x16 s = zero16(), dp = zero16();
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                const bf16x8 ak = *reinterpret_cast<const bf16x8 *>(s_k + (kbk * 32 + r) * kPadRow + 16 * kk + 8 * hf);
-                const bf16x8 av = *reinterpret_cast<const bf16x8 *>(s_v + (kbk * 32 + r) * kPadRow + 16 * kk + 8 * hf);
+                const vec8<T> ak = *reinterpret_cast<const vec8<T> *>(s_k + (kbk * 32 + r) * kPadRow + 16 * kk + 8 * hf);
+                const vec8<T> av = *reinterpret_cast<const vec8<T> *>(s_v + (kbk * 32 + r) * kPadRow + 16 * kk + 8 * hf);
                 s = mfma(ak, qf[kk], s);
                 dp = mfma(av, dof[kk], dp);
             }
@@ -163,25 +165,25 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
             }
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) {
-                const bf16x8 pf = pack_half(s, sp);
+                const vec8<T> pf = pack_half<T>(s, sp);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 a = load_kperm(s_kt + (db * 32 + r) * kPadT + kbk * 32, sp, hf);
+                    const vec8<T> a = load_kperm(s_kt + (db * 32 + r) * kPadT + kbk * 32, sp, hf);
                     acc[db] = mfma(a, pf, acc[db]);
                 }
             }
         }
     }
     if (qrow < N && gq >= 0) {
-        __bf16 *op = dq + gq * ld_d + (int64_t)h * kHD;
+        T *op = dq + gq * ld_d + (int64_t)h * kHD;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 w;
+                vec4<T> w;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w[j] = (__bf16)(acc[db][4 * g + j] * scale);
-                *reinterpret_cast<bf16x4 *>(op + db * 32 + 8 * g + 4 * hf) = w;
+                for (int j = 0; j < 4; ++j) w[j] = (T)(acc[db][4 * g + j] * scale);
+                *reinterpret_cast<vec4<T> *>(op + db * 32 + 8 * g + 4 * hf) = w;
             }
     }
 }
@@ -189,17 +191,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
 // ---------------------------------------------------------------------------------------
 // dK, dV: workgroup = 128 keys, loop over query tiles of 32
 // ---------------------------------------------------------------------------------------
+template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(
-    const __bf16 *__restrict__ q, const __bf16 *__restrict__ k, const __bf16 *__restrict__ v,
-    const __bf16 *__restrict__ qt, const __bf16 *__restrict__ d_o, const __bf16 *__restrict__ dot,
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
+    const T *__restrict__ qt, const T *__restrict__ d_o, const T *__restrict__ dot,
     int64_t ld, RowMap rm, int64_t ld_out, const float *__restrict__ lse,
     const float *__restrict__ delta, int N, int Np, int H, float scale, float scale_log2,
-    __bf16 *__restrict__ dk, __bf16 *__restrict__ dv, int64_t ld_d) {
+    T *__restrict__ dk, T *__restrict__ dv, int64_t ld_d) {
     // double buffered (one barrier per query tile)
-    __shared__ __attribute__((aligned(16))) __bf16 s_q2[2][32 * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_do2[2][32 * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_qt2[2][kHD * kPadT32];
-    __shared__ __attribute__((aligned(16))) __bf16 s_dot2[2][kHD * kPadT32];
+    __shared__ __attribute__((aligned(16))) T s_q2[2][32 * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_do2[2][32 * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_qt2[2][kHD * kPadT32];
+    __shared__ __attribute__((aligned(16))) T s_dot2[2][kHD * kPadT32];
     __shared__ __attribute__((aligned(16))) float s_lse2[2][32];
     __shared__ __attribute__((aligned(16))) float s_delta2[2][32];
 
@@ -213,23 +216,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(
     // only its gradient has nowhere to go
     const bool key_live = krow < N;
 
-    const __bf16 *qb = q + (int64_t)h * kHD;
-    const __bf16 *kb = k + (int64_t)h * kHD;
-    const __bf16 *vb = v + (int64_t)h * kHD;
-    const __bf16 *qtb = qt + ((int64_t)(b * H + h) * kHD) * Np;
-    const __bf16 *dotb = dot + ((int64_t)(b * H + h) * kHD) * Np;
-    const __bf16 *dob = d_o + (int64_t)h * kHD;
+    const T *qb = q + (int64_t)h * kHD;
+    const T *kb = k + (int64_t)h * kHD;
+    const T *vb = v + (int64_t)h * kHD;
+    const T *qtb = qt + ((int64_t)(b * H + h) * kHD) * Np;
+    const T *dotb = dot + ((int64_t)(b * H + h) * kHD) * Np;
+    const T *dob = d_o + (int64_t)h * kHD;
     const float *lseb = lse + ((int64_t)b * H + h) * N;
     const float *delb = delta + ((int64_t)b * H + h) * N;
 
-    bf16x8 kf[4], vf[4];
+    vec8<T> kf[4], vf[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) kf[kk][j] = vf[kk][j] = (__bf16)0.f;
+        for (int j = 0; j < 8; ++j) kf[kk][j] = vf[kk][j] = (T)0.f;
         if (gk >= 0) {
-            kf[kk] = *reinterpret_cast<const bf16x8 *>(kb + gk * ld + 16 * kk + 8 * hf);
-            vf[kk] = *reinterpret_cast<const bf16x8 *>(vb + gk * ld + 16 * kk + 8 * hf);
+            kf[kk] = *reinterpret_cast<const vec8<T> *>(kb + gk * ld + 16 * kk + 8 * hf);
+            vf[kk] = *reinterpret_cast<const vec8<T> *>(vb + gk * ld + 16 * kk + 8 * hf);
         }
     }
     f32x16 dkt[2] = {zero16(), zero16()}, dvt[2] = {zero16(), zero16()};
@@ -238,18 +241,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(
     // Q^T, dO^T: 64 d-rows x 4 chunks of 8 queries = 256 chunks (1 per thread)
     const int rr = threadIdx.x >> 3, rx = (threadIdx.x & 7) * 8;        // row-major tiles
     const int tr = threadIdx.x >> 2, tx = (threadIdx.x & 3) * 8;        // transposed tiles
-    bf16x8 pq, pdo, pqt, pdot;
+    vec8<T> pq, pdo, pqt, pdot;
     float plse = INFINITY, pdel = 0.f;
     auto fetch = [&](int q0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) pq[j] = pdo[j] = (__bf16)0.f;
+        for (int j = 0; j < 8; ++j) pq[j] = pdo[j] = (T)0.f;
         const int64_t gr = q0 + rr < N ? grow(rm, b, q0 + rr, N) : -1;
         if (gr >= 0) {
-            pq = *reinterpret_cast<const bf16x8 *>(qb + gr * ld + rx);
-            pdo = *reinterpret_cast<const bf16x8 *>(dob + gr * ld_out + rx);
+            pq = *reinterpret_cast<const vec8<T> *>(qb + gr * ld + rx);
+            pdo = *reinterpret_cast<const vec8<T> *>(dob + gr * ld_out + rx);
         }
-        pqt = *reinterpret_cast<const bf16x8 *>(qtb + (int64_t)tr * Np + q0 + tx);
-        pdot = *reinterpret_cast<const bf16x8 *>(dotb + (int64_t)tr * Np + q0 + tx);
+        pqt = *reinterpret_cast<const vec8<T> *>(qtb + (int64_t)tr * Np + q0 + tx);
+        pdot = *reinterpret_cast<const vec8<T> *>(dotb + (int64_t)tr * Np + q0 + tx);
         if (threadIdx.x < 32) {
             const bool ok = q0 + (int)threadIdx.x < N;
             plse = ok ? lseb[q0 + threadIdx.x] : INFINITY;         // +inf -> p = 0 for padded queries
@@ -257,15 +260,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(
         }
     };
     auto commit = [&](int buf) {
-        __bf16 *s_q = s_q2[buf], *s_do = s_do2[buf], *s_qt = s_qt2[buf], *s_dot = s_dot2[buf];
+        T *s_q = s_q2[buf], *s_do = s_do2[buf], *s_qt = s_qt2[buf], *s_dot = s_dot2[buf];
         float *s_lse = s_lse2[buf], *s_delta = s_delta2[buf];
-        *reinterpret_cast<bf16x8 *>(s_q + rr * kPadRow + rx) = pq;
-        *reinterpret_cast<bf16x8 *>(s_do + rr * kPadRow + rx) = pdo;
-        const bf16x4 *a = reinterpret_cast<const bf16x4 *>(&pqt), *g = reinterpret_cast<const bf16x4 *>(&pdot);
-        *reinterpret_cast<bf16x4 *>(s_qt + tr * kPadT32 + tx) = a[0];
-        *reinterpret_cast<bf16x4 *>(s_qt + tr * kPadT32 + tx + 4) = a[1];
-        *reinterpret_cast<bf16x4 *>(s_dot + tr * kPadT32 + tx) = g[0];
-        *reinterpret_cast<bf16x4 *>(s_dot + tr * kPadT32 + tx + 4) = g[1];
+        *reinterpret_cast<vec8<T> *>(s_q + rr * kPadRow + rx) = pq;
+        *reinterpret_cast<vec8<T> *>(s_do + rr * kPadRow + rx) = pdo;
+        const vec4<T> *a = reinterpret_cast<const vec4<T> *>(&pqt), *g = reinterpret_cast<const vec4<T> *>(&pdot);
+        *reinterpret_cast<vec4<T> *>(s_qt + tr * kPadT32 + tx) = a[0];
+        *reinterpret_cast<vec4<T> *>(s_qt + tr * kPadT32 + tx + 4) = a[1];
+        *reinterpret_cast<vec4<T> *>(s_dot + tr * kPadT32 + tx) = g[0];
+        *reinterpret_cast<vec4<T> *>(s_dot + tr * kPadT32 + tx + 4) = g[1];
         if (threadIdx.x < 32) {
             s_lse[threadIdx.x] = plse;
             s_delta[threadIdx.x] = pdel;
@@ -282,14 +285,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(
             commit((t + 1) & 1);
             if (t + 2 < ntiles) fetch((t + 2) * 32);
         }
-        const __bf16 *s_q = s_q2[t & 1], *s_do = s_do2[t & 1], *s_qt = s_qt2[t & 1], *s_dot = s_dot2[t & 1];
+        const T *s_q = s_q2[t & 1], *s_do = s_do2[t & 1], *s_qt = s_qt2[t & 1], *s_dot = s_dot2[t & 1];
         const float *s_lse = s_lse2[t & 1], *s_delta = s_delta2[t & 1];
 
         f32x16 s = zero16(), dp = zero16();
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            const bf16x8 aq = *reinterpret_cast<const bf16x8 *>(s_q + r * kPadRow + 16 * kk + 8 * hf);
-            const bf16x8 ad = *reinterpret_cast<const bf16x8 *>(s_do + r * kPadRow + 16 * kk + 8 * hf);
+            const vec8<T> aq = *reinterpret_cast<const vec8<T> *>(s_q + r * kPadRow + 16 * kk + 8 * hf);
+            const vec8<T> ad = *reinterpret_cast<const vec8<T> *>(s_do + r * kPadRow + 16 * kk + 8 * hf);
             s = mfma(aq, kf[kk], s);          // S[query (reg)][key (lane)]
             dp = mfma(ad, vf[kk], dp);        // dP[query][key]
         }
@@ -308,31 +311,31 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(
         }
 #pragma unroll
         for (int sp = 0; sp < 2; ++sp) {
-            const bf16x8 pf = pack_half(s, sp), dsf = pack_half(dp, sp);
+            const vec8<T> pf = pack_half<T>(s, sp), dsf = pack_half<T>(dp, sp);
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
-                const bf16x8 ado = load_kperm(s_dot + (db * 32 + r) * kPadT32, sp, hf);
-                const bf16x8 aq = load_kperm(s_qt + (db * 32 + r) * kPadT32, sp, hf);
+                const vec8<T> ado = load_kperm(s_dot + (db * 32 + r) * kPadT32, sp, hf);
+                const vec8<T> aq = load_kperm(s_qt + (db * 32 + r) * kPadT32, sp, hf);
                 dvt[db] = mfma(ado, pf, dvt[db]);          // dV^T[d][key] += dO^T P
                 dkt[db] = mfma(aq, dsf, dkt[db]);          // dK^T[d][key] += Q^T dS
             }
         }
     }
     if (key_live && gk >= 0) {
-        __bf16 *pk = dk + gk * ld_d + (int64_t)h * kHD;
-        __bf16 *pv = dv + gk * ld_d + (int64_t)h * kHD;
+        T *pk = dk + gk * ld_d + (int64_t)h * kHD;
+        T *pv = dv + gk * ld_d + (int64_t)h * kHD;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 wk, wv;
+                vec4<T> wk, wv;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    wk[j] = (__bf16)(dkt[db][4 * g + j] * scale);
-                    wv[j] = (__bf16)dvt[db][4 * g + j];
+                    wk[j] = (T)(dkt[db][4 * g + j] * scale);
+                    wv[j] = (T)dvt[db][4 * g + j];
                 }
-                *reinterpret_cast<bf16x4 *>(pk + db * 32 + 8 * g + 4 * hf) = wk;
-                *reinterpret_cast<bf16x4 *>(pv + db * 32 + 8 * g + 4 * hf) = wv;
+                *reinterpret_cast<vec4<T> *>(pk + db * 32 + 8 * g + 4 * hf) = wk;
+                *reinterpret_cast<vec4<T> *>(pv + db * 32 + 8 * g + 4 * hf) = wv;
             }
     }
 }
@@ -348,12 +351,16 @@ int64_t vah_attn_bwd_workspace_bytes(int64_t B, int64_t H, int64_t N) {
     return 3 * B * H * 64 * Np * 2 + (B * H * N * 4 + 15) / 16 * 16;
 }
 
-static int attn_bwd_impl(const char *fn, const void *q, const void *k, const void *v, int64_t ld,
-                         vah::attn::RowMap rm, const void *out, const void *dout, int64_t ld_out,
-                         const float *lse, int64_t B, int64_t H, int64_t N, float scale, void *ws, void *dq,
-                         void *dk, void *dv, int64_t ld_d, void *stream) {
-    using namespace vah;
-    using namespace vah::attn;
+}  // extern "C"
+
+namespace vah {
+namespace attn {
+namespace {
+
+template <typename T>
+int attn_bwd_impl(const char *fn, const void *q, const void *k, const void *v, int64_t ld, RowMap rm, const void *out,
+                  const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t H, int64_t N, float scale, void *ws,
+                  void *dq, void *dk, void *dv, int64_t ld_d, void *stream) {
     if (B < 0 || H < 1 || N < 0 || ld < H * kHD || ld_out < H * kHD || ld_d < H * kHD || B > 65535 || H > 65535)
         return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (B == 0 || N == 0) return VAH_OK;
@@ -366,17 +373,17 @@ static int attn_bwd_impl(const char *fn, const void *q, const void *k, const voi
     hipStream_t st = (hipStream_t)stream;
     // whole sequences: the lean kernels of attn_flash.hip (no transposed copies; of ws only B*H*N floats for delta)
     if (rm.win == 0)
-        return attn_bwd_seq(q, k, v, ld, out, dout, ld_out, lse, B, H, N, scale, nullptr, nullptr, 0, nullptr, (float *)ws, dq, dk, dv,
-                            ld_d, st);
+        return attn_bwd_seq<T>(q, k, v, ld, out, dout, ld_out, lse, B, H, N, scale, nullptr, nullptr, 0, nullptr, (float *)ws, dq, dk,
+                               dv, ld_d, st);
     const int Np = (int)((N + 63) / 64 * 64);
     const int64_t tsz = B * H * 64 * (int64_t)Np;
-    __bf16 *kt = (__bf16 *)ws, *qt = kt + tsz, *dot = qt + tsz;
+    T *kt = (T *)ws, *qt = kt + tsz, *dot = qt + tsz;
     float *delta = (float *)(dot + tsz);
     const dim3 tg(Np / 64, (unsigned)H, (unsigned)B);
     {
-        LaunchScope scope("attn_transpose_bf16", 3 * 2 * B * H * N * kHD * 2, st);
-        hipLaunchKernelGGL(attn_bwd_prologue_kernel, dim3(3 * tg.x, tg.y, tg.z), dim3(256), 0, st, (const __bf16 *)q,
-                           (const __bf16 *)k, ld, (const __bf16 *)out, (const __bf16 *)dout, ld_out, rm, (int)N, Np,
+        LaunchScope scope(tname<T>("attn_transpose_bf16", "attn_transpose_f16"), 3 * 2 * B * H * N * kHD * 2, st);
+        hipLaunchKernelGGL((attn_bwd_prologue_kernel<T>), dim3(3 * tg.x, tg.y, tg.z), dim3(256), 0, st, (const T *)q,
+                           (const T *)k, ld, (const T *)out, (const T *)dout, ld_out, rm, (int)N, Np,
                            (int)H, kt, qt, dot, delta);
         if (int rc = check_launch(fn)) return rc;
     }
@@ -385,42 +392,38 @@ static int attn_bwd_impl(const char *fn, const void *q, const void *k, const voi
     {
         // useful flops of the whole backward = 2.5x the forward (S, dP, dV, dK, dQ products); both kernels
         // recompute S and dP: dq runs 3 products (6 B H N^2 64), dkdv 4 (8 B H N^2 64)
-        LaunchScope scope(rm.win ? "attn_win_bwd_dq_bf16" : "attn_bwd_dq_bf16", 6 * B * H * N * kHD * 2, st, 0,
-                          6 * B * H * N * N * kHD);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                           (const __bf16 *)v, kt, (const __bf16 *)dout, ld, rm, ld_out, lse, delta,
-                           (int)N, Np, (int)H, scale, scale_log2, (__bf16 *)dq, ld_d);
+        LaunchScope scope(rm.win ? tname<T>("attn_win_bwd_dq_bf16", "attn_win_bwd_dq_f16") : tname<T>("attn_bwd_dq_bf16", "attn_bwd_dq_f16"),
+                          6 * B * H * N * kHD * 2, st, 0, 6 * B * H * N * N * kHD);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<T>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                           (const T *)v, kt, (const T *)dout, ld, rm, ld_out, lse, delta,
+                           (int)N, Np, (int)H, scale, scale_log2, (T *)dq, ld_d);
         if (int rc = check_launch(fn)) return rc;
     }
-    LaunchScope scope(rm.win ? "attn_win_bwd_dkdv_bf16" : "attn_bwd_dkdv_bf16", 8 * B * H * N * kHD * 2, st, 0,
-                      8 * B * H * N * N * kHD);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                       (const __bf16 *)v, qt, (const __bf16 *)dout, dot, ld, rm, ld_out, lse, delta,
-                       (int)N, Np, (int)H, scale, scale_log2, (__bf16 *)dk, (__bf16 *)dv, ld_d);
+    LaunchScope scope(rm.win ? tname<T>("attn_win_bwd_dkdv_bf16", "attn_win_bwd_dkdv_f16") : tname<T>("attn_bwd_dkdv_bf16", "attn_bwd_dkdv_f16"),
+                      8 * B * H * N * kHD * 2, st, 0, 8 * B * H * N * N * kHD);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                       (const T *)v, qt, (const T *)dout, dot, ld, rm, ld_out, lse, delta,
+                       (int)N, Np, (int)H, scale, scale_log2, (T *)dk, (T *)dv, ld_d);
     return check_launch(fn);
 }
 
-int vah_attn_bwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
-                      const void *out, const void *dout, int64_t ld_out, const float *lse, int64_t B,
-                      int64_t H, int64_t N, float scale, void *ws, void *dq, void *dk, void *dv,
-                      int64_t ld_d, int64_t batch_stride_d, void *stream) {
-    using namespace vah;
+template <typename T>
+int attn_bwd_entry(const char *fn, const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, const void *out,
+                   const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t H, int64_t N, float scale, void *ws,
+                   void *dq, void *dk, void *dv, int64_t ld_d, int64_t batch_stride_d, void *stream) {
     clear_error();
-    const char *fn = "vah_attn_bwd_bf16";
     if (N > 0 && (batch_stride != N * ld || batch_stride_d != N * ld_d))
         return fail(VAH_E_SHAPE, "%s: batch strides must be N*ld", fn);
-    return attn_bwd_impl(fn, q, k, v, ld, attn::RowMap{0, 0, 0, 0, 0}, out, dout, ld_out, lse, B, H, N, scale, ws,
-                         dq, dk, dv, ld_d, stream);
+    return attn_bwd_impl<T>(fn, q, k, v, ld, RowMap{0, 0, 0, 0, 0}, out, dout, ld_out, lse, B, H, N, scale, ws, dq, dk, dv, ld_d,
+                            stream);
 }
 
-int vah_attn_bias_bwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, const void *out,
-                           const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t H, int64_t N, float scale,
-                           const void *bias, const void *bias_t, int64_t ldb, void *ds_out, float *delta_ws, void *dq, void *dk,
-                           void *dv, int64_t ld_d, int64_t batch_stride_d, void *stream) {
-    using namespace vah;
-    using namespace vah::attn;
+template <typename T>
+int attn_bias_bwd_entry(const char *fn, const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
+                        const void *out, const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t H, int64_t N,
+                        float scale, const void *bias, const void *bias_t, int64_t ldb, void *ds_out, float *delta_ws, void *dq,
+                        void *dk, void *dv, int64_t ld_d, int64_t batch_stride_d, void *stream) {
     clear_error();
-    const char *fn = "vah_attn_bias_bwd_bf16";
     if (N > 0 && (batch_stride != N * ld || batch_stride_d != N * ld_d)) return fail(VAH_E_SHAPE, "%s: batch strides must be N*ld", fn);
     if (B < 0 || H < 1 || N < 0 || ld < H * kHD || ld_out < H * kHD || ld_d < H * kHD || B > 65535 || H > 65535 || N >= (1 << 24) ||
         ldb < N || ldb % 64)
@@ -431,37 +434,95 @@ int vah_attn_bias_bwd_bf16(const void *q, const void *k, const void *v, int64_t 
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dout) % 16 || (ld % 8) || (ld_out % 8) || (ld_d % 4) ||
         ((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)bias | (uintptr_t)bias_t | (uintptr_t)ds_out) % 8)
         return fail(VAH_E_ALIGN, "%s: misaligned operand", fn);
-    return attn_bwd_seq(q, k, v, ld, out, dout, ld_out, lse, B, H, N, scale, bias, bias_t, ldb, ds_out, delta_ws, dq, dk, dv, ld_d,
-                        (hipStream_t)stream);
+    // the whole call (its two kernels also report as attn_bwd_dq_* / attn_bwd_dkdv_*): q, k, v, out, dout in, dq, dk, dv out,
+    // bias and bias_t in, ds_out out; flops as the plain backward's
+    LaunchScope scope(tname<T>("attn_bias_bwd_bf16", "attn_bias_bwd_f16"),
+                      8 * B * H * N * kHD * 2 + B * H * N * 4 + 2 * H * N * N * 2 + B * H * N * N * 2, (hipStream_t)stream, 0,
+                      10 * B * H * N * N * kHD);
+    return attn_bwd_seq<T>(q, k, v, ld, out, dout, ld_out, lse, B, H, N, scale, bias, bias_t, ldb, ds_out, delta_ws, dq, dk, dv, ld_d,
+                           (hipStream_t)stream);
 }
 
-int vah_attn_win_bwd_bf16(const void *q, const void *k, const void *v, int64_t ld, const void *out,
-                          const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t grid_h,
-                          int64_t grid_w, int64_t win, int64_t H, float scale, void *ws, void *dq,
-                          void *dk, void *dv, int64_t ld_d, void *stream) {
-    using namespace vah;
+template <typename T>
+int attn_win_bwd_entry(const char *fn, const void *q, const void *k, const void *v, int64_t ld, const void *out, const void *dout,
+                       int64_t ld_out, const float *lse, int64_t B, int64_t grid_h, int64_t grid_w, int64_t win, int64_t H,
+                       float scale, void *ws, void *dq, void *dk, void *dv, int64_t ld_d, void *stream) {
     clear_error();
-    const char *fn = "vah_attn_win_bwd_bf16";
-    attn::RowMap rm;
+    RowMap rm;
     int64_t Z = 0, N = 0;
     if (win < 1) return fail(VAH_E_SHAPE, "%s: win must be >= 1", fn);
-    if (int rc = attn::make_rowmap(fn, win, B, grid_h, grid_w, &Z, &N, &rm)) return rc;
+    if (int rc = make_rowmap(fn, win, B, grid_h, grid_w, &Z, &N, &rm)) return rc;
     // windows of <= 224 tokens: one kernel, one workgroup per (window, head), everything resident (attn_win.hip);
     // ws unused
-    if (N <= 224 && Z >= 1 && Z <= 65535 && H >= 1 && H <= 65535 && ld >= H * attn::kHD && ld_out >= H * attn::kHD &&
-        ld_d >= H * attn::kHD) {
+    if (N <= 224 && Z >= 1 && Z <= 65535 && H >= 1 && H <= 65535 && ld >= H * kHD && ld_out >= H * kHD && ld_d >= H * kHD) {
         if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv) return fail(VAH_E_NULL, "%s: null pointer", fn);
         if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dout) % 16 || (ld % 8) || (ld_out % 8) ||
             ((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 8 || (ld_d % 4))
             return fail(VAH_E_ALIGN, "%s: q/k/v/out/dout need 16-byte aligned rows, dq/dk/dv 8-byte", fn);
         // one kernel does the work of the prologue, dq and dkdv kernels: bytes = q, k, v, out, dout in, dq, dk, dv out;
         // flops (algorithmic) = S, dP, dQ, dK, dV = 10 N^2 64 per (window, head); the kernel forms S and dP twice
-        LaunchScope scope("attn_win_bwd_bf16", 8 * Z * H * N * attn::kHD * 2 + Z * H * N * 4, (hipStream_t)stream, 0,
-                          10 * Z * H * N * N * attn::kHD);
-        return attn::attn_win_bwd_resident(q, k, v, ld, out, dout, ld_out, rm, lse, Z, H, N, scale, dq, dk, dv, ld_d,
-                                           (hipStream_t)stream);
+        LaunchScope scope(tname<T>("attn_win_bwd_bf16", "attn_win_bwd_f16"), 8 * Z * H * N * kHD * 2 + Z * H * N * 4,
+                          (hipStream_t)stream, 0, 10 * Z * H * N * N * kHD);
+        return attn_win_bwd_resident<T>(q, k, v, ld, out, dout, ld_out, rm, lse, Z, H, N, scale, dq, dk, dv, ld_d, (hipStream_t)stream);
     }
-    return attn_bwd_impl(fn, q, k, v, ld, rm, out, dout, ld_out, lse, Z, H, N, scale, ws, dq, dk, dv, ld_d, stream);
+    return attn_bwd_impl<T>(fn, q, k, v, ld, rm, out, dout, ld_out, lse, Z, H, N, scale, ws, dq, dk, dv, ld_d, stream);
+}
+
+}  // namespace
+}  // namespace attn
+}  // namespace vah
+
+// The bf16 entry points and their fp16 twins: identical arguments, checks and error codes.
+extern "C" {
+
+int vah_attn_bwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
+                      const void *out, const void *dout, int64_t ld_out, const float *lse, int64_t B,
+                      int64_t H, int64_t N, float scale, void *ws, void *dq, void *dk, void *dv,
+                      int64_t ld_d, int64_t batch_stride_d, void *stream) {
+    return vah::attn::attn_bwd_entry<__bf16>("vah_attn_bwd_bf16", q, k, v, ld, batch_stride, out, dout, ld_out, lse, B, H, N, scale,
+                                             ws, dq, dk, dv, ld_d, batch_stride_d, stream);
+}
+
+int vah_attn_bwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
+                     const void *out, const void *dout, int64_t ld_out, const float *lse, int64_t B,
+                     int64_t H, int64_t N, float scale, void *ws, void *dq, void *dk, void *dv,
+                     int64_t ld_d, int64_t batch_stride_d, void *stream) {
+    return vah::attn::attn_bwd_entry<_Float16>("vah_attn_bwd_f16", q, k, v, ld, batch_stride, out, dout, ld_out, lse, B, H, N, scale,
+                                               ws, dq, dk, dv, ld_d, batch_stride_d, stream);
+}
+
+int vah_attn_bias_bwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, const void *out,
+                           const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t H, int64_t N, float scale,
+                           const void *bias, const void *bias_t, int64_t ldb, void *ds_out, float *delta_ws, void *dq, void *dk,
+                           void *dv, int64_t ld_d, int64_t batch_stride_d, void *stream) {
+    return vah::attn::attn_bias_bwd_entry<__bf16>("vah_attn_bias_bwd_bf16", q, k, v, ld, batch_stride, out, dout, ld_out, lse, B, H,
+                                                  N, scale, bias, bias_t, ldb, ds_out, delta_ws, dq, dk, dv, ld_d, batch_stride_d,
+                                                  stream);
+}
+
+int vah_attn_bias_bwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, const void *out,
+                          const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t H, int64_t N, float scale,
+                          const void *bias, const void *bias_t, int64_t ldb, void *ds_out, float *delta_ws, void *dq, void *dk,
+                          void *dv, int64_t ld_d, int64_t batch_stride_d, void *stream) {
+    return vah::attn::attn_bias_bwd_entry<_Float16>("vah_attn_bias_bwd_f16", q, k, v, ld, batch_stride, out, dout, ld_out, lse, B, H,
+                                                    N, scale, bias, bias_t, ldb, ds_out, delta_ws, dq, dk, dv, ld_d, batch_stride_d,
+                                                    stream);
+}
+
+int vah_attn_win_bwd_bf16(const void *q, const void *k, const void *v, int64_t ld, const void *out,
+                          const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t grid_h,
+                          int64_t grid_w, int64_t win, int64_t H, float scale, void *ws, void *dq,
+                          void *dk, void *dv, int64_t ld_d, void *stream) {
+    return vah::attn::attn_win_bwd_entry<__bf16>("vah_attn_win_bwd_bf16", q, k, v, ld, out, dout, ld_out, lse, B, grid_h, grid_w,
+                                                 win, H, scale, ws, dq, dk, dv, ld_d, stream);
+}
+
+int vah_attn_win_bwd_f16(const void *q, const void *k, const void *v, int64_t ld, const void *out,
+                         const void *dout, int64_t ld_out, const float *lse, int64_t B, int64_t grid_h,
+                         int64_t grid_w, int64_t win, int64_t H, float scale, void *ws, void *dq,
+                         void *dk, void *dv, int64_t ld_d, void *stream) {
+    return vah::attn::attn_win_bwd_entry<_Float16>("vah_attn_win_bwd_f16", q, k, v, ld, out, dout, ld_out, lse, B, grid_h, grid_w,
+                                                   win, H, scale, ws, dq, dk, dv, ld_d, stream);
 }
 
 }  // extern "C"

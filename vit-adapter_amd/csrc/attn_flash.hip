@@ -1,4 +1,5 @@
-// Global (whole-sequence) attention forward and backward for head_dim 64, bf16 in / fp32 accumulate.
+// Global (whole-sequence) attention forward and backward for head_dim 64, bf16 or fp16 in (T, attn_common.h) / fp32
+// accumulate.
 //
 // Arithmetic of the reference's Attention (/root/reference/detection/mmdet_custom/models/backbones/base/vit.py:
 // 83-88): softmax(q k^T * scale) v.  At head_dim 64 this operator is bound by the VALU, not the matrix pipe: a 32 x 32
@@ -20,16 +21,18 @@ namespace {
 typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8;
 
-__device__ __forceinline__ const __bf16 *tile_lane_base(const __bf16 *tile, int lane) {
+template <typename T>
+__device__ __forceinline__ const T *tile_lane_base(const T *tile, int lane) {
     const int grp = lane >> 4, i16 = lane & 15;
     return tile + (4 * (grp >> 1) + (i16 >> 2)) * kPadRow + 16 * (grp & 1) + 4 * (i16 & 3);
 }
 // A operand T^T[m = d][k = token] of a row-major LDS tile T[token][d] in the k order of pack_half (attn_win.hip)
-__device__ __forceinline__ bf16x8 load_tr(const __bf16 *base, int tok0, int db) {
-    const __bf16 *p0 = base + tok0 * kPadRow + 32 * db;
+template <typename T>
+__device__ __forceinline__ vec8<T> load_tr(const T *base, int tok0, int db) {
+    const T *p0 = base + tok0 * kPadRow + 32 * db;
     const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p0);
     const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(p0 + 8 * kPadRow));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
+    return __builtin_bit_cast(vec8<T>, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 // Exchange across the two 32-lane halves on the VALU: after v_permlane32_swap a = [x.lo, x.lo], b = [x.hi, x.hi].
 // Inline asm: with the builtin and one value for both operands the compiler folds max(a, b) to a.  The s_nop covers
@@ -55,14 +58,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kQB = 128, kKT = 64;
 
 // BIAS: an additive term per (head, query, key) - BEiT's relative position bias (base/beit.py:120-144): `bias` holds
-// bias * log2(e) as bf16, (H, N, ldb) with ldb a multiple of 64 >= N (columns beyond N unused)
-template <bool BIAS>
+// bias * log2(e) as T, (H, N, ldb) with ldb a multiple of 64 >= N (columns beyond N unused)
+template <typename T, bool BIAS>
 __global__ __launch_bounds__(256) void attn_fwd_seq_kernel(
-    const __bf16 *__restrict__ q, const __bf16 *__restrict__ k, const __bf16 *__restrict__ v, int64_t ld, int N, int H,
-    float scale_log2, const __bf16 *__restrict__ bias, int64_t ldb, __bf16 *__restrict__ out, int64_t ld_out,
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, int64_t ld, int N, int H,
+    float scale_log2, const T *__restrict__ bias, int64_t ldb, T *__restrict__ out, int64_t ld_out,
     float *__restrict__ lse) {
-    __shared__ __attribute__((aligned(16))) __bf16 s_k2[2][kKT * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_v2[2][kKT * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_k2[2][kKT * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_v2[2][kKT * kPadRow];
     const int h = blockIdx.y, b = blockIdx.z;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = lane & 31, hf = lane >> 5;
@@ -70,33 +73,33 @@ __global__ __launch_bounds__(256) void attn_fwd_seq_kernel(
     const int64_t seq0 = (int64_t)b * N;
     const int64_t gq = seq0 + min(qrow, N - 1);
 
-    bf16x8 qf[4];
+    vec8<T> qf[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) qf[kk] = *reinterpret_cast<const bf16x8 *>(q + gq * ld + h * kHD + 16 * kk + 8 * hf);
+    for (int kk = 0; kk < 4; ++kk) qf[kk] = *reinterpret_cast<const vec8<T> *>(q + gq * ld + h * kHD + 16 * kk + 8 * hf);
 
     // staging: 512 pieces of 16 bytes per tile and matrix, two per thread (rows sr and sr + 32)
     const int sr = threadIdx.x >> 3, sc = (threadIdx.x & 7) * 8;
-    const __bf16 *kp = k + h * kHD + sc, *vp = v + h * kHD + sc;
-    bf16x8 pk0, pk1, pv0, pv1;
+    const T *kp = k + h * kHD + sc, *vp = v + h * kHD + sc;
+    vec8<T> pk0, pk1, pv0, pv1;
     auto fetch = [&](int key0) {
         const int64_t g0 = (seq0 + min(key0 + sr, N - 1)) * ld, g1 = (seq0 + min(key0 + sr + 32, N - 1)) * ld;
-        pk0 = *reinterpret_cast<const bf16x8 *>(kp + g0);
-        pk1 = *reinterpret_cast<const bf16x8 *>(kp + g1);
-        pv0 = *reinterpret_cast<const bf16x8 *>(vp + g0);
-        pv1 = *reinterpret_cast<const bf16x8 *>(vp + g1);
+        pk0 = *reinterpret_cast<const vec8<T> *>(kp + g0);
+        pk1 = *reinterpret_cast<const vec8<T> *>(kp + g1);
+        pv0 = *reinterpret_cast<const vec8<T> *>(vp + g0);
+        pv1 = *reinterpret_cast<const vec8<T> *>(vp + g1);
     };
     auto commit = [&](int buf) {
-        *reinterpret_cast<bf16x8 *>(s_k2[buf] + sr * kPadRow + sc) = pk0;
-        *reinterpret_cast<bf16x8 *>(s_k2[buf] + (sr + 32) * kPadRow + sc) = pk1;
-        *reinterpret_cast<bf16x8 *>(s_v2[buf] + sr * kPadRow + sc) = pv0;
-        *reinterpret_cast<bf16x8 *>(s_v2[buf] + (sr + 32) * kPadRow + sc) = pv1;
+        *reinterpret_cast<vec8<T> *>(s_k2[buf] + sr * kPadRow + sc) = pk0;
+        *reinterpret_cast<vec8<T> *>(s_k2[buf] + (sr + 32) * kPadRow + sc) = pk1;
+        *reinterpret_cast<vec8<T> *>(s_v2[buf] + sr * kPadRow + sc) = pv0;
+        *reinterpret_cast<vec8<T> *>(s_v2[buf] + (sr + 32) * kPadRow + sc) = pv1;
     };
 
     f32x16 o[2] = {zero16(), zero16()};
     f32x16 lsum = zero16();
-    bf16x8 ones;
+    vec8<T> ones;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.f;
+    for (int j = 0; j < 8; ++j) ones[j] = (T)1.f;
     const f32x2 sc2 = {scale_log2, scale_log2};
     float m_run = -INFINITY;
     const int ntiles = (N + kKT - 1) / kKT;
@@ -109,15 +112,15 @@ __global__ __launch_bounds__(256) void attn_fwd_seq_kernel(
             commit((t + 1) & 1);
             if (t + 2 < ntiles) fetch((t + 2) * kKT);
         }
-        const __bf16 *s_k = s_k2[t & 1];
-        const __bf16 *vbase = tile_lane_base(s_v2[t & 1], lane);
-        bf16x4 bv[2][4];
+        const T *s_k = s_k2[t & 1];
+        const T *vbase = tile_lane_base(s_v2[t & 1], lane);
+        vec4<T> bv[2][4];
         if constexpr (BIAS) {           // this lane's query row, 4 consecutive keys per register group
-            const __bf16 *bp = bias + ((int64_t)h * N + min(qrow, N - 1)) * ldb + t * kKT + 4 * hf;
+            const T *bp = bias + ((int64_t)h * N + min(qrow, N - 1)) * ldb + t * kKT + 4 * hf;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) bv[kb][g] = *reinterpret_cast<const bf16x4 *>(bp + 32 * kb + 8 * g);
+                for (int g = 0; g < 4; ++g) bv[kb][g] = *reinterpret_cast<const vec4<T> *>(bp + 32 * kb + 8 * g);
         }
 
         f32x16 s[2];
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256) void attn_fwd_seq_kernel(
             s[kb] = zero16();
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
-                s[kb] = mfma(*reinterpret_cast<const bf16x8 *>(s_k + (kb * 32 + r) * kPadRow + 16 * kk + 8 * hf), qf[kk], s[kb]);
+                s[kb] = mfma(*reinterpret_cast<const vec8<T> *>(s_k + (kb * 32 + r) * kPadRow + 16 * kk + 8 * hf), qf[kk], s[kb]);
         }
         if constexpr (BIAS) {           // scores in the log2 domain from here on
 #pragma unroll
@@ -176,12 +179,12 @@ __global__ __launch_bounds__(256) void attn_fwd_seq_kernel(
                 s[kb][i + 1] = __builtin_amdgcn_exp2f(x[1]);
             }
         // O^T += V^T P^T; the row sums of P ride along as a third block whose A operand is all ones (4 MFMAs on a pipe
-        // with slack instead of 32 VALU adds on the pipe that bounds the loop), from the same bf16 P the product uses
+        // with slack instead of 32 VALU adds on the pipe that bounds the loop), from the same T-rounded P the product uses
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) {
-                const bf16x8 pf = pack_half(s[kb], sp);
+                const vec8<T> pf = pack_half<T>(s[kb], sp);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) o[db] = mfma(load_tr(vbase, kb * 32 + 16 * sp, db), pf, o[db]);
                 lsum = mfma(ones, pf, lsum);
@@ -191,15 +194,15 @@ __global__ __launch_bounds__(256) void attn_fwd_seq_kernel(
     const float l_tot = lsum[0];      // the MFMA has summed over all keys: every row of column r is query r's sum
     const float inv = 1.f / l_tot;
     if (qrow < N) {
-        __bf16 *op = out + gq * ld_out + (int64_t)h * kHD;
+        T *op = out + gq * ld_out + (int64_t)h * kHD;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 w;
+                vec4<T> w;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w[j] = (__bf16)(o[db][4 * g + j] * inv);
-                *reinterpret_cast<bf16x4 *>(op + db * 32 + 8 * g + 4 * hf) = w;
+                for (int j = 0; j < 4; ++j) w[j] = (T)(o[db][4 * g + j] * inv);
+                *reinterpret_cast<vec4<T> *>(op + db * 32 + 8 * g + 4 * hf) = w;
             }
         if (hf == 0) lse[((int64_t)b * H + h) * N + qrow] = m_run + log2f(l_tot);
     }
@@ -215,15 +218,15 @@ __global__ __launch_bounds__(256) void attn_fwd_seq_kernel(
 // are clamped, not zero-filled.
 // ---------------------------------------------------------------------------------------
 // BIAS: scores carry `bias` as in the forward; dS (= d loss / d bias of this image) is written to ds_out
-// (B, H, N, ldb) bf16, the caller sums it over the batch
-template <bool BIAS>
+// (B, H, N, ldb) as T, the caller sums it over the batch
+template <typename T, bool BIAS>
 __global__ __launch_bounds__(256) void attn_bwd_dq_seq_kernel(
-    const __bf16 *__restrict__ q, const __bf16 *__restrict__ k, const __bf16 *__restrict__ v, int64_t ld,
-    const __bf16 *__restrict__ o, const __bf16 *__restrict__ d_o, int64_t ld_out, const float *__restrict__ lse, int N, int H,
-    float scale, float scale_log2, const __bf16 *__restrict__ bias, int64_t ldb, __bf16 *__restrict__ ds_out,
-    float *__restrict__ delta, __bf16 *__restrict__ dq, int64_t ld_d) {
-    __shared__ __attribute__((aligned(16))) __bf16 s_k2[2][kKT * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_v2[2][kKT * kPadRow];
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, int64_t ld,
+    const T *__restrict__ o, const T *__restrict__ d_o, int64_t ld_out, const float *__restrict__ lse, int N, int H,
+    float scale, float scale_log2, const T *__restrict__ bias, int64_t ldb, T *__restrict__ ds_out,
+    float *__restrict__ delta, T *__restrict__ dq, int64_t ld_d) {
+    __shared__ __attribute__((aligned(16))) T s_k2[2][kKT * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_v2[2][kKT * kPadRow];
     const int h = blockIdx.y, b = blockIdx.z;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = lane & 31, hf = lane >> 5;
@@ -231,13 +234,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_seq_kernel(
     const int64_t seq0 = (int64_t)b * N;
     const int64_t gq = seq0 + min(qrow, N - 1);
 
-    bf16x8 qf[4], dof[4];
+    vec8<T> qf[4], dof[4];
     float part = 0.f;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        qf[kk] = *reinterpret_cast<const bf16x8 *>(q + gq * ld + h * kHD + 16 * kk + 8 * hf);
-        dof[kk] = *reinterpret_cast<const bf16x8 *>(d_o + gq * ld_out + h * kHD + 16 * kk + 8 * hf);
-        const bf16x8 of = *reinterpret_cast<const bf16x8 *>(o + gq * ld_out + h * kHD + 16 * kk + 8 * hf);
+        qf[kk] = *reinterpret_cast<const vec8<T> *>(q + gq * ld + h * kHD + 16 * kk + 8 * hf);
+        dof[kk] = *reinterpret_cast<const vec8<T> *>(d_o + gq * ld_out + h * kHD + 16 * kk + 8 * hf);
+        const vec8<T> of = *reinterpret_cast<const vec8<T> *>(o + gq * ld_out + h * kHD + 16 * kk + 8 * hf);
 #pragma unroll
         for (int j = 0; j < 8; ++j) part += (float)of[j] * (float)dof[kk][j];
     }
@@ -246,20 +249,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_seq_kernel(
     if (hf == 0 && qrow < N) delta[((int64_t)b * H + h) * N + qrow] = delta_q;
 
     const int sr = threadIdx.x >> 3, sc = (threadIdx.x & 7) * 8;
-    const __bf16 *kp = k + h * kHD + sc, *vp = v + h * kHD + sc;
-    bf16x8 pk0, pk1, pv0, pv1;
+    const T *kp = k + h * kHD + sc, *vp = v + h * kHD + sc;
+    vec8<T> pk0, pk1, pv0, pv1;
     auto fetch = [&](int key0) {
         const int64_t g0 = (seq0 + min(key0 + sr, N - 1)) * ld, g1 = (seq0 + min(key0 + sr + 32, N - 1)) * ld;
-        pk0 = *reinterpret_cast<const bf16x8 *>(kp + g0);
-        pk1 = *reinterpret_cast<const bf16x8 *>(kp + g1);
-        pv0 = *reinterpret_cast<const bf16x8 *>(vp + g0);
-        pv1 = *reinterpret_cast<const bf16x8 *>(vp + g1);
+        pk0 = *reinterpret_cast<const vec8<T> *>(kp + g0);
+        pk1 = *reinterpret_cast<const vec8<T> *>(kp + g1);
+        pv0 = *reinterpret_cast<const vec8<T> *>(vp + g0);
+        pv1 = *reinterpret_cast<const vec8<T> *>(vp + g1);
     };
     auto commit = [&](int buf) {
-        *reinterpret_cast<bf16x8 *>(s_k2[buf] + sr * kPadRow + sc) = pk0;
-        *reinterpret_cast<bf16x8 *>(s_k2[buf] + (sr + 32) * kPadRow + sc) = pk1;
-        *reinterpret_cast<bf16x8 *>(s_v2[buf] + sr * kPadRow + sc) = pv0;
-        *reinterpret_cast<bf16x8 *>(s_v2[buf] + (sr + 32) * kPadRow + sc) = pv1;
+        *reinterpret_cast<vec8<T> *>(s_k2[buf] + sr * kPadRow + sc) = pk0;
+        *reinterpret_cast<vec8<T> *>(s_k2[buf] + (sr + 32) * kPadRow + sc) = pk1;
+        *reinterpret_cast<vec8<T> *>(s_v2[buf] + sr * kPadRow + sc) = pv0;
+        *reinterpret_cast<vec8<T> *>(s_v2[buf] + (sr + 32) * kPadRow + sc) = pv1;
     };
 
     f32x16 acc[2] = {zero16(), zero16()};
@@ -274,23 +277,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_seq_kernel(
             commit((t + 1) & 1);
             if (t + 2 < ntiles) fetch((t + 2) * kKT);
         }
-        const __bf16 *s_k = s_k2[t & 1], *s_v = s_v2[t & 1];
-        const __bf16 *kbase = tile_lane_base(s_k, lane);
-        bf16x4 bv[2][4];
+        const T *s_k = s_k2[t & 1], *s_v = s_v2[t & 1];
+        const T *kbase = tile_lane_base(s_k, lane);
+        vec4<T> bv[2][4];
         const int64_t brow = ((int64_t)h * N + min(qrow, N - 1)) * ldb + t * kKT + 4 * hf;
         if constexpr (BIAS) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) bv[kb][g] = *reinterpret_cast<const bf16x4 *>(bias + brow + 32 * kb + 8 * g);
+                for (int g = 0; g < 4; ++g) bv[kb][g] = *reinterpret_cast<const vec4<T> *>(bias + brow + 32 * kb + 8 * g);
         }
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             f32x16 s = zero16(), dp = zero16();
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                s = mfma(*reinterpret_cast<const bf16x8 *>(s_k + (kb * 32 + r) * kPadRow + 16 * kk + 8 * hf), qf[kk], s);
-                dp = mfma(*reinterpret_cast<const bf16x8 *>(s_v + (kb * 32 + r) * kPadRow + 16 * kk + 8 * hf), dof[kk], dp);
+                s = mfma(*reinterpret_cast<const vec8<T> *>(s_k + (kb * 32 + r) * kPadRow + 16 * kk + 8 * hf), qf[kk], s);
+                dp = mfma(*reinterpret_cast<const vec8<T> *>(s_v + (kb * 32 + r) * kPadRow + 16 * kk + 8 * hf), dof[kk], dp);
             }
 #pragma unroll
             for (int i = 0; i < 16; i += 2) {                           // dS^T = P^T o (dP^T - delta)
@@ -308,48 +311,48 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_seq_kernel(
             }
             if constexpr (BIAS) {
                 if (qrow < N) {
-                    __bf16 *dp_ = ds_out + (int64_t)b * H * N * ldb + brow + 32 * kb;
+                    T *dp_ = ds_out + (int64_t)b * H * N * ldb + brow + 32 * kb;
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        bf16x4 w;
+                        vec4<T> w;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) w[j] = (__bf16)s[4 * g + j];
-                        *reinterpret_cast<bf16x4 *>(dp_ + 8 * g) = w;
+                        for (int j = 0; j < 4; ++j) w[j] = (T)s[4 * g + j];
+                        *reinterpret_cast<vec4<T> *>(dp_ + 8 * g) = w;
                     }
                 }
             }
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) {
-                const bf16x8 pf = pack_half(s, sp);
+                const vec8<T> pf = pack_half<T>(s, sp);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) acc[db] = mfma(load_tr(kbase, kb * 32 + 16 * sp, db), pf, acc[db]);
             }
         }
     }
     if (qrow < N) {
-        __bf16 *op = dq + gq * ld_d + (int64_t)h * kHD;
+        T *op = dq + gq * ld_d + (int64_t)h * kHD;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 w;
+                vec4<T> w;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w[j] = (__bf16)(acc[db][4 * g + j] * scale);
-                *reinterpret_cast<bf16x4 *>(op + db * 32 + 8 * g + 4 * hf) = w;
+                for (int j = 0; j < 4; ++j) w[j] = (T)(acc[db][4 * g + j] * scale);
+                *reinterpret_cast<vec4<T> *>(op + db * 32 + 8 * g + 4 * hf) = w;
             }
     }
 }
 
 // dK, dV: workgroup = 128 keys (32 per wave), loop over query tiles of 64
 // BIAS: bias_t = the forward's bias TRANSPOSED, (H, N keys, ldb queries): this lane's key row, 4 consecutive queries
-template <bool BIAS>
+template <typename T, bool BIAS>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_seq_kernel(
-    const __bf16 *__restrict__ q, const __bf16 *__restrict__ k, const __bf16 *__restrict__ v, int64_t ld,
-    const __bf16 *__restrict__ d_o, int64_t ld_out, const float *__restrict__ lse, const float *__restrict__ delta, int N, int H,
-    float scale, float scale_log2, const __bf16 *__restrict__ bias_t, int64_t ldb, __bf16 *__restrict__ dk,
-    __bf16 *__restrict__ dv, int64_t ld_d) {
-    __shared__ __attribute__((aligned(16))) __bf16 s_q2[2][kKT * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_do2[2][kKT * kPadRow];
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, int64_t ld,
+    const T *__restrict__ d_o, int64_t ld_out, const float *__restrict__ lse, const float *__restrict__ delta, int N, int H,
+    float scale, float scale_log2, const T *__restrict__ bias_t, int64_t ldb, T *__restrict__ dk,
+    T *__restrict__ dv, int64_t ld_d) {
+    __shared__ __attribute__((aligned(16))) T s_q2[2][kKT * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_do2[2][kKT * kPadRow];
     __shared__ __attribute__((aligned(16))) float s_lse2[2][kKT];
     __shared__ __attribute__((aligned(16))) float s_delta2[2][kKT];
     const int h = blockIdx.y, b = blockIdx.z;
@@ -359,23 +362,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_seq_kernel(
     const int64_t seq0 = (int64_t)b * N;
     const int64_t gk = seq0 + min(krow, N - 1);
 
-    bf16x8 kf[4], vf[4];
+    vec8<T> kf[4], vf[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        kf[kk] = *reinterpret_cast<const bf16x8 *>(k + gk * ld + h * kHD + 16 * kk + 8 * hf);
-        vf[kk] = *reinterpret_cast<const bf16x8 *>(v + gk * ld + h * kHD + 16 * kk + 8 * hf);
+        kf[kk] = *reinterpret_cast<const vec8<T> *>(k + gk * ld + h * kHD + 16 * kk + 8 * hf);
+        vf[kk] = *reinterpret_cast<const vec8<T> *>(v + gk * ld + h * kHD + 16 * kk + 8 * hf);
     }
     const int sr = threadIdx.x >> 3, sc = (threadIdx.x & 7) * 8;
-    const __bf16 *qp = q + h * kHD + sc, *dop = d_o + h * kHD + sc;
+    const T *qp = q + h * kHD + sc, *dop = d_o + h * kHD + sc;
     const float *lseb = lse + ((int64_t)b * H + h) * N, *delb = delta + ((int64_t)b * H + h) * N;
-    bf16x8 pq0, pq1, pd0, pd1;
+    vec8<T> pq0, pq1, pd0, pd1;
     float plse = 0.f, pdel = 0.f;
     auto fetch = [&](int q0) {
         const int64_t r0 = seq0 + min(q0 + sr, N - 1), r1 = seq0 + min(q0 + sr + 32, N - 1);
-        pq0 = *reinterpret_cast<const bf16x8 *>(qp + r0 * ld);
-        pq1 = *reinterpret_cast<const bf16x8 *>(qp + r1 * ld);
-        pd0 = *reinterpret_cast<const bf16x8 *>(dop + r0 * ld_out);
-        pd1 = *reinterpret_cast<const bf16x8 *>(dop + r1 * ld_out);
+        pq0 = *reinterpret_cast<const vec8<T> *>(qp + r0 * ld);
+        pq1 = *reinterpret_cast<const vec8<T> *>(qp + r1 * ld);
+        pd0 = *reinterpret_cast<const vec8<T> *>(dop + r0 * ld_out);
+        pd1 = *reinterpret_cast<const vec8<T> *>(dop + r1 * ld_out);
         if (threadIdx.x < kKT) {
             const int n = q0 + threadIdx.x;
             plse = n < N ? lseb[n] : INFINITY;                  // +inf: p = 0 for queries that do not exist
@@ -383,10 +386,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_seq_kernel(
         }
     };
     auto commit = [&](int buf) {
-        *reinterpret_cast<bf16x8 *>(s_q2[buf] + sr * kPadRow + sc) = pq0;
-        *reinterpret_cast<bf16x8 *>(s_q2[buf] + (sr + 32) * kPadRow + sc) = pq1;
-        *reinterpret_cast<bf16x8 *>(s_do2[buf] + sr * kPadRow + sc) = pd0;
-        *reinterpret_cast<bf16x8 *>(s_do2[buf] + (sr + 32) * kPadRow + sc) = pd1;
+        *reinterpret_cast<vec8<T> *>(s_q2[buf] + sr * kPadRow + sc) = pq0;
+        *reinterpret_cast<vec8<T> *>(s_q2[buf] + (sr + 32) * kPadRow + sc) = pq1;
+        *reinterpret_cast<vec8<T> *>(s_do2[buf] + sr * kPadRow + sc) = pd0;
+        *reinterpret_cast<vec8<T> *>(s_do2[buf] + (sr + 32) * kPadRow + sc) = pd1;
         if (threadIdx.x < kKT) {
             s_lse2[buf][threadIdx.x] = plse;
             s_delta2[buf][threadIdx.x] = pdel;
@@ -405,24 +408,24 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_seq_kernel(
             commit((t + 1) & 1);
             if (t + 2 < ntiles) fetch((t + 2) * kKT);
         }
-        const __bf16 *s_q = s_q2[t & 1], *s_do = s_do2[t & 1];
+        const T *s_q = s_q2[t & 1], *s_do = s_do2[t & 1];
         const float *s_lse = s_lse2[t & 1], *s_delta = s_delta2[t & 1];
-        const __bf16 *qbase = tile_lane_base(s_q, lane), *dobase = tile_lane_base(s_do, lane);
-        bf16x4 bv[2][4];
+        const T *qbase = tile_lane_base(s_q, lane), *dobase = tile_lane_base(s_do, lane);
+        vec4<T> bv[2][4];
         if constexpr (BIAS) {
-            const __bf16 *bp = bias_t + ((int64_t)h * N + min(krow, N - 1)) * ldb + t * kKT + 4 * hf;
+            const T *bp = bias_t + ((int64_t)h * N + min(krow, N - 1)) * ldb + t * kKT + 4 * hf;
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) bv[qb][g] = *reinterpret_cast<const bf16x4 *>(bp + 32 * qb + 8 * g);
+                for (int g = 0; g < 4; ++g) bv[qb][g] = *reinterpret_cast<const vec4<T> *>(bp + 32 * qb + 8 * g);
         }
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             f32x16 s = zero16(), dp = zero16();
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                s = mfma(*reinterpret_cast<const bf16x8 *>(s_q + (qb * 32 + r) * kPadRow + 16 * kk + 8 * hf), kf[kk], s);      // S[q][key]
-                dp = mfma(*reinterpret_cast<const bf16x8 *>(s_do + (qb * 32 + r) * kPadRow + 16 * kk + 8 * hf), vf[kk], dp);   // dP[q][key]
+                s = mfma(*reinterpret_cast<const vec8<T> *>(s_q + (qb * 32 + r) * kPadRow + 16 * kk + 8 * hf), kf[kk], s);      // S[q][key]
+                dp = mfma(*reinterpret_cast<const vec8<T> *>(s_do + (qb * 32 + r) * kPadRow + 16 * kk + 8 * hf), vf[kk], dp);   // dP[q][key]
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -442,7 +445,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_seq_kernel(
             }
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) {
-                const bf16x8 pf = pack_half(s, sp), dsf = pack_half(dp, sp);
+                const vec8<T> pf = pack_half<T>(s, sp), dsf = pack_half<T>(dp, sp);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
                     dvt[db] = mfma(load_tr(dobase, qb * 32 + 16 * sp, db), pf, dvt[db]);      // dV^T[d][key] += dO^T P
@@ -452,39 +455,41 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_seq_kernel(
         }
     }
     if (krow < N) {
-        __bf16 *pk = dk + gk * ld_d + (int64_t)h * kHD, *pv = dv + gk * ld_d + (int64_t)h * kHD;
+        T *pk = dk + gk * ld_d + (int64_t)h * kHD, *pv = dv + gk * ld_d + (int64_t)h * kHD;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 wk, wv;
+                vec4<T> wk, wv;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    wk[j] = (__bf16)(dkt[db][4 * g + j] * scale);
-                    wv[j] = (__bf16)dvt[db][4 * g + j];
+                    wk[j] = (T)(dkt[db][4 * g + j] * scale);
+                    wv[j] = (T)dvt[db][4 * g + j];
                 }
-                *reinterpret_cast<bf16x4 *>(pk + db * 32 + 8 * g + 4 * hf) = wk;
-                *reinterpret_cast<bf16x4 *>(pv + db * 32 + 8 * g + 4 * hf) = wv;
+                *reinterpret_cast<vec4<T> *>(pk + db * 32 + 8 * g + 4 * hf) = wk;
+                *reinterpret_cast<vec4<T> *>(pv + db * 32 + 8 * g + 4 * hf) = wv;
             }
     }
 }
 
 }  // namespace
 
+template <typename T>
 int attn_fwd_seq(const void *q, const void *k, const void *v, int64_t ld, int64_t B, int64_t H, int64_t N, float scale,
                  const void *bias, int64_t ldb, void *out, int64_t ld_out, float *lse, hipStream_t st) {
     const dim3 grid((unsigned)((N + kQB - 1) / kQB), (unsigned)H, (unsigned)B);
     if (bias)
-        hipLaunchKernelGGL(attn_fwd_seq_kernel<true>, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                           (const __bf16 *)v, ld, (int)N, (int)H, scale * 1.4426950408889634f, (const __bf16 *)bias, ldb,
-                           (__bf16 *)out, ld_out, lse);
+        hipLaunchKernelGGL((attn_fwd_seq_kernel<T, true>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                           (const T *)v, ld, (int)N, (int)H, scale * 1.4426950408889634f, (const T *)bias, ldb,
+                           (T *)out, ld_out, lse);
     else
-        hipLaunchKernelGGL(attn_fwd_seq_kernel<false>, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                           (const __bf16 *)v, ld, (int)N, (int)H, scale * 1.4426950408889634f, (const __bf16 *)nullptr,
-                           (int64_t)0, (__bf16 *)out, ld_out, lse);
+        hipLaunchKernelGGL((attn_fwd_seq_kernel<T, false>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                           (const T *)v, ld, (int)N, (int)H, scale * 1.4426950408889634f, (const T *)nullptr,
+                           (int64_t)0, (T *)out, ld_out, lse);
     return check_launch("attn_fwd_seq");
 }
 
+template <typename T>
 int attn_bwd_seq(const void *q, const void *k, const void *v, int64_t ld, const void *o, const void *d_o, int64_t ld_out,
                  const float *lse, int64_t B, int64_t H, int64_t N, float scale, const void *bias, const void *bias_t,
                  int64_t ldb, void *ds_out, float *delta, void *dq, void *dk, void *dv, int64_t ld_d, hipStream_t st) {
@@ -493,28 +498,39 @@ int attn_bwd_seq(const void *q, const void *k, const void *v, int64_t ld, const 
     {
         // useful flops of the whole backward = 2.5x the forward (S, dP, dV, dK, dQ products); both kernels form S and
         // dP: dq runs 3 products (6 B H N^2 64), dkdv 4 (8 B H N^2 64)
-        LaunchScope scope("attn_bwd_dq_bf16", 6 * B * H * N * kHD * 2, st, 0, 6 * B * H * N * N * kHD);
+        LaunchScope scope(tname<T>("attn_bwd_dq_bf16", "attn_bwd_dq_f16"), 6 * B * H * N * kHD * 2, st, 0, 6 * B * H * N * N * kHD);
         if (bias)
-            hipLaunchKernelGGL(attn_bwd_dq_seq_kernel<true>, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                               (const __bf16 *)v, ld, (const __bf16 *)o, (const __bf16 *)d_o, ld_out, lse, (int)N, (int)H, scale,
-                               scale_log2, (const __bf16 *)bias, ldb, (__bf16 *)ds_out, delta, (__bf16 *)dq, ld_d);
+            hipLaunchKernelGGL((attn_bwd_dq_seq_kernel<T, true>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                               (const T *)v, ld, (const T *)o, (const T *)d_o, ld_out, lse, (int)N, (int)H, scale,
+                               scale_log2, (const T *)bias, ldb, (T *)ds_out, delta, (T *)dq, ld_d);
         else
-            hipLaunchKernelGGL(attn_bwd_dq_seq_kernel<false>, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                               (const __bf16 *)v, ld, (const __bf16 *)o, (const __bf16 *)d_o, ld_out, lse, (int)N, (int)H, scale,
-                               scale_log2, (const __bf16 *)nullptr, (int64_t)0, (__bf16 *)nullptr, delta, (__bf16 *)dq, ld_d);
+            hipLaunchKernelGGL((attn_bwd_dq_seq_kernel<T, false>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                               (const T *)v, ld, (const T *)o, (const T *)d_o, ld_out, lse, (int)N, (int)H, scale,
+                               scale_log2, (const T *)nullptr, (int64_t)0, (T *)nullptr, delta, (T *)dq, ld_d);
         if (int rc = check_launch("attn_bwd_dq_seq")) return rc;
     }
-    LaunchScope scope("attn_bwd_dkdv_bf16", 8 * B * H * N * kHD * 2, st, 0, 8 * B * H * N * N * kHD);
+    LaunchScope scope(tname<T>("attn_bwd_dkdv_bf16", "attn_bwd_dkdv_f16"), 8 * B * H * N * kHD * 2, st, 0, 8 * B * H * N * N * kHD);
     if (bias)
-        hipLaunchKernelGGL(attn_bwd_dkdv_seq_kernel<true>, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                           (const __bf16 *)v, ld, (const __bf16 *)d_o, ld_out, lse, delta, (int)N, (int)H, scale, scale_log2,
-                           (const __bf16 *)bias_t, ldb, (__bf16 *)dk, (__bf16 *)dv, ld_d);
+        hipLaunchKernelGGL((attn_bwd_dkdv_seq_kernel<T, true>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                           (const T *)v, ld, (const T *)d_o, ld_out, lse, delta, (int)N, (int)H, scale, scale_log2,
+                           (const T *)bias_t, ldb, (T *)dk, (T *)dv, ld_d);
     else
-        hipLaunchKernelGGL(attn_bwd_dkdv_seq_kernel<false>, grid, dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k,
-                           (const __bf16 *)v, ld, (const __bf16 *)d_o, ld_out, lse, delta, (int)N, (int)H, scale, scale_log2,
-                           (const __bf16 *)nullptr, (int64_t)0, (__bf16 *)dk, (__bf16 *)dv, ld_d);
+        hipLaunchKernelGGL((attn_bwd_dkdv_seq_kernel<T, false>), grid, dim3(256), 0, st, (const T *)q, (const T *)k,
+                           (const T *)v, ld, (const T *)d_o, ld_out, lse, delta, (int)N, (int)H, scale, scale_log2,
+                           (const T *)nullptr, (int64_t)0, (T *)dk, (T *)dv, ld_d);
     return check_launch("attn_bwd_dkdv_seq");
 }
+
+template int attn_fwd_seq<__bf16>(const void *, const void *, const void *, int64_t, int64_t, int64_t, int64_t, float, const void *,
+                                  int64_t, void *, int64_t, float *, hipStream_t);
+template int attn_fwd_seq<_Float16>(const void *, const void *, const void *, int64_t, int64_t, int64_t, int64_t, float, const void *,
+                                    int64_t, void *, int64_t, float *, hipStream_t);
+template int attn_bwd_seq<__bf16>(const void *, const void *, const void *, int64_t, const void *, const void *, int64_t, const float *,
+                                  int64_t, int64_t, int64_t, float, const void *, const void *, int64_t, void *, float *, void *, void *,
+                                  void *, int64_t, hipStream_t);
+template int attn_bwd_seq<_Float16>(const void *, const void *, const void *, int64_t, const void *, const void *, int64_t,
+                                    const float *, int64_t, int64_t, int64_t, float, const void *, const void *, int64_t, void *, float *,
+                                    void *, void *, void *, int64_t, hipStream_t);
 
 }  // namespace attn
 }  // namespace vah

@@ -1,4 +1,4 @@
-// Fused softmax attention forward for gfx950, bf16 in / bf16 out, fp32 accumulate, head_dim 64.
+// Fused softmax attention forward for gfx950, bf16 or fp16 in / out (T, attn_common.h), fp32 accumulate, head_dim 64.
 //
 // Arithmetic of the reference's Attention / WindowedAttention
 // (/root/reference/detection/mmdet_custom/models/backbones/base/vit.py:83-88,154-159):
@@ -29,13 +29,14 @@ constexpr int kWaves = 4;
 constexpr int kQBlock = 32 * kWaves;     // queries per workgroup
 constexpr int kKTile = 64;               // keys per step
 
+template <typename T>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
-    const __bf16 *__restrict__ q, const __bf16 *__restrict__ k, const __bf16 *__restrict__ vt,
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ vt,
     int64_t ld, RowMap rm, int N, int Np, int H, float scale_log2,
-    __bf16 *__restrict__ out, int64_t ld_out, float *__restrict__ lse) {
+    T *__restrict__ out, int64_t ld_out, float *__restrict__ lse) {
     // double buffered: tile t+1 is written while tile t is being multiplied (one barrier per tile)
-    __shared__ __attribute__((aligned(16))) __bf16 s_k2[2][kKTile * kPadRow];
-    __shared__ __attribute__((aligned(16))) __bf16 s_vt2[2][kHD * kPadT];
+    __shared__ __attribute__((aligned(16))) T s_k2[2][kKTile * kPadRow];
+    __shared__ __attribute__((aligned(16))) T s_vt2[2][kHD * kPadT];
 
     const int h = blockIdx.y, b = blockIdx.z;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -43,17 +44,17 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const int qrow = blockIdx.x * kQBlock + wave * 32 + r;           // this lane's query
     const int qload = min(qrow, N - 1);
 
-    const __bf16 *qb = q + (int64_t)h * kHD;
-    const __bf16 *kb = k + (int64_t)h * kHD;
-    const __bf16 *vtb = vt + ((int64_t)(b * H + h) * kHD) * Np;
+    const T *qb = q + (int64_t)h * kHD;
+    const T *kb = k + (int64_t)h * kHD;
+    const T *vtb = vt + ((int64_t)(b * H + h) * kHD) * Np;
     const int64_t gq = grow(rm, b, qload, N);          // -1: padded token, q = 0
 
-    bf16x8 qf[4];
+    vec8<T> qf[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) qf[kk][j] = (__bf16)0.f;
-        if (gq >= 0) qf[kk] = *reinterpret_cast<const bf16x8 *>(qb + gq * ld + 16 * kk + 8 * hf);
+        for (int j = 0; j < 8; ++j) qf[kk][j] = (T)0.f;
+        if (gq >= 0) qf[kk] = *reinterpret_cast<const vec8<T> *>(qb + gq * ld + 16 * kk + 8 * hf);
     }
 
     f32x16 o[2] = {zero16(), zero16()};
@@ -62,27 +63,27 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     // staging: 512 16-byte chunks per tile and per matrix, 2 per thread
     const int c0 = threadIdx.x, c1 = threadIdx.x + 256;
     const int kr0 = c0 >> 3, kc0 = (c0 & 7) * 8, kr1 = c1 >> 3, kc1 = (c1 & 7) * 8;
-    bf16x8 pk0, pk1, pv0, pv1;
+    vec8<T> pk0, pk1, pv0, pv1;
     auto fetch = [&](int key0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) pk0[j] = pk1[j] = (__bf16)0.f;
+        for (int j = 0; j < 8; ++j) pk0[j] = pk1[j] = (T)0.f;
         const int64_t g0 = key0 + kr0 < N ? grow(rm, b, key0 + kr0, N) : -1;
         const int64_t g1 = key0 + kr1 < N ? grow(rm, b, key0 + kr1, N) : -1;
-        if (g0 >= 0) pk0 = *reinterpret_cast<const bf16x8 *>(kb + g0 * ld + kc0);
-        if (g1 >= 0) pk1 = *reinterpret_cast<const bf16x8 *>(kb + g1 * ld + kc1);
-        pv0 = *reinterpret_cast<const bf16x8 *>(vtb + (int64_t)kr0 * Np + key0 + kc0);
-        pv1 = *reinterpret_cast<const bf16x8 *>(vtb + (int64_t)kr1 * Np + key0 + kc1);
+        if (g0 >= 0) pk0 = *reinterpret_cast<const vec8<T> *>(kb + g0 * ld + kc0);
+        if (g1 >= 0) pk1 = *reinterpret_cast<const vec8<T> *>(kb + g1 * ld + kc1);
+        pv0 = *reinterpret_cast<const vec8<T> *>(vtb + (int64_t)kr0 * Np + key0 + kc0);
+        pv1 = *reinterpret_cast<const vec8<T> *>(vtb + (int64_t)kr1 * Np + key0 + kc1);
     };
     auto commit = [&](int buf) {
-        __bf16 *s_k = s_k2[buf], *s_vt = s_vt2[buf];
-        *reinterpret_cast<bf16x8 *>(s_k + kr0 * kPadRow + kc0) = pk0;
-        *reinterpret_cast<bf16x8 *>(s_k + kr1 * kPadRow + kc1) = pk1;
+        T *s_k = s_k2[buf], *s_vt = s_vt2[buf];
+        *reinterpret_cast<vec8<T> *>(s_k + kr0 * kPadRow + kc0) = pk0;
+        *reinterpret_cast<vec8<T> *>(s_k + kr1 * kPadRow + kc1) = pk1;
         // V^T rows are 64 keys wide: two 8-byte halves keep 8-byte alignment under the 136-byte stride
-        const bf16x4 *a0 = reinterpret_cast<const bf16x4 *>(&pv0), *a1 = reinterpret_cast<const bf16x4 *>(&pv1);
-        *reinterpret_cast<bf16x4 *>(s_vt + kr0 * kPadT + kc0) = a0[0];
-        *reinterpret_cast<bf16x4 *>(s_vt + kr0 * kPadT + kc0 + 4) = a0[1];
-        *reinterpret_cast<bf16x4 *>(s_vt + kr1 * kPadT + kc1) = a1[0];
-        *reinterpret_cast<bf16x4 *>(s_vt + kr1 * kPadT + kc1 + 4) = a1[1];
+        const vec4<T> *a0 = reinterpret_cast<const vec4<T> *>(&pv0), *a1 = reinterpret_cast<const vec4<T> *>(&pv1);
+        *reinterpret_cast<vec4<T> *>(s_vt + kr0 * kPadT + kc0) = a0[0];
+        *reinterpret_cast<vec4<T> *>(s_vt + kr0 * kPadT + kc0 + 4) = a0[1];
+        *reinterpret_cast<vec4<T> *>(s_vt + kr1 * kPadT + kc1) = a1[0];
+        *reinterpret_cast<vec4<T> *>(s_vt + kr1 * kPadT + kc1 + 4) = a1[1];
     };
 
     const int ntiles = (N + kKTile - 1) / kKTile;
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
             commit((t + 1) & 1);         // overwrites the buffer tile t-1 lived in
             if (t + 2 < ntiles) fetch((t + 2) * kKTile);
         }
-        const __bf16 *s_k = s_k2[t & 1], *s_vt = s_vt2[t & 1];
+        const T *s_k = s_k2[t & 1], *s_vt = s_vt2[t & 1];
 
         // S^T = K Q^T : two blocks of 32 keys
         f32x16 s[2] = {zero16(), zero16()};
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
         for (int kbk = 0; kbk < 2; ++kbk)
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8 *>(s_k + (kbk * 32 + r) * kPadRow + 16 * kk + 8 * hf);
+                const vec8<T> a = *reinterpret_cast<const vec8<T> *>(s_k + (kbk * 32 + r) * kPadRow + 16 * kk + 8 * hf);
                 s[kbk] = mfma(a, qf[kk], s[kbk]);
             }
         const int key0 = t * kKTile;
@@ -143,10 +144,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
         for (int kbk = 0; kbk < 2; ++kbk)
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) {
-                const bf16x8 pf = pack_half(s[kbk], sp);
+                const vec8<T> pf = pack_half<T>(s[kbk], sp);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 a = load_kperm(s_vt + (db * 32 + r) * kPadT + kbk * 32, sp, hf);
+                    const vec8<T> a = load_kperm(s_vt + (db * 32 + r) * kPadT + kbk * 32, sp, hf);
                     o[db] = mfma(a, pf, o[db]);
                 }
             }
@@ -155,15 +156,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.f / l_tot;
     if (qrow < N && gq >= 0) {
-        __bf16 *op = out + gq * ld_out + (int64_t)h * kHD;
+        T *op = out + gq * ld_out + (int64_t)h * kHD;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 w;
+                vec4<T> w;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w[j] = (__bf16)(o[db][4 * g + j] * inv);
-                *reinterpret_cast<bf16x4 *>(op + db * 32 + 8 * g + 4 * hf) = w;
+                for (int j = 0; j < 4; ++j) w[j] = (T)(o[db][4 * g + j] * inv);
+                *reinterpret_cast<vec4<T> *>(op + db * 32 + 8 * g + 4 * hf) = w;
             }
         if (hf == 0) lse[((int64_t)b * H + h) * N + qrow] = m_run + log2f(l_tot);
     } else if (qrow < N && hf == 0) {
@@ -201,69 +202,13 @@ int make_rowmap(const char *fn, int64_t win, int64_t B, int64_t gh, int64_t gw, 
 }  // namespace attn
 }  // namespace vah
 
-extern "C" {
+namespace vah {
+namespace attn {
+namespace {
 
-static int attn_fwd_impl(const char *fn, const void *q, const void *k, const void *v, int64_t ld,
-                         vah::attn::RowMap rm, int64_t B, int64_t H, int64_t N, float scale,
-                         void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream);
-
-int vah_attn_fwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
-                      int64_t B, int64_t H, int64_t N, float scale, void *vt_ws, void *out,
-                      int64_t ld_out, float *lse, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_attn_fwd_bf16";
-    if (N > 0 && batch_stride != N * ld) return fail(VAH_E_SHAPE, "%s: batch_stride must be N*ld", fn);
-    return attn_fwd_impl(fn, q, k, v, ld, attn::RowMap{0, 0, 0, 0, 0}, B, H, N, scale, vt_ws, out, ld_out, lse, stream);
-}
-
-int vah_attn_bias_fwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, int64_t B, int64_t H,
-                           int64_t N, float scale, const void *bias, int64_t ldb, void *out, int64_t ld_out, float *lse,
-                           void *stream) {
-    using namespace vah;
-    using namespace vah::attn;
-    clear_error();
-    const char *fn = "vah_attn_bias_fwd_bf16";
-    if (N > 0 && batch_stride != N * ld) return fail(VAH_E_SHAPE, "%s: batch_stride must be N*ld", fn);
-    if (B < 0 || H < 1 || N < 0 || ld < H * kHD || ld_out < H * kHD || B > 65535 || H > 65535 || N >= (1 << 24) || ldb < N ||
-        ldb % 64)
-        return fail(VAH_E_SHAPE, "%s: bad dims (ldb must be a multiple of 64 >= N)", fn);
-    if (B == 0 || N == 0) return VAH_OK;
-    if (!q || !k || !v || !bias || !out || !lse) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (ld % 8) || ((uintptr_t)out | (uintptr_t)bias) % 8 || (ld_out % 4))
-        return fail(VAH_E_ALIGN, "%s: q/k/v need 16-byte aligned rows (ld %% 8 == 0), out / bias 8-byte", fn);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("attn_bias_fwd_bf16", 4 * B * H * N * kHD * 2 + B * H * N * 4 + B * H * N * N * 2, st, 0, 4 * B * H * N * N * kHD);
-    return attn_fwd_seq(q, k, v, ld, B, H, N, scale, bias, ldb, out, ld_out, lse, st);
-}
-
-int vah_attn_win_fwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t B,
-                          int64_t grid_h, int64_t grid_w, int64_t win, int64_t H, float scale,
-                          void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_attn_win_fwd_bf16";
-    attn::RowMap rm;
-    int64_t Z = 0, N = 0;
-    if (win < 1) return fail(VAH_E_SHAPE, "%s: win must be >= 1", fn);
-    if (int rc = attn::make_rowmap(fn, win, B, grid_h, grid_w, &Z, &N, &rm)) return rc;
-    // windows of <= 224 tokens: one workgroup per (window, head) with K and V resident (attn_win.hip); vt_ws unused
-    if (N <= 224 && Z >= 1 && Z <= 65535 && H >= 1 && H <= 65535 && ld >= H * attn::kHD && ld_out >= H * attn::kHD) {
-        if (!q || !k || !v || !out || !lse) return fail(VAH_E_NULL, "%s: null pointer", fn);
-        if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (ld % 8) || ((uintptr_t)out % 8) || (ld_out % 4))
-            return fail(VAH_E_ALIGN, "%s: q/k/v need 16-byte aligned rows (ld %% 8 == 0), out 8-byte", fn);
-        LaunchScope scope("attn_win_fwd_bf16", 4 * Z * H * N * attn::kHD * 2 + Z * H * N * 4, (hipStream_t)stream, 0,
-                          4 * Z * H * N * N * attn::kHD);
-        return attn::attn_win_fwd_resident(q, k, v, ld, rm, Z, H, N, scale, out, ld_out, lse, (hipStream_t)stream);
-    }
-    return attn_fwd_impl(fn, q, k, v, ld, rm, Z, H, N, scale, vt_ws, out, ld_out, lse, stream);
-}
-
-static int attn_fwd_impl(const char *fn, const void *q, const void *k, const void *v, int64_t ld,
-                         vah::attn::RowMap rm, int64_t B, int64_t H, int64_t N, float scale,
-                         void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream) {
-    using namespace vah;
-    using namespace vah::attn;
+template <typename T>
+int attn_fwd_impl(const char *fn, const void *q, const void *k, const void *v, int64_t ld, RowMap rm, int64_t B, int64_t H,
+                  int64_t N, float scale, void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream) {
     if (B < 0 || H < 1 || N < 0 || ld < H * kHD || ld_out < H * kHD || B > 65535 || H > 65535)
         return fail(VAH_E_SHAPE, "%s: bad dims B=%lld H=%lld N=%lld ld=%lld", fn, (long long)B,
                     (long long)H, (long long)N, (long long)ld);
@@ -276,25 +221,123 @@ static int attn_fwd_impl(const char *fn, const void *q, const void *k, const voi
     hipStream_t st = (hipStream_t)stream;
     if (rm.win == 0) {
         // whole sequences: the lean kernel of attn_flash.hip (no V^T workspace, no transpose launch)
-        LaunchScope scope("attn_fwd_bf16", 4 * B * H * N * kHD * 2 + B * H * N * 4, st, 0, 4 * B * H * N * N * kHD);
-        return attn_fwd_seq(q, k, v, ld, B, H, N, scale, nullptr, 0, out, ld_out, lse, st);
+        LaunchScope scope(tname<T>("attn_fwd_bf16", "attn_fwd_f16"), 4 * B * H * N * kHD * 2 + B * H * N * 4, st, 0,
+                          4 * B * H * N * N * kHD);
+        return attn_fwd_seq<T>(q, k, v, ld, B, H, N, scale, nullptr, 0, out, ld_out, lse, st);
     }
     const int Np = (int)vah_attn_padded_len(N);
     {
-        LaunchScope scope("attn_transpose_bf16", 2 * B * H * N * kHD * 2, st);
-        hipLaunchKernelGGL(transpose_to_dn, dim3(Np / 64, (unsigned)H, (unsigned)B), dim3(256), 0, st,
-                           (const __bf16 *)v, ld, rm, (int)N, Np, (int)H, (__bf16 *)vt_ws);
+        LaunchScope scope(tname<T>("attn_transpose_bf16", "attn_transpose_f16"), 2 * B * H * N * kHD * 2, st);
+        hipLaunchKernelGGL((transpose_to_dn<T>), dim3(Np / 64, (unsigned)H, (unsigned)B), dim3(256), 0, st,
+                           (const T *)v, ld, rm, (int)N, Np, (int)H, (T *)vt_ws);
         if (int rc = check_launch(fn)) return rc;
     }
     const float scale_log2 = scale * 1.4426950408889634f;
-    // algorithmic bytes: q, k, v read once, out written once (bf16) + lse
+    // algorithmic bytes: q, k, v read once, out written once (16-bit) + lse
     // flops: QK^T + PV = 4 * B * heads * N^2 * 64; windows: N = win^2 with the padded keys
-    LaunchScope scope(rm.win ? "attn_win_fwd_bf16" : "attn_fwd_bf16", 4 * B * H * N * kHD * 2 + B * H * N * 4, st, 0,
-                      4 * B * H * N * N * kHD);
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)((N + kQBlock - 1) / kQBlock), (unsigned)H, (unsigned)B),
-                       dim3(256), 0, st, (const __bf16 *)q, (const __bf16 *)k, (const __bf16 *)vt_ws, ld,
-                       rm, (int)N, Np, (int)H, scale_log2, (__bf16 *)out, ld_out, lse);
+    LaunchScope scope(rm.win ? tname<T>("attn_win_fwd_bf16", "attn_win_fwd_f16") : tname<T>("attn_fwd_bf16", "attn_fwd_f16"),
+                      4 * B * H * N * kHD * 2 + B * H * N * 4, st, 0, 4 * B * H * N * N * kHD);
+    hipLaunchKernelGGL((attn_fwd_kernel<T>), dim3((unsigned)((N + kQBlock - 1) / kQBlock), (unsigned)H, (unsigned)B),
+                       dim3(256), 0, st, (const T *)q, (const T *)k, (const T *)vt_ws, ld,
+                       rm, (int)N, Np, (int)H, scale_log2, (T *)out, ld_out, lse);
     return check_launch(fn);
+}
+
+template <typename T>
+int attn_fwd_entry(const char *fn, const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, int64_t B,
+                   int64_t H, int64_t N, float scale, void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream) {
+    clear_error();
+    if (N > 0 && batch_stride != N * ld) return fail(VAH_E_SHAPE, "%s: batch_stride must be N*ld", fn);
+    return attn_fwd_impl<T>(fn, q, k, v, ld, RowMap{0, 0, 0, 0, 0}, B, H, N, scale, vt_ws, out, ld_out, lse, stream);
+}
+
+template <typename T>
+int attn_bias_fwd_entry(const char *fn, const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, int64_t B,
+                        int64_t H, int64_t N, float scale, const void *bias, int64_t ldb, void *out, int64_t ld_out, float *lse,
+                        void *stream) {
+    clear_error();
+    if (N > 0 && batch_stride != N * ld) return fail(VAH_E_SHAPE, "%s: batch_stride must be N*ld", fn);
+    if (B < 0 || H < 1 || N < 0 || ld < H * kHD || ld_out < H * kHD || B > 65535 || H > 65535 || N >= (1 << 24) || ldb < N ||
+        ldb % 64)
+        return fail(VAH_E_SHAPE, "%s: bad dims (ldb must be a multiple of 64 >= N)", fn);
+    if (B == 0 || N == 0) return VAH_OK;
+    if (!q || !k || !v || !bias || !out || !lse) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (ld % 8) || ((uintptr_t)out | (uintptr_t)bias) % 8 || (ld_out % 4))
+        return fail(VAH_E_ALIGN, "%s: q/k/v need 16-byte aligned rows (ld %% 8 == 0), out / bias 8-byte", fn);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("attn_bias_fwd_bf16", "attn_bias_fwd_f16"),
+                      4 * B * H * N * kHD * 2 + B * H * N * 4 + B * H * N * N * 2, st, 0, 4 * B * H * N * N * kHD);
+    return attn_fwd_seq<T>(q, k, v, ld, B, H, N, scale, bias, ldb, out, ld_out, lse, st);
+}
+
+template <typename T>
+int attn_win_fwd_entry(const char *fn, const void *q, const void *k, const void *v, int64_t ld, int64_t B, int64_t grid_h,
+                       int64_t grid_w, int64_t win, int64_t H, float scale, void *vt_ws, void *out, int64_t ld_out, float *lse,
+                       void *stream) {
+    clear_error();
+    RowMap rm;
+    int64_t Z = 0, N = 0;
+    if (win < 1) return fail(VAH_E_SHAPE, "%s: win must be >= 1", fn);
+    if (int rc = make_rowmap(fn, win, B, grid_h, grid_w, &Z, &N, &rm)) return rc;
+    // windows of <= 224 tokens: one workgroup per (window, head) with K and V resident (attn_win.hip); vt_ws unused
+    if (N <= 224 && Z >= 1 && Z <= 65535 && H >= 1 && H <= 65535 && ld >= H * kHD && ld_out >= H * kHD) {
+        if (!q || !k || !v || !out || !lse) return fail(VAH_E_NULL, "%s: null pointer", fn);
+        if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (ld % 8) || ((uintptr_t)out % 8) || (ld_out % 4))
+            return fail(VAH_E_ALIGN, "%s: q/k/v need 16-byte aligned rows (ld %% 8 == 0), out 8-byte", fn);
+        LaunchScope scope(tname<T>("attn_win_fwd_bf16", "attn_win_fwd_f16"), 4 * Z * H * N * kHD * 2 + Z * H * N * 4,
+                          (hipStream_t)stream, 0, 4 * Z * H * N * N * kHD);
+        return attn_win_fwd_resident<T>(q, k, v, ld, rm, Z, H, N, scale, out, ld_out, lse, (hipStream_t)stream);
+    }
+    return attn_fwd_impl<T>(fn, q, k, v, ld, rm, Z, H, N, scale, vt_ws, out, ld_out, lse, stream);
+}
+
+}  // namespace
+}  // namespace attn
+}  // namespace vah
+
+// The bf16 entry points and their fp16 twins: identical arguments, checks and error codes.
+extern "C" {
+
+int vah_attn_fwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
+                      int64_t B, int64_t H, int64_t N, float scale, void *vt_ws, void *out,
+                      int64_t ld_out, float *lse, void *stream) {
+    return vah::attn::attn_fwd_entry<__bf16>("vah_attn_fwd_bf16", q, k, v, ld, batch_stride, B, H, N, scale, vt_ws, out, ld_out,
+                                             lse, stream);
+}
+
+int vah_attn_fwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride,
+                     int64_t B, int64_t H, int64_t N, float scale, void *vt_ws, void *out,
+                     int64_t ld_out, float *lse, void *stream) {
+    return vah::attn::attn_fwd_entry<_Float16>("vah_attn_fwd_f16", q, k, v, ld, batch_stride, B, H, N, scale, vt_ws, out, ld_out,
+                                               lse, stream);
+}
+
+int vah_attn_bias_fwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, int64_t B, int64_t H,
+                           int64_t N, float scale, const void *bias, int64_t ldb, void *out, int64_t ld_out, float *lse,
+                           void *stream) {
+    return vah::attn::attn_bias_fwd_entry<__bf16>("vah_attn_bias_fwd_bf16", q, k, v, ld, batch_stride, B, H, N, scale, bias, ldb,
+                                                  out, ld_out, lse, stream);
+}
+
+int vah_attn_bias_fwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t batch_stride, int64_t B, int64_t H,
+                          int64_t N, float scale, const void *bias, int64_t ldb, void *out, int64_t ld_out, float *lse,
+                          void *stream) {
+    return vah::attn::attn_bias_fwd_entry<_Float16>("vah_attn_bias_fwd_f16", q, k, v, ld, batch_stride, B, H, N, scale, bias, ldb,
+                                                    out, ld_out, lse, stream);
+}
+
+int vah_attn_win_fwd_bf16(const void *q, const void *k, const void *v, int64_t ld, int64_t B,
+                          int64_t grid_h, int64_t grid_w, int64_t win, int64_t H, float scale,
+                          void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream) {
+    return vah::attn::attn_win_fwd_entry<__bf16>("vah_attn_win_fwd_bf16", q, k, v, ld, B, grid_h, grid_w, win, H, scale, vt_ws,
+                                                 out, ld_out, lse, stream);
+}
+
+int vah_attn_win_fwd_f16(const void *q, const void *k, const void *v, int64_t ld, int64_t B,
+                         int64_t grid_h, int64_t grid_w, int64_t win, int64_t H, float scale,
+                         void *vt_ws, void *out, int64_t ld_out, float *lse, void *stream) {
+    return vah::attn::attn_win_fwd_entry<_Float16>("vah_attn_win_fwd_f16", q, k, v, ld, B, grid_h, grid_w, win, H, scale, vt_ws,
+                                                   out, ld_out, lse, stream);
 }
 
 }  // extern "C"

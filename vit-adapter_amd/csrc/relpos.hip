@@ -4,9 +4,9 @@
 // bias[h][i][j] = table[index[i][j]][h] (N x N x heads, N = 1 + Wh * Ww with the class token) and adds it to the scores;
 // autograd scatters the (heads, N, N) gradient back into the (T, heads) table.  Done with torch ops around the MFMA
 // kernels that was 126 ms of a 187 ms BEiT-L step (gather 26, transposed bf16 copies 55, indexing_backward 45).
-//   relpos_build: table, index -> the two operands the attention kernels read: bias * log2(e) as bf16 (heads, N, ldb)
+//   relpos_build: table, index -> the two operands the attention kernels read: bias * log2(e) as bf16 / fp16 (heads, N, ldb)
 //                 and its per-head transpose, both written with coalesced rows (two passes over the index);
-//   relpos_grad:  dS (B, heads, N, ldb) bf16 (written per image by the dQ kernel) -> d table (T, heads): one workgroup
+//   relpos_grad:  dS (B, heads, N, ldb) bf16 / fp16 (written per image by the dQ kernel) -> d table (T, heads): one workgroup
 //                 per (head, slab of query rows) adds its elements into LDS bins (consecutive keys of a row hit
 //                 consecutive bins, so the lanes of a wave do not collide), the slabs' bins are summed by a second
 //                 launch.  The sum order inside a slab is the LDS unit's: results are reproducible to fp32 rounding,
@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "common.h"
 
@@ -22,22 +23,24 @@ namespace {
 
 constexpr float kLog2e = 1.4426950408889634f;
 
-// TRANSPOSED == false: out[h][i][j] = table[index[i][j]][h] * log2e;  true: out[h][j][i] (rows = keys)
-template <bool TRANSPOSED>
+// TRANSPOSED == false: out[h][i][j] = table[index[i][j]][h] * log2e;  true: out[h][j][i] (rows = keys).  E: the 16-bit type of
+// the attention operands (__bf16 or _Float16)
+template <typename E, bool TRANSPOSED>
 __global__ __launch_bounds__(256) void relpos_build_kernel(const float *__restrict__ table, const int64_t *__restrict__ index, int N,
-                                                           int H, int64_t ldb, __bf16 *__restrict__ out) {
+                                                           int H, int64_t ldb, E *__restrict__ out) {
     const int col = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;        // out[h][row][col]
     if (col >= ldb) return;
     if (col >= N) {                      // padding columns: zero (the kernels read them in their last tile)
-        for (int h = 0; h < H; ++h) out[((int64_t)h * N + row) * ldb + col] = (__bf16)0.f;
+        for (int h = 0; h < H; ++h) out[((int64_t)h * N + row) * ldb + col] = (E)0.f;
         return;
     }
     const int64_t t = TRANSPOSED ? index[(int64_t)col * N + row] : index[(int64_t)row * N + col];
     const float *tp = table + t * H;
-    for (int h = 0; h < H; ++h) out[((int64_t)h * N + row) * ldb + col] = (__bf16)(tp[h] * kLog2e);
+    for (int h = 0; h < H; ++h) out[((int64_t)h * N + row) * ldb + col] = (E)(tp[h] * kLog2e);
 }
 
-__global__ __launch_bounds__(256) void relpos_grad_kernel(const __bf16 *__restrict__ ds, const int64_t *__restrict__ index, int B,
+template <typename E>
+__global__ __launch_bounds__(256) void relpos_grad_kernel(const E *__restrict__ ds, const int64_t *__restrict__ index, int B,
                                                           int H, int N, int64_t ldb, int T, int rows_per_slab,
                                                           float *__restrict__ part) {
     extern __shared__ float s_bins[];
@@ -75,46 +78,66 @@ __global__ __launch_bounds__(256) void relpos_grad_reduce(const float *__restric
 
 constexpr int kSlabs = 32;
 
+template <typename E>
+int relpos_bias_build(const char *fn, const float *table, const int64_t *index, int64_t T, int64_t H, int64_t N, int64_t ldb,
+                      void *bias, void *bias_t, void *stream) {
+    clear_error();
+    if (T < 1 || H < 1 || N < 1 || ldb < N || N > 65535) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (!table || !index || !bias || !bias_t) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(std::is_same<E, _Float16>::value ? "relpos_bias_build_f16" : "relpos_bias_build", 2 * N * N * 8 + 2 * H * N * N * 2,
+                      st);
+    const dim3 grid((unsigned)((ldb + 255) / 256), (unsigned)N);
+    hipLaunchKernelGGL((relpos_build_kernel<E, false>), grid, dim3(256), 0, st, table, index, (int)N, (int)H, ldb, (E *)bias);
+    hipLaunchKernelGGL((relpos_build_kernel<E, true>), grid, dim3(256), 0, st, table, index, (int)N, (int)H, ldb, (E *)bias_t);
+    return check_launch(fn);
+}
+
+template <typename E>
+int relpos_bias_grad(const char *fn, const void *ds, const int64_t *index, int64_t B, int64_t H, int64_t N, int64_t ldb, int64_t T,
+                     float *ws, float *dtable, void *stream) {
+    clear_error();
+    if (T < 1 || H < 1 || N < 1 || B < 1 || ldb < N || H > 65535 || T * 4 > 150 * 1024) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (!ds || !index || !ws || !dtable) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows_per_slab = (int)((N + kSlabs - 1) / kSlabs), slabs = (int)((N + rows_per_slab - 1) / rows_per_slab);
+    const int lds = (int)(T * 4);
+    if (int rc = allow_dynamic_lds((const void *)relpos_grad_kernel<E>, lds, fn)) return rc;
+    LaunchScope scope(std::is_same<E, _Float16>::value ? "relpos_bias_grad_f16" : "relpos_bias_grad", B * H * N * N * 2 + N * N * 8, st);
+    hipLaunchKernelGGL((relpos_grad_kernel<E>), dim3(slabs, (unsigned)H), dim3(256), lds, st, (const E *)ds, index, (int)B, (int)H,
+                       (int)N, ldb, (int)T, rows_per_slab, ws);
+    if (int rc = check_launch(fn)) return rc;
+    hipLaunchKernelGGL(relpos_grad_reduce, dim3((unsigned)((T * H + 255) / 256)), dim3(256), 0, st, (const float *)ws, slabs, (int)H,
+                       (int)T, dtable);
+    return check_launch(fn);
+}
+
 }  // namespace
 }  // namespace vah
 
+// bias / bias_t / ds are bf16 in the plain entry points, fp16 in the _f16 twins (same arguments, checks and error codes)
 extern "C" {
 
 int vah_relpos_bias_build(const float *table, const int64_t *index, int64_t T, int64_t H, int64_t N, int64_t ldb, void *bias,
                           void *bias_t, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_relpos_bias_build";
-    if (T < 1 || H < 1 || N < 1 || ldb < N || N > 65535) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (!table || !index || !bias || !bias_t) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("relpos_bias_build", 2 * N * N * 8 + 2 * H * N * N * 2, st);
-    const dim3 grid((unsigned)((ldb + 255) / 256), (unsigned)N);
-    hipLaunchKernelGGL(relpos_build_kernel<false>, grid, dim3(256), 0, st, table, index, (int)N, (int)H, ldb, (__bf16 *)bias);
-    hipLaunchKernelGGL(relpos_build_kernel<true>, grid, dim3(256), 0, st, table, index, (int)N, (int)H, ldb, (__bf16 *)bias_t);
-    return check_launch(fn);
+    return vah::relpos_bias_build<__bf16>("vah_relpos_bias_build", table, index, T, H, N, ldb, bias, bias_t, stream);
+}
+
+int vah_relpos_bias_build_f16(const float *table, const int64_t *index, int64_t T, int64_t H, int64_t N, int64_t ldb, void *bias,
+                              void *bias_t, void *stream) {
+    return vah::relpos_bias_build<_Float16>("vah_relpos_bias_build_f16", table, index, T, H, N, ldb, bias, bias_t, stream);
 }
 
 int64_t vah_relpos_bias_grad_ws_floats(int64_t T, int64_t H) { return vah::kSlabs * H * T; }
 
 int vah_relpos_bias_grad(const void *ds, const int64_t *index, int64_t B, int64_t H, int64_t N, int64_t ldb, int64_t T, float *ws,
                          float *dtable, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_relpos_bias_grad";
-    if (T < 1 || H < 1 || N < 1 || B < 1 || ldb < N || H > 65535 || T * 4 > 150 * 1024) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (!ds || !index || !ws || !dtable) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    hipStream_t st = (hipStream_t)stream;
-    const int rows_per_slab = (int)((N + kSlabs - 1) / kSlabs), slabs = (int)((N + rows_per_slab - 1) / rows_per_slab);
-    const int lds = (int)(T * 4);
-    if (int rc = allow_dynamic_lds((const void *)relpos_grad_kernel, lds, fn)) return rc;
-    LaunchScope scope("relpos_bias_grad", B * H * N * N * 2 + N * N * 8, st);
-    hipLaunchKernelGGL(relpos_grad_kernel, dim3(slabs, (unsigned)H), dim3(256), lds, st, (const __bf16 *)ds, index, (int)B, (int)H, (int)N,
-                       ldb, (int)T, rows_per_slab, ws);
-    if (int rc = check_launch(fn)) return rc;
-    hipLaunchKernelGGL(relpos_grad_reduce, dim3((unsigned)((T * H + 255) / 256)), dim3(256), 0, st, (const float *)ws, slabs, (int)H, (int)T,
-                       dtable);
-    return check_launch(fn);
+    return vah::relpos_bias_grad<__bf16>("vah_relpos_bias_grad", ds, index, B, H, N, ldb, T, ws, dtable, stream);
+}
+
+int vah_relpos_bias_grad_f16(const void *ds, const int64_t *index, int64_t B, int64_t H, int64_t N, int64_t ldb, int64_t T, float *ws,
+                             float *dtable, void *stream) {
+    return vah::relpos_bias_grad<_Float16>("vah_relpos_bias_grad_f16", ds, index, B, H, N, ldb, T, ws, dtable, stream);
 }
 
 }  // extern "C"

@@ -100,12 +100,12 @@ class Attention(nn.Module):
             qkv_bias = torch.cat((self.q_bias, torch.zeros_like(self.v_bias, requires_grad=False), self.v_bias))
         packed = F.linear(x, self.qkv.weight, qkv_bias).reshape(B, N, 3, self.num_heads, -1)
         drop = self.attn_drop.p if self.training else 0.
-        fast = x.is_cuda and packed.dtype == torch.bfloat16 and drop == 0.
+        fast = x.is_cuda and packed.dtype in (torch.bfloat16, torch.float16) and drop == 0.
         out = None
         if (fast and rel_pos_bias is None and self.relative_position_bias_table is not None
                 and N == self.window_size[0] * self.window_size[1] + 1):
-            # bf16 autocast: the MFMA kernels of csrc/attn_flash.hip with the relative position bias as an additive term
-            # inside them, its two bf16 operands built straight from the table (no (heads, N, N) fp32 tensor)
+            # bf16 / fp16 autocast: the MFMA kernels of csrc/attn_flash.hip with the relative position bias as an additive term
+            # inside them, its two 16-bit operands built straight from the table (no (heads, N, N) fp32 tensor)
             out = kernels.attention_relpos(packed, self.relative_position_bias_table, self.relative_position_index, self.scale)
         bias = None
         if out is None:

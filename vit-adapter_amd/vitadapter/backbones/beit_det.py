@@ -7,7 +7,7 @@ qkv projection, base/beit.py:175-195 - unlike the ViT flavour, which pads q, k, 
 ``window_size``^2 grid, every block with its own relative position bias table of (2 w - 1)^2 rows; parameter names and
 shapes equal the reference's.  Used by the htc++ configs (window_attn / window_size lists, 14 and 56).
 
-Under bf16 autocast on the GPU the attention runs on the MFMA kernels of csrc/attn_flash.hip with the bias as an
+Under bf16 or fp16 autocast on the GPU the attention runs on the MFMA kernels of csrc/attn_flash.hip with the bias as an
 additive term (kernels.attention_relpos): the windows of a block are one batch of sequences for them, because here the
 projection output already is per-window contiguous.
 """
@@ -67,7 +67,7 @@ class Attention(nn.Module):
         packed = F.linear(x, self.qkv.weight, qkv_bias).reshape(B, N, 3, self.num_heads, -1)
         drop = self.attn_drop.p if self.training else 0.
         out = None
-        if x.is_cuda and packed.dtype == torch.bfloat16 and drop == 0. and rel_pos_bias is None:
+        if x.is_cuda and packed.dtype in (torch.bfloat16, torch.float16) and drop == 0. and rel_pos_bias is None:
             out = kernels.attention_relpos(packed, self.relative_position_bias_table, self.relative_position_index, self.scale)
         if out is None:                      # the reference's op order
             q, k, v = packed.permute(2, 0, 3, 1, 4).unbind(0)
