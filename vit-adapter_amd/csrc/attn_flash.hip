@@ -418,6 +418,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_seq_kernel(
             for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) bv[qb][g] = *reinterpret_cast<const vec4<T> *>(bp + 32 * qb + 8 * g);
+            // columns beyond N are ignored by contract: lse = +inf meets a non-finite entry there as NaN, so the last
+            // tile zeroes them (-inf + 0: p = 0 for queries that do not exist)
+            if (t == ntiles - 1) {
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (t * kKT + 32 * qb + 8 * g + 4 * hf + j >= N) bv[qb][g][j] = (T)0.f;
+            }
         }
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
