@@ -364,8 +364,17 @@ int vah_colsum_f32(const float *g, int64_t batch, int64_t batch_stride, int64_t 
  *   bwd_stats:  sums[0:C] = sum dy, sums[C:2C] = sum dy * xhat
  *   bwd_apply:  dt = gamma * rstd * (dy - mdy - xhat * mdyx);  da, db <- dt (own dtypes, may be NULL);
  *               dxlo += upsample^T(dt)  (fp32, zero-filled by the caller; NULL to skip)
- * The caller owns the statistics between the passes (SyncBatchNorm all-reduces them there). */
+ * The caller owns the statistics between the passes (SyncBatchNorm all-reduces them there).
+ * ws needs no initialisation: each call writes every partial row it reads.
+ * Limits, the same for all four passes (VAH_E_SHAPE, decided on the host before any launch, from N, C, H, W, scale and
+ * x != NULL alone, so a forward that ran has a backward that runs):  N <= 512 (one partial row of ws per image and
+ * chunk of rows);  N * C * H * W < 2^40;  W <= 8192;  with x and scale > 1, a tile of rows_per_block rows of
+ * (W + W / scale) floats must fit 150 KB of LDS, where rows_per_block = 8192 / W rounded down to a multiple of
+ * 2 * scale (at least 2 * scale, at most H) while N * ceil(H / rows_per_block) <= 512, and otherwise
+ * ceil(H / floor(512 / N)) rounded up to a multiple of 2 * scale: 256 x 256 at scale 4 runs up to N = 170.
+ * vah_bn_tail_supported answers 1 where the four passes accept the shape and 0 where they refuse it. */
 int64_t vah_bn_tail_ws_floats(int64_t C);
+int vah_bn_tail_supported(int64_t N, int64_t C, int64_t H, int64_t W, int scale, int has_x);
 int vah_bn_tail_stats(const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale,
                       int64_t N, int64_t C, int64_t H, int64_t W, const float *shift, float *sums, float *ws,
                       void *stream);

@@ -221,8 +221,9 @@ __device__ __forceinline__ float block_sum(float v, float *s_red) {      // 256 
     return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
-// part[(n * chunks + chunk)][2C]: (sum t | sum t^2) of the block's pixels, for its channel only; the
-// other columns of the row are left untouched, so the partial buffer is zero-filled by the host.
+// part[(n * chunks + chunk)][2C]: (sum t | sum t^2) of the block's pixels, for its channel only.  The C planes of
+// one (n, chunk) between them write every column of its row and tail_finalize reads the N * chunks (<= kTailParts)
+// rows that were written and no other, so the partial buffer needs no initialisation.
 __global__ __launch_bounds__(256) void tail_stats_kernel(Operands o, float *__restrict__ part) {
     __shared__ float s_red[4];
     const int64_t plane = blockIdx.x / o.chunks;
@@ -583,22 +584,17 @@ __global__ __launch_bounds__(256) void maxpool3s2_bwd_kernel(const __bf16 *__res
     }
 }
 
-int fill_operands(const char *fn, Operands &o, const void *a, int a_bf16, const void *b, int b_bf16, const float *x,
-                  int scale, int64_t N, int64_t C, int64_t H, int64_t W) {
+constexpr size_t kTailLdsMax = 150 * 1024;      // dynamic LDS of tail_bwd_apply_kernel (160 KB per CU on gfx950)
+
+// The shape rule and the tiling plan of all four passes (and of vah_bn_tail_supported): a shape is accepted by
+// every entry point or by none, whichever pointers a particular call passes.
+int plan_tail(const char *fn, Operands &o, int has_x, int scale, int64_t N, int64_t C, int64_t H, int64_t W) {
     if (N < 1 || C < 1 || H < 1 || W < 4 || W % 4 || W > kTilePx) return fail(VAH_E_SHAPE, "%s: bad shape", fn);
     if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return fail(VAH_E_SHAPE, "%s: scale must be 1, 2, 4 or 8", fn);
-    if (x && (H % scale || W % scale || (W / scale) % 4)) return fail(VAH_E_SHAPE, "%s: H, W not multiples of the scale", fn);
+    if (has_x && (H % scale || W % scale || (W / scale) % 4)) return fail(VAH_E_SHAPE, "%s: H, W not multiples of the scale", fn);
     if (N * C * H * W >= ((int64_t)1 << 40)) return fail(VAH_E_SHAPE, "%s: too large", fn);
-    if (!a) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)a | (uintptr_t)b) % 8 || (uintptr_t)x % 16 || (!a_bf16 && (uintptr_t)a % 16) || (b && !b_bf16 && (uintptr_t)b % 16))
-        return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    o.relu = o.y_bf16 = o.dy_bf16 = 0;
-    o.shift = nullptr;
-    o.a = a;
-    o.b = b;
-    o.x = x;
-    o.a_bf16 = a_bf16;
-    o.b_bf16 = b_bf16;
+    // every (image, chunk) owns one partial row of the workspace, and an image has at least one chunk
+    if (N > kTailParts) return fail(VAH_E_SHAPE, "%s: batch %lld above %d", fn, (long long)N, kTailParts);
     o.scale = scale;
     o.C = (int)C;
     o.H = (int)H;
@@ -618,7 +614,28 @@ int fill_operands(const char *fn, Operands &o, const void *a, int a_bf16, const 
     }
     // exact for items < 2^16 (a block has rows_per_block * W / 4 <= 8192 / 4 + 2 * scale * W / 4 of them)
     if ((int64_t)o.rows_per_block * (W / 4) >= 65536) return fail(VAH_E_SHAPE, "%s: row too wide for the tiling", fn);
+    // the adjoint of the upsample stages a tile of dt and its column sums in LDS; the forward passes are held to
+    // the same limit, so that a forward that ran has a backward that runs
+    if (has_x && scale > 1 && (size_t)o.rows_per_block * (o.W + o.Wl) * sizeof(float) > kTailLdsMax)
+        return fail(VAH_E_SHAPE, "%s: a tile of %d rows x (%d + %d) floats does not fit %d KB of LDS (batch too large for "
+                    "this map, or rows too wide)", fn, o.rows_per_block, o.W, o.Wl, (int)(kTailLdsMax / 1024));
     o.quad_magic = W / 4 > 1 ? (unsigned)(((uint64_t)1 << 32) / (uint64_t)(W / 4)) + 1u : 0u;      // one quad per row: no division
+    return VAH_OK;
+}
+
+int fill_operands(const char *fn, Operands &o, const void *a, int a_bf16, const void *b, int b_bf16, const float *x,
+                  int scale, int64_t N, int64_t C, int64_t H, int64_t W) {
+    if (int rc = plan_tail(fn, o, x != nullptr, scale, N, C, H, W)) return rc;
+    if (!a) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)a | (uintptr_t)b) % 8 || (uintptr_t)x % 16 || (!a_bf16 && (uintptr_t)a % 16) || (b && !b_bf16 && (uintptr_t)b % 16))
+        return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    o.relu = o.y_bf16 = o.dy_bf16 = 0;
+    o.shift = nullptr;
+    o.a = a;
+    o.b = b;
+    o.x = x;
+    o.a_bf16 = a_bf16;
+    o.b_bf16 = b_bf16;
     return VAH_OK;
 }
 
@@ -683,6 +700,13 @@ __global__ __launch_bounds__(256) void pixel_shuffle2_kernel(const __bf16 *__res
 extern "C" {
 
 int64_t vah_bn_tail_ws_floats(int64_t C) { return (int64_t)vah::kTailParts * 2 * C; }
+
+int vah_bn_tail_supported(int64_t N, int64_t C, int64_t H, int64_t W, int scale, int has_x) {
+    using namespace vah;
+    clear_error();
+    Operands o;
+    return plan_tail("vah_bn_tail_supported", o, has_x != 0, scale, N, C, H, W) == VAH_OK ? 1 : 0;
+}
 
 int vah_bn_tail_stats(const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale, int64_t N,
                       int64_t C, int64_t H, int64_t W, const float *shift, float *sums, float *ws, void *stream) {
@@ -761,7 +785,6 @@ int vah_bn_tail_bwd_apply(const void *a, int a_bf16, const void *b, int b_bf16, 
     hipStream_t st = (hipStream_t)stream;
     size_t smem = 0;
     if (dxlo && x && scale > 1) smem = (size_t)o.rows_per_block * (o.W + o.Wl) * sizeof(float);
-    if (smem > 150 * 1024) return fail(VAH_E_SHAPE, "%s: tile does not fit LDS", fn);
     LaunchScope scope("bn_tail_bwd_apply", N * C * H * W * (2 * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0)) + 4), st);
     if (smem > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)tail_bwd_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);

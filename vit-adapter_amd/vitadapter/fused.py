@@ -1227,6 +1227,13 @@ def _bn_fusable(norm, a):
             and (norm.weight is None or norm.weight.dtype == torch.float32))
 
 
+def _tail_shape_ok(a, scale, has_x):
+    """the shape rule of the four vah_bn_tail_* entry points (batch and LDS-tile limits included): what they refuse
+    takes the reference expression"""
+    N, C, H, W = a.shape
+    return bool(_vah.lib.vah_bn_tail_supported(N, C, H, W, scale, int(has_x)))
+
+
 def tail_takes_conv_bias(norm, ref):
     """True when bn_tail will run fused for inputs like ``ref``: the caller may then run the
     convolutions that feed it WITHOUT bias and hand the biases to bn_tail as ``shift``."""
@@ -1253,7 +1260,7 @@ def bn_tail(norm, a, b=None, x=None, scale=1, shift=None):
             and (b is None or (b.shape == a.shape and b.dtype in (torch.bfloat16, torch.float32)))
             and scale in (1, 2, 4, 8) and a.shape[3] % (4 * scale) == 0 and a.shape[2] % scale == 0
             and tuple(x.shape) == (a.shape[0], a.shape[1], a.shape[2] // scale, a.shape[3] // scale)
-            and x.dtype in (torch.bfloat16, torch.float32)):
+            and x.dtype in (torch.bfloat16, torch.float32) and _tail_shape_ok(a, scale, True)):
         return _BNTail.apply(a, b, x, norm.weight, norm.bias, shift, norm, scale, False, torch.float32)
     t = a if b is None else a + b
     if shift is not None:
@@ -1271,7 +1278,8 @@ def bn_relu(norm, a):
     (adapter_modules.py:217-241): statistics pass + normalise-and-clamp pass, output in a's dtype;
     the backward recomputes the ReLU mask from ``a``."""
     # the two-pass form pays from a few million elements on (below that MIOpen's single kernel wins)
-    if ENABLED['bn_relu'] and _bn_fusable(norm, a) and a.shape[3] % 4 == 0 and a.numel() >= BN_RELU_MIN_NUMEL:
+    if (ENABLED['bn_relu'] and _bn_fusable(norm, a) and a.shape[3] % 4 == 0 and a.numel() >= BN_RELU_MIN_NUMEL
+            and _tail_shape_ok(a, 1, False)):
         return _BNTail.apply(a, None, None, norm.weight, norm.bias, None, norm, 1, True, a.dtype)
     return F.relu(norm(a))
 
