@@ -528,6 +528,42 @@ int vah_dwconv3x3_tokens_bf16(const void *x, const float *w, const float *bias, 
 int vah_dwconv3x3_tokens_wgrad_bf16(const void *x, const void *g, int64_t B, int64_t H, int64_t W,
                                     int64_t C, float *dw, float *db, float *ws, void *stream);
 
+/* ---- fp16 twins of the row-streaming kernels above (fp16 autocast, the reference's AMP mode) ----
+ * The same kernels instantiated on _Float16 for every 16-bit operand (y / h / ya / yb, g / gh / ga / gb, z, dz, the
+ * DWConv rows and their gradients): same signatures, argument checks, error codes and messages (with the function
+ * name changed), same launch geometry and workspace sizes (vah_reduce_ws_floats serves both types).  All arithmetic,
+ * statistics, partial rows and parameter gradients are fp32 as in the bf16 form.  fp32 -> fp16 stores round to nearest
+ * even, overflow to +-inf and keep subnormals (what torch's .to(float16) does): a loss-scaled gradient in fp16's
+ * subnormal range survives and an overflow reaches GradScaler as inf.  Profiler rows carry an _f16 suffix
+ * ("layernorm_fwd_f16", "residual_layernorm_bwd_f16", "dwconv_tokens_dgrad_f16", ...) with the same byte accounting. */
+int vah_layernorm_fwd_f32_f16(const float *x, const float *w, const float *b, int64_t rows, int64_t C,
+                              float eps, void *y_f16, float *mean, float *rstd, void *stream);
+int vah_layernorm_bwd_f32_f16(const float *x, const void *g_f16, const float *w, const float *mean,
+                              const float *rstd, const float *gres, int64_t rows, int64_t C,
+                              float *dx, float *dw, float *db, float *ws /* K = 2C */, void *stream);
+int vah_residual_layernorm_fwd_f16(const float *x, const void *z_f16, const float *gamma, const float *sc,
+                                   int64_t batch, int64_t rows_per_batch, int64_t C, const float *w, const float *b,
+                                   float eps, float *t, void *h_f16, float *mean, float *rstd, void *stream);
+int vah_residual_layernorm_bwd_f16(const float *t, const void *gh_f16, const float *w, const float *mean,
+                                   const float *rstd, const float *gt, const void *z_f16, const float *gamma,
+                                   const float *sc, int64_t batch, int64_t rows_per_batch, int64_t C, float *dt,
+                                   void *dz_f16, float *dgamma, float *dw, float *db, float *ws, void *stream);
+int vah_layernorm_dual_fwd_f16(const float *x, const float *wa, const float *ba, const float *wb, const float *bb,
+                               int64_t rows, int64_t C, float eps, void *ya_f16, void *yb_f16, float *mean,
+                               float *rstd, void *stream);
+int vah_layernorm_dual_bwd_f16(const float *x, const void *ga_f16, const void *gb_f16, const float *wa, const float *wb,
+                               const float *mean, const float *rstd, const float *gres, int64_t rows, int64_t C,
+                               float *dx, float *dparams, float *ws, void *stream);
+int vah_scale_residual_fwd_f16(const float *x, const void *z_f16, const float *gamma, const float *s,
+                               int64_t batch, int64_t rows_per_batch, int64_t C, float *y, void *stream);
+int vah_scale_residual_bwd_f16(const float *g, const void *z_f16, const float *gamma, const float *s,
+                               int64_t batch, int64_t rows_per_batch, int64_t C,
+                               void *dz_f16, float *dgamma, float *ws, void *stream);
+int vah_dwconv3x3_tokens_f16(const void *x, const float *w, const float *bias, int64_t B, int64_t H,
+                             int64_t W, int64_t C, int mode, void *y, void *stream);
+int vah_dwconv3x3_tokens_wgrad_f16(const void *x, const void *g, int64_t B, int64_t H, int64_t W,
+                                   int64_t C, float *dw, float *db, float *ws, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch timing (bench.py's roofline leg).  While enabled, every kernel launched through
  * this library is bracketed by two hipEvents recorded on the launch's own stream.

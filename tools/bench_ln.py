@@ -1,6 +1,10 @@
 #!/usr/bin/env python
 """Row-streaming kernels of the blocks alone: residual + LayerNorm forward / backward at the two row counts of base_det
-(2 x 4096 ViT tokens, 2 x 21504 adapter tokens), C = 768, with the bytes each pass moves."""
+(2 x 4096 ViT tokens, 2 x 21504 adapter tokens), C = 768, with the bytes each pass moves.
+
+    python tools/bench_ln.py [--dtype bf16|fp16]     (the autocast type: the bf16 kernels or their fp16 twins)
+"""
+import argparse
 import os
 import sys
 
@@ -13,7 +17,13 @@ from bench_msda import timeit  # noqa: E402
 from vitadapter import fused  # noqa: E402
 
 
+DTYPES = {'bf16': torch.bfloat16, 'fp16': torch.float16}
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--dtype', choices=sorted(DTYPES), default='bf16', help='autocast type (default bf16)')
+    dt = DTYPES[ap.parse_args().dtype]
     C = 768
     norm = torch.nn.LayerNorm(C, eps=1e-6).cuda()
     gamma = torch.ones(C, device='cuda', requires_grad=True)
@@ -21,8 +31,8 @@ def main():
     _vah.prof_enable(True, 'layernorm,residual_layernorm')
     for rows in (8192, 43008):
         x = torch.randn(2, rows // 2, C, device='cuda', requires_grad=True)
-        z = torch.randn(2, rows // 2, C, device='cuda').to(torch.bfloat16).requires_grad_(True)
-        with torch.autocast('cuda', dtype=torch.bfloat16):
+        z = torch.randn(2, rows // 2, C, device='cuda').to(dt).requires_grad_(True)
+        with torch.autocast('cuda', dtype=dt):
             t, y = fused.residual_ln(x, z, gamma, None, norm)
             tf = timeit(lambda: fused.residual_ln(x, z, gamma, None, norm), iters=30)
         gy, gt = torch.randn_like(y), torch.randn_like(t)
@@ -30,7 +40,7 @@ def main():
         n = rows * C
         print('rows %6d residual+LN fwd %6.1f us (%.2f TB/s on %d MB) | bwd %6.1f us (%.2f TB/s on %d MB)'
               % (rows, tf * 1e6, n * 12 / tf / 1e12, n * 12 >> 20, tb * 1e6, n * 18 / tb / 1e12, n * 18 >> 20), flush=True)
-        with torch.autocast('cuda', dtype=torch.bfloat16):
+        with torch.autocast('cuda', dtype=dt):
             y2 = fused.layer_norm(norm, x)
             tf = timeit(lambda: fused.layer_norm(norm, x), iters=30)
         g2 = torch.randn_like(y2)

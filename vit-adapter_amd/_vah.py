@@ -158,6 +158,17 @@ for _n in ('vah_layernorm_fwd_f32_bf16', 'vah_layernorm_bwd_f32_bf16', 'vah_scal
            'vah_maxpool3s2_nhwc_fwd_bf16', 'vah_maxpool3s2_nhwc_bwd_bf16'):
     getattr(lib, _n).restype = ctypes.c_int
 
+# fp16 twins of the row-streaming kernels of csrc/fused_ops.hip: the bf16 signatures, _Float16 in the 16-bit operands
+FUSED_F16_TWINS = {
+    'vah_layernorm_fwd_f32_bf16': 'vah_layernorm_fwd_f32_f16', 'vah_layernorm_bwd_f32_bf16': 'vah_layernorm_bwd_f32_f16',
+    'vah_residual_layernorm_fwd': 'vah_residual_layernorm_fwd_f16', 'vah_residual_layernorm_bwd': 'vah_residual_layernorm_bwd_f16',
+    'vah_layernorm_dual_fwd': 'vah_layernorm_dual_fwd_f16', 'vah_layernorm_dual_bwd': 'vah_layernorm_dual_bwd_f16',
+    'vah_scale_residual_fwd': 'vah_scale_residual_fwd_f16', 'vah_scale_residual_bwd': 'vah_scale_residual_bwd_f16',
+    'vah_dwconv3x3_tokens_bf16': 'vah_dwconv3x3_tokens_f16', 'vah_dwconv3x3_tokens_wgrad_bf16': 'vah_dwconv3x3_tokens_wgrad_f16',
+}
+for _b16, _f16 in FUSED_F16_TWINS.items():
+    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))
@@ -178,6 +189,9 @@ EXPORTS = (
     'vah_scale_residual_bwd', 'vah_dwconv3x3_tokens_bf16', 'vah_dwconv3x3_tokens_wgrad_bf16', 'vah_colsum_bf16', 'vah_colsum_f32',
     'vah_layernorm_dual_fwd', 'vah_layernorm_dual_bwd',
     'vah_residual_layernorm_fwd', 'vah_residual_layernorm_bwd',
+    'vah_layernorm_fwd_f32_f16', 'vah_layernorm_bwd_f32_f16', 'vah_residual_layernorm_fwd_f16', 'vah_residual_layernorm_bwd_f16',
+    'vah_layernorm_dual_fwd_f16', 'vah_layernorm_dual_bwd_f16', 'vah_scale_residual_fwd_f16', 'vah_scale_residual_bwd_f16',
+    'vah_dwconv3x3_tokens_f16', 'vah_dwconv3x3_tokens_wgrad_f16',
     'vah_gemm_set_tuning', 'vah_gemm_bf16', 'vah_gemm_bf16_fin', 'vah_colsum_bf16_partials', 'vah_gemm_table_dump', 'vah_gemm_table_load', 'vah_gemm_library_version', 'vah_gemm_rejected_candidates',
     'vah_bn_tail_ws_floats', 'vah_bn_tail_supported', 'vah_bn_tail_stats', 'vah_bn_tail_apply', 'vah_bn_tail_bwd_stats', 'vah_bn_tail_bwd_apply',
     'vah_bn_finalize_stats', 'vah_transpose_tokens', 'vah_maxpool3s2_fwd_bf16', 'vah_maxpool3s2_bwd_bf16',

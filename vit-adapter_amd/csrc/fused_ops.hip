@@ -14,6 +14,13 @@
 //                          (ref: segmentation/mmseg_custom/models/backbones/adapter_modules.py:72-87):
 //                          no slice / transpose / contiguous / cat copies, no MIOpen naive bf16
 //                          depthwise kernels (3.3 ms per step measured)
+//
+// The kernels that touch a 16-bit operand are templates on its element type T: __bf16 (bf16 autocast) or
+// _Float16 (fp16 autocast, the *_f16 entry points).  All arithmetic, statistics, partial rows and parameter
+// gradients are fp32 for both; T appears in loads, stores and converts only.  float -> _Float16 is the plain
+// cast (v_cvt_f16_f32 / v_cvt_pk_f16_f32: round to nearest even, overflow to +-inf, subnormals kept - what
+// torch's .to(float16) does): loss-scaled gradients live in fp16's subnormal range and an overflow has to
+// reach GradScaler as inf, so no cvt_pkrtz, no saturation, no flushed denormals.
 #include <algorithm>
 
 #include "common.h"
@@ -23,6 +30,18 @@ namespace {
 
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
+typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
+
+// vector of 4 elements of the kernels' 16-bit type T
+template <typename T> struct Vec16;
+template <> struct Vec16<__bf16> { typedef bf16x4 x4; };
+template <> struct Vec16<_Float16> { typedef f16x4 x4; };
+template <typename T> using vec4 = typename Vec16<T>::x4;
+
+// profiler row of the instantiation: the bf16 name or its _f16 twin
+template <typename T> constexpr const char *tname(const char *bf16_name, const char *f16_name);
+template <> constexpr const char *tname<__bf16>(const char *bf16_name, const char *) { return bf16_name; }
+template <> constexpr const char *tname<_Float16>(const char *, const char *f16_name) { return f16_name; }
 
 constexpr int kMaxVecAll = 8;    // float4 groups per lane: C <= 64 * 4 * 8 = 2048 (template NV <= 8)
 
@@ -32,18 +51,19 @@ constexpr int kMaxVecAll = 8;    // float4 groups per lane: C <= 64 * 4 * 8 = 20
 // With a residual update fused in front (z != NULL):  t = x + sc[b] * gamma * z  is written to `sum`
 // (fp32) and normalised in the same pass - the pattern  x = x + drop_path(gamma * f(..)); h = norm(x)
 // of consecutive sub-blocks (base/vit.py:301-306), which otherwise re-reads x from HBM.
+template <typename T>
 struct ResidualIn {
-    const __bf16 *z;          // NULL: plain LayerNorm of x
+    const T *z;               // NULL: plain LayerNorm of x
     const float *gamma, *sc;  // optional
     int64_t rows_per_batch;
     float *sum;               // t out (forward) / unused (backward)
 };
 
-template <int kMaxVec, bool kRes>
+template <typename T, int kMaxVec, bool kRes>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float *__restrict__ x,
                                                      const float *__restrict__ w,
                                                      const float *__restrict__ b, int64_t rows, int C,
-                                                     float eps, ResidualIn res, __bf16 *__restrict__ y,
+                                                     float eps, ResidualIn<T> res, T *__restrict__ y,
                                                      float *__restrict__ mean, float *__restrict__ rstd) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -54,7 +74,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float *__restrict__ x
     float s = 0.f;
     // every load of the row is requested before the first is used: with the residual operands read
     // under `if (res.z)` inside the slot loop each slot waited for its own x / z / gamma round trip
-    bf16x4 zv[kMaxVec];
+    vec4<T> zv[kMaxVec];
     float4 gm[kMaxVec], wv4[kMaxVec], bv4[kMaxVec];
     float sb = 1.f;
     if constexpr (kRes) sb = res.sc ? res.sc[row / res.rows_per_batch] : 1.f;
@@ -63,7 +83,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float *__restrict__ x
         const int i = min(lane + 64 * j, nvec - 1);          // clamped: dead slots re-read the last vector
         v[j] = *reinterpret_cast<const float4 *>(xr + 4 * i);
         if constexpr (kRes) {
-            zv[j] = *reinterpret_cast<const bf16x4 *>(res.z + row * C + 4 * i);
+            zv[j] = *reinterpret_cast<const vec4<T> *>(res.z + row * C + 4 * i);
             gm[j] = make_float4(1.f, 1.f, 1.f, 1.f);
             if (res.gamma) gm[j] = *reinterpret_cast<const float4 *>(res.gamma + 4 * i);
         }
@@ -98,18 +118,18 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float *__restrict__ x
         }
     }
     const float rs = rsqrtf(wave_sum(q) / (float)C + eps);
-    __bf16 *yr = y + row * C;
+    T *yr = y + row * C;
 #pragma unroll
     for (int j = 0; j < kMaxVec; ++j) {
         const int i = lane + 64 * j;
         if (i < nvec) {
             const float4 ww = wv4[j], bb = bv4[j];
-            bf16x4 o;
-            o[0] = (__bf16)((v[j].x - mu) * rs * ww.x + bb.x);
-            o[1] = (__bf16)((v[j].y - mu) * rs * ww.y + bb.y);
-            o[2] = (__bf16)((v[j].z - mu) * rs * ww.z + bb.z);
-            o[3] = (__bf16)((v[j].w - mu) * rs * ww.w + bb.w);
-            *reinterpret_cast<bf16x4 *>(yr + 4 * i) = o;
+            vec4<T> o;
+            o[0] = (T)((v[j].x - mu) * rs * ww.x + bb.x);
+            o[1] = (T)((v[j].y - mu) * rs * ww.y + bb.y);
+            o[2] = (T)((v[j].z - mu) * rs * ww.z + bb.z);
+            o[3] = (T)((v[j].w - mu) * rs * ww.w + bb.w);
+            *reinterpret_cast<vec4<T> *>(yr + 4 * i) = o;
         }
     }
     if (lane == 0) {
@@ -167,14 +187,14 @@ __global__ __launch_bounds__(256) void finalize_partials(const float *__restrict
 // 512-workgroup grid ran as two back-to-back rounds, each a full load -> reduce -> store latency
 // chain).  The accumulators now live in the wave's own LDS row (plain read-add-write, no atomics:
 // nobody else touches it; ~100 LDS clocks per row) and the weights are read from LDS where used.
-template <int kMaxVec, int kWaves, bool kRes, int kFly>
+template <typename T, int kMaxVec, int kWaves, bool kRes, int kFly>
 __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__restrict__ x,
-                                                     const __bf16 *__restrict__ g,
+                                                     const T *__restrict__ g,
                                                      const float *__restrict__ w,
                                                      const float *__restrict__ mean,
                                                      const float *__restrict__ rstd,
                                                      const float *__restrict__ gres, int64_t rows, int C,
-                                                     ResidualIn res, __bf16 *__restrict__ dz,
+                                                     ResidualIn<T> res, T *__restrict__ dz,
                                                      float *__restrict__ dx, float *__restrict__ part) {
     constexpr int ncol = kRes ? 3 : 2;       // kRes: res.z != nullptr (compile time: its registers)
     extern __shared__ __attribute__((aligned(16))) float s_red[];      // [kWaves][ncol * C] | w[C] | gamma[C]
@@ -198,7 +218,7 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
     for (int64_t row = (int64_t)blockIdx.x * kWaves + wv; row < rows; row += kFly * stride) {
         int64_t rws[kFly];
         float4 xv[kFly][kMaxVec], rv[kFly][kMaxVec];
-        bf16x4 gv[kFly][kMaxVec], zv[kFly][kMaxVec];
+        vec4<T> gv[kFly][kMaxVec], zv[kFly][kMaxVec];
         float mu[kFly], rs[kFly], sb[kFly];
 #pragma unroll
         for (int u = 0; u < kFly; ++u) {
@@ -212,10 +232,10 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
                 const int i = lane + 64 * j;
                 if (i < nvec) {
                     xv[u][j] = *reinterpret_cast<const float4 *>(x + rws[u] * C + 4 * i);
-                    gv[u][j] = *reinterpret_cast<const bf16x4 *>(g + rws[u] * C + 4 * i);
+                    gv[u][j] = *reinterpret_cast<const vec4<T> *>(g + rws[u] * C + 4 * i);
                     rv[u][j] = gres ? *reinterpret_cast<const float4 *>(gres + rws[u] * C + 4 * i)
                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (kRes) zv[u][j] = *reinterpret_cast<const bf16x4 *>(res.z + rws[u] * C + 4 * i);
+                    if constexpr (kRes) zv[u][j] = *reinterpret_cast<const vec4<T> *>(res.z + rws[u] * C + 4 * i);
                 }
             }
         }
@@ -266,12 +286,12 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
                     *reinterpret_cast<float4 *>(dr + 4 * i) = d;
                     if constexpr (kRes) {                 // t = x + sc * gamma * z in front: dz, dgamma from dt = d
                         const float4 gm = *reinterpret_cast<const float4 *>(s_gm + 4 * i);
-                        bf16x4 o;
-                        o[0] = (__bf16)(sb[u] * gm.x * d.x);
-                        o[1] = (__bf16)(sb[u] * gm.y * d.y);
-                        o[2] = (__bf16)(sb[u] * gm.z * d.z);
-                        o[3] = (__bf16)(sb[u] * gm.w * d.w);
-                        *reinterpret_cast<bf16x4 *>(dz + rws[u] * C + 4 * i) = o;
+                        vec4<T> o;
+                        o[0] = (T)(sb[u] * gm.x * d.x);
+                        o[1] = (T)(sb[u] * gm.y * d.y);
+                        o[2] = (T)(sb[u] * gm.z * d.z);
+                        o[3] = (T)(sb[u] * gm.w * d.w);
+                        *reinterpret_cast<vec4<T> *>(dz + rws[u] * C + 4 * i) = o;
                         float4 *pg = reinterpret_cast<float4 *>(acc + 2 * C + 4 * i);
                         float4 ag = *pg;
                         ag.x += sb[u] * d.x * (float)zv[u][j][0];
@@ -303,11 +323,11 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
 //   dx = gres + rstd * (gw - mean(gw) - xhat * mean(gw * xhat)),   gw = ga * wa + gb * wb
 // instead of two chained passes over 132 MB rows.
 // ---------------------------------------------------------------------------------------
-template <int kMaxVec>
+template <typename T, int kMaxVec>
 __global__ __launch_bounds__(256) void ln_dual_fwd_kernel(const float *__restrict__ x, const float *__restrict__ wa,
                                                           const float *__restrict__ ba, const float *__restrict__ wb,
                                                           const float *__restrict__ bb, int64_t rows, int C, float eps,
-                                                          __bf16 *__restrict__ ya, __bf16 *__restrict__ yb,
+                                                          T *__restrict__ ya, T *__restrict__ yb,
                                                           float *__restrict__ mean, float *__restrict__ rstd) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -341,17 +361,17 @@ __global__ __launch_bounds__(256) void ln_dual_fwd_kernel(const float *__restric
             const float4 xh = make_float4((v[j].x - mu) * rs, (v[j].y - mu) * rs, (v[j].z - mu) * rs, (v[j].w - mu) * rs);
             const float4 w1 = *reinterpret_cast<const float4 *>(wa + 4 * i), b1 = *reinterpret_cast<const float4 *>(ba + 4 * i);
             const float4 w2 = *reinterpret_cast<const float4 *>(wb + 4 * i), b2 = *reinterpret_cast<const float4 *>(bb + 4 * i);
-            bf16x4 o1, o2;
-            o1[0] = (__bf16)(xh.x * w1.x + b1.x);
-            o1[1] = (__bf16)(xh.y * w1.y + b1.y);
-            o1[2] = (__bf16)(xh.z * w1.z + b1.z);
-            o1[3] = (__bf16)(xh.w * w1.w + b1.w);
-            o2[0] = (__bf16)(xh.x * w2.x + b2.x);
-            o2[1] = (__bf16)(xh.y * w2.y + b2.y);
-            o2[2] = (__bf16)(xh.z * w2.z + b2.z);
-            o2[3] = (__bf16)(xh.w * w2.w + b2.w);
-            *reinterpret_cast<bf16x4 *>(ya + row * C + 4 * i) = o1;
-            *reinterpret_cast<bf16x4 *>(yb + row * C + 4 * i) = o2;
+            vec4<T> o1, o2;
+            o1[0] = (T)(xh.x * w1.x + b1.x);
+            o1[1] = (T)(xh.y * w1.y + b1.y);
+            o1[2] = (T)(xh.z * w1.z + b1.z);
+            o1[3] = (T)(xh.w * w1.w + b1.w);
+            o2[0] = (T)(xh.x * w2.x + b2.x);
+            o2[1] = (T)(xh.y * w2.y + b2.y);
+            o2[2] = (T)(xh.z * w2.z + b2.z);
+            o2[3] = (T)(xh.w * w2.w + b2.w);
+            *reinterpret_cast<vec4<T> *>(ya + row * C + 4 * i) = o1;
+            *reinterpret_cast<vec4<T> *>(yb + row * C + 4 * i) = o2;
         }
     }
     if (lane == 0) {
@@ -361,9 +381,9 @@ __global__ __launch_bounds__(256) void ln_dual_fwd_kernel(const float *__restric
 }
 
 // partial row: [dwa | dba | dwb | dbb]
-template <int kMaxVec>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kMaxVec <= 3 ? 3 : 1))) void ln_dual_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ ga,
-                                                          const __bf16 *__restrict__ gb, const float *__restrict__ wa,
+template <typename T, int kMaxVec>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kMaxVec <= 3 ? 3 : 1))) void ln_dual_bwd_kernel(const float *__restrict__ x, const T *__restrict__ ga,
+                                                          const T *__restrict__ gb, const float *__restrict__ wa,
                                                           const float *__restrict__ wb, const float *__restrict__ mean,
                                                           const float *__restrict__ rstd, const float *__restrict__ gres,
                                                           int64_t rows, int C, float *__restrict__ dx,
@@ -390,17 +410,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kMaxVec <= 
         // stand-in address + select): with the loads under `ga ? .. : ..` inside the slot loop each vector
         // slot paid its own memory round trip, three per row
         float4 xl[kMaxVec];
-        bf16x4 g1l[kMaxVec], g2l[kMaxVec];
+        vec4<T> g1l[kMaxVec], g2l[kMaxVec];
         {
-            const __bf16 *gap = ga ? ga : reinterpret_cast<const __bf16 *>(x);
-            const __bf16 *gbp = gb ? gb : reinterpret_cast<const __bf16 *>(x);
+            const T *gap = ga ? ga : reinterpret_cast<const T *>(x);
+            const T *gbp = gb ? gb : reinterpret_cast<const T *>(x);
             const float *grp = gres ? gres : x;
 #pragma unroll
             for (int j = 0; j < kMaxVec; ++j) {
                 const int i = min(lane + 64 * j, nvec - 1);
                 xl[j] = *reinterpret_cast<const float4 *>(x + row * C + 4 * i);
-                g1l[j] = *reinterpret_cast<const bf16x4 *>(gap + row * C + 4 * i);
-                g2l[j] = *reinterpret_cast<const bf16x4 *>(gbp + row * C + 4 * i);
+                g1l[j] = *reinterpret_cast<const vec4<T> *>(gap + row * C + 4 * i);
+                g2l[j] = *reinterpret_cast<const vec4<T> *>(gbp + row * C + 4 * i);
                 rv[j] = *reinterpret_cast<const float4 *>(grp + row * C + 4 * i);
             }
         }
@@ -412,9 +432,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kMaxVec <= 
             if (!gres || i >= nvec) rv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < nvec) {
                 const float4 xv = xl[j];
-                bf16x4 g1 = g1l[j], g2 = g2l[j];
-                if (!ga) g1 = bf16x4{};
-                if (!gb) g2 = bf16x4{};
+                vec4<T> g1 = g1l[j], g2 = g2l[j];
+                if (!ga) g1 = vec4<T>{};
+                if (!gb) g2 = vec4<T>{};
                 xh[j] = make_float4((xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs, (xv.w - mu) * rs);
                 const float a0 = (float)g1[0], a1 = (float)g1[1], a2 = (float)g1[2], a3 = (float)g1[3];
                 const float b0 = (float)g2[0], b1 = (float)g2[1], b2 = (float)g2[2], b3 = (float)g2[3];
@@ -547,8 +567,9 @@ __global__ __launch_bounds__(256) void colsum_f32_kernel(const float *__restrict
 // ---------------------------------------------------------------------------------------
 // y = x + s[b] * gamma[c] * z
 // ---------------------------------------------------------------------------------------
+template <typename T>
 __global__ __launch_bounds__(256) void scale_residual_fwd_kernel(
-    const float *__restrict__ x, const __bf16 *__restrict__ z, const float *__restrict__ gamma,
+    const float *__restrict__ x, const T *__restrict__ z, const float *__restrict__ gamma,
     const float *__restrict__ s, int64_t rows_per_batch, int C, int64_t total_vec, float *__restrict__ y) {
     const int nvec = C >> 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total_vec; i += (int64_t)gridDim.x * 256) {
@@ -556,7 +577,7 @@ __global__ __launch_bounds__(256) void scale_residual_fwd_kernel(
         const int cv = (int)(i - row * nvec);
         const float sb = s ? s[row / rows_per_batch] : 1.f;
         const float4 xv = *reinterpret_cast<const float4 *>(x + 4 * i);
-        const bf16x4 zv = *reinterpret_cast<const bf16x4 *>(z + 4 * i);
+        const vec4<T> zv = *reinterpret_cast<const vec4<T> *>(z + 4 * i);
         float4 gm = make_float4(1.f, 1.f, 1.f, 1.f);
         if (gamma) gm = *reinterpret_cast<const float4 *>(gamma + 4 * cv);
         *reinterpret_cast<float4 *>(y + 4 * i) =
@@ -569,10 +590,11 @@ __global__ __launch_bounds__(256) void scale_residual_fwd_kernel(
 // (1 KB of a row), the 4 waves of a workgroup take every 4th row of the strip with 4 rows in flight
 // each (a thread-per-column-group walk with one row in flight ran at 1.5 TB/s); dgamma partials stay
 // in registers and are summed over the 4 waves through LDS.
+template <typename T>
 __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
-    const float *__restrict__ g, const __bf16 *__restrict__ z, const float *__restrict__ gamma,
+    const float *__restrict__ g, const T *__restrict__ z, const float *__restrict__ gamma,
     const float *__restrict__ s, int64_t rows, int64_t rows_per_batch, int C, int rows_per_block,
-    __bf16 *__restrict__ dz, float *__restrict__ part) {
+    T *__restrict__ dz, float *__restrict__ part) {
     __shared__ float4 s_acc[4][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nvec = C >> 2;
@@ -586,7 +608,7 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int64_t r = row0 + wv; r < row1; r += 16) {
             float4 gv[4];
-            bf16x4 zv[4];
+            vec4<T> zv[4];
             float sb[4];
             bool ok[4];
 #pragma unroll
@@ -596,7 +618,7 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
                 if (ok[u]) {
                     const int64_t off = rr * C + 4 * cv;
                     gv[u] = *reinterpret_cast<const float4 *>(g + off);
-                    zv[u] = *reinterpret_cast<const bf16x4 *>(z + off);
+                    zv[u] = *reinterpret_cast<const vec4<T> *>(z + off);
                     sb[u] = s ? s[rr / rows_per_batch] : 1.f;
                 }
             }
@@ -604,12 +626,12 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
             for (int u = 0; u < 4; ++u) {
                 if (!ok[u]) continue;
                 const int64_t off = (r + 4 * u) * C + 4 * cv;
-                bf16x4 o;
-                o[0] = (__bf16)(sb[u] * gm.x * gv[u].x);
-                o[1] = (__bf16)(sb[u] * gm.y * gv[u].y);
-                o[2] = (__bf16)(sb[u] * gm.z * gv[u].z);
-                o[3] = (__bf16)(sb[u] * gm.w * gv[u].w);
-                *reinterpret_cast<bf16x4 *>(dz + off) = o;
+                vec4<T> o;
+                o[0] = (T)(sb[u] * gm.x * gv[u].x);
+                o[1] = (T)(sb[u] * gm.y * gv[u].y);
+                o[2] = (T)(sb[u] * gm.z * gv[u].z);
+                o[3] = (T)(sb[u] * gm.w * gv[u].w);
+                *reinterpret_cast<vec4<T> *>(dz + off) = o;
                 acc.x += sb[u] * gv[u].x * (float)zv[u][0];
                 acc.y += sb[u] * gv[u].y * (float)zv[u][1];
                 acc.z += sb[u] * gv[u].z * (float)zv[u][2];
@@ -632,18 +654,19 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
 
 // dz = s[b] * g without a layer scale: no column reduction to carry, a flat streaming pass
 // (blockIdx.y = batch element, so no per-element division for s[b]).
+template <typename T>
 __global__ __launch_bounds__(256) void scale_only_bwd_kernel(const float *__restrict__ g, const float *__restrict__ s,
-                                                             int64_t vec_per_batch, __bf16 *__restrict__ dz) {
+                                                             int64_t vec_per_batch, T *__restrict__ dz) {
     const float sb = s ? s[blockIdx.y] : 1.f;
     const int64_t base = (int64_t)blockIdx.y * vec_per_batch;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < vec_per_batch; i += (int64_t)gridDim.x * 256) {
         const float4 v = *reinterpret_cast<const float4 *>(g + 4 * (base + i));
-        bf16x4 o;
-        o[0] = (__bf16)(sb * v.x);
-        o[1] = (__bf16)(sb * v.y);
-        o[2] = (__bf16)(sb * v.z);
-        o[3] = (__bf16)(sb * v.w);
-        *reinterpret_cast<bf16x4 *>(dz + 4 * (base + i)) = o;
+        vec4<T> o;
+        o[0] = (T)(sb * v.x);
+        o[1] = (T)(sb * v.y);
+        o[2] = (T)(sb * v.z);
+        o[3] = (T)(sb * v.w);
+        *reinterpret_cast<vec4<T> *>(dz + 4 * (base + i)) = o;
     }
 }
 
@@ -662,11 +685,11 @@ __device__ __forceinline__ int map_of(const Maps &mp, int tok) { return tok >= m
 // Thread = (token slot, channel group of 4): the 36 filter taps of its channels stay in registers
 // while it walks tokens with a grid stride (a per-output reload of the taps made the kernel
 // 8x slower than its memory traffic allows).
-template <int MODE>
-__global__ __launch_bounds__(256) void dwconv_kernel(const __bf16 *__restrict__ x,
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void dwconv_kernel(const T *__restrict__ x,
                                                      const float *__restrict__ w,
                                                      const float *__restrict__ bias, Maps mp, int N,
-                                                     int C, int64_t total_tok, __bf16 *__restrict__ y) {
+                                                     int C, int64_t total_tok, T *__restrict__ y) {
     const int nvec = C >> 2;
     const int slots = 256 / nvec;
     const int slot = threadIdx.x / nvec, cv = threadIdx.x - slot * nvec;
@@ -687,14 +710,14 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const __bf16 *__restrict__ 
         float4 acc = b4;
         // all 9 neighbour rows are requested before the first is used (clamped coordinates, zero weight
         // outside the map): loads under `if (inside)` each got their own s_waitcnt vmcnt(0)
-        bf16x4 v[9];
+        vec4<T> v[9];
         bool in[9];
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
             in[tap] = yy >= 0 && yy < H && xx >= 0 && xx < W;
             const int yc = min(max(yy, 0), H - 1), xc = min(max(xx, 0), W - 1);
-            v[tap] = *reinterpret_cast<const bf16x4 *>(x + ((b * N + t0 + (int64_t)yc * W + xc) * C + 4 * cv));
+            v[tap] = *reinterpret_cast<const vec4<T> *>(x + ((b * N + t0 + (int64_t)yc * W + xc) * C + 4 * cv));
         }
         __builtin_amdgcn_sched_barrier(0);                  // keep the 9 loads above their uses (the scheduler sank them)
 #pragma unroll
@@ -704,20 +727,21 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const __bf16 *__restrict__ 
             acc.z += (in[tap] ? wt[2][tap] : 0.f) * (float)v[tap][2];
             acc.w += (in[tap] ? wt[3][tap] : 0.f) * (float)v[tap][3];
         }
-        bf16x4 o;
-        o[0] = (__bf16)acc.x;
-        o[1] = (__bf16)acc.y;
-        o[2] = (__bf16)acc.z;
-        o[3] = (__bf16)acc.w;
-        *reinterpret_cast<bf16x4 *>(y + tokg * C + 4 * cv) = o;
+        vec4<T> o;
+        o[0] = (T)acc.x;
+        o[1] = (T)acc.y;
+        o[2] = (T)acc.z;
+        o[3] = (T)acc.w;
+        *reinterpret_cast<vec4<T> *>(y + tokg * C + 4 * cv) = o;
     }
 }
 
 // dw[c][tap] = sum_tok g[tok,c] * x[neighbour(tok,tap), c];  db[c] = sum g.  Thread = (token slot,
 // channel group): walks tokens with a grid stride, 40 partial sums in registers; the slots of a
 // workgroup are summed through LDS into one partial row [dw (C*9) | db (C)].
-__global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const __bf16 *__restrict__ x,
-                                                           const __bf16 *__restrict__ g, Maps mp, int N,
+template <typename T>
+__global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const T *__restrict__ x,
+                                                           const T *__restrict__ g, Maps mp, int N,
                                                            int C, int64_t total_tok,
                                                            float *__restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float s_red[];      // [slots][C*10]
@@ -737,18 +761,18 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const __bf16 *__restr
             const int m = map_of(mp, tok);
             const int H = mp.h[m], W = mp.w[m], t0 = mp.t[m];
             const int py = (tok - t0) / W, px = (tok - t0) - py * W;
-            const bf16x4 gv = *reinterpret_cast<const bf16x4 *>(g + tokg * C + 4 * cv);
+            const vec4<T> gv = *reinterpret_cast<const vec4<T> *>(g + tokg * C + 4 * cv);
             const float gf[4] = {(float)gv[0], (float)gv[1], (float)gv[2], (float)gv[3]};
 #pragma unroll
             for (int c = 0; c < 4; ++c) ab[c] += gf[c];
-            bf16x4 v[9];                                        // all 9 neighbour rows in flight at once
+            vec4<T> v[9];                                        // all 9 neighbour rows in flight at once
             bool in[9];
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
                 in[tap] = yy >= 0 && yy < H && xx >= 0 && xx < W;
                 const int yc = min(max(yy, 0), H - 1), xc = min(max(xx, 0), W - 1);
-                v[tap] = *reinterpret_cast<const bf16x4 *>(x + ((b * N + t0 + (int64_t)yc * W + xc) * C + 4 * cv));
+                v[tap] = *reinterpret_cast<const vec4<T> *>(x + ((b * N + t0 + (int64_t)yc * W + xc) * C + 4 * cv));
             }
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap)
@@ -782,53 +806,30 @@ inline unsigned grid_for(int64_t work_items, int per_block) {
     return (unsigned)g;
 }
 
-}  // namespace
-}  // namespace vah
-
-extern "C" {
-
-static int ln_fwd_launch(const char *fn, const float *x, const float *w, const float *b, int64_t rows, int64_t C,
-                         float eps, vah::ResidualIn res, void *y, float *mean, float *rstd, void *stream);
-
-int vah_layernorm_fwd_f32_bf16(const float *x, const float *w, const float *b, int64_t rows,
-                               int64_t C, float eps, void *y, float *mean, float *rstd, void *stream) {
-    return ln_fwd_launch("vah_layernorm_fwd_f32_bf16", x, w, b, rows, C, eps, vah::ResidualIn{nullptr, nullptr, nullptr, 1, nullptr},
-                         y, mean, rstd, stream);
-}
-
-// t = x + sc[b] * gamma * z (written to t, fp32), h = LayerNorm(t) (bf16): vah_scale_residual_fwd and
-// vah_layernorm_fwd_f32_bf16 in one pass over the rows.  gamma, sc optional.
-int vah_residual_layernorm_fwd(const float *x, const void *z, const float *gamma, const float *sc, int64_t batch,
-                               int64_t rows_per_batch, int64_t C, const float *w, const float *b, float eps, float *t,
-                               void *h, float *mean, float *rstd, void *stream) {
-    using namespace vah;
-    const char *fn = "vah_residual_layernorm_fwd";
-    clear_error();
-    if (batch < 0 || rows_per_batch < 0) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (batch * rows_per_batch > 0 && (!z || !t)) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)gamma | (uintptr_t)t) % 16 || (uintptr_t)z % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    return ln_fwd_launch(fn, x, w, b, batch * rows_per_batch, C, eps,
-                         ResidualIn{(const __bf16 *)z, gamma, sc, std::max<int64_t>(rows_per_batch, 1), t}, h, mean, rstd, stream);
-}
-
-static int ln_fwd_launch(const char *fn, const float *x, const float *w, const float *b, int64_t rows, int64_t C,
-                         float eps, vah::ResidualIn res, void *y, float *mean, float *rstd, void *stream) {
-    using namespace vah;
+// ---------------------------------------------------------------------------------------
+// Launch helpers: one copy of the argument checks, launch geometry and workspace layout for both element
+// types.  `fn` is the entry point's own name (messages), T its 16-bit type.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+int ln_fwd_launch(const char *fn, const float *x, const float *w, const float *b, int64_t rows, int64_t C, float eps,
+                  ResidualIn<T> res, void *y, float *mean, float *rstd, void *stream) {
     clear_error();
     if (rows < 0 || C < 4 || C % 4 || C > 64 * 4 * kMaxVecAll) return fail(VAH_E_SHAPE, "%s: C=%lld unsupported", fn, (long long)C);
     if (rows == 0) return VAH_OK;
     if (!x || !w || !b || !y || !mean || !rstd) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)b) % 16 || (uintptr_t)y % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
     hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope(res.z ? "residual_layernorm_fwd" : "layernorm_fwd", rows * C * (res.z ? 12 : 6), st);
+    LaunchScope scope(res.z ? tname<T>("residual_layernorm_fwd", "residual_layernorm_fwd_f16")
+                            : tname<T>("layernorm_fwd", "layernorm_fwd_f16"),
+                      rows * C * (res.z ? 12 : 6), st);
 #define VAH_LN_FWD(NV)                                                                          \
     do {                                                                                        \
         if (res.z)                                                                              \
-            hipLaunchKernelGGL((ln_fwd_kernel<NV, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, w, b, \
-                               rows, (int)C, eps, res, (__bf16 *)y, mean, rstd);                \
+            hipLaunchKernelGGL((ln_fwd_kernel<T, NV, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, w, b, \
+                               rows, (int)C, eps, res, (T *)y, mean, rstd);                     \
         else                                                                                    \
-            hipLaunchKernelGGL((ln_fwd_kernel<NV, false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, w, b, \
-                               rows, (int)C, eps, res, (__bf16 *)y, mean, rstd);                \
+            hipLaunchKernelGGL((ln_fwd_kernel<T, NV, false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, w, b, \
+                               rows, (int)C, eps, res, (T *)y, mean, rstd);                     \
     } while (0)
     if (C <= 256) VAH_LN_FWD(1);
     else if (C <= 512) VAH_LN_FWD(2);
@@ -839,12 +840,25 @@ static int ln_fwd_launch(const char *fn, const float *x, const float *w, const f
     return check_launch(fn);
 }
 
-int64_t vah_reduce_ws_floats(int64_t K) { return (int64_t)vah::kMaxParts * K; }
+// t = x + sc[b] * gamma * z (written to t, fp32), h = LayerNorm(t) (T): the scale-residual forward and the
+// LayerNorm forward in one pass over the rows.  gamma, sc optional.
+template <typename T>
+int residual_ln_fwd(const char *fn, const float *x, const void *z, const float *gamma, const float *sc, int64_t batch,
+                    int64_t rows_per_batch, int64_t C, const float *w, const float *b, float eps, float *t, void *h,
+                    float *mean, float *rstd, void *stream) {
+    clear_error();
+    if (batch < 0 || rows_per_batch < 0) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (batch * rows_per_batch > 0 && (!z || !t)) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)gamma | (uintptr_t)t) % 16 || (uintptr_t)z % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    return ln_fwd_launch<T>(fn, x, w, b, batch * rows_per_batch, C, eps,
+                            ResidualIn<T>{(const T *)z, gamma, sc, std::max<int64_t>(rows_per_batch, 1), t}, h, mean, rstd,
+                            stream);
+}
 
-static int ln_bwd_launch(const char *fn, const float *x, const void *g, const float *w, const float *mean,
-                         const float *rstd, const float *gres, int64_t rows, int64_t C, vah::ResidualIn res, void *dz,
-                         float *dx, float *dw, float *db, float *dgamma, float *ws, void *stream) {
-    using namespace vah;
+template <typename T>
+int ln_bwd_launch(const char *fn, const float *x, const void *g, const float *w, const float *mean, const float *rstd,
+                  const float *gres, int64_t rows, int64_t C, ResidualIn<T> res, void *dz, float *dx, float *dw, float *db,
+                  float *dgamma, float *ws, void *stream) {
     clear_error();
     if (rows < 0 || C < 4 || C % 4 || C > 64 * 4 * kMaxVecAll) return fail(VAH_E_SHAPE, "%s: C=%lld unsupported", fn, (long long)C);
     if (!dw || !db || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
@@ -866,16 +880,18 @@ static int ln_bwd_launch(const char *fn, const float *x, const void *g, const fl
     int64_t nblocks = (rows + waves - 1) / waves;
     nblocks = std::min<int64_t>(nblocks, kMaxParts);          // the scratch holds kMaxParts * ncol * C floats
     const size_t smem = (size_t)waves * ncol * C * sizeof(float) + wbytes;
-    LaunchScope scope(res.z ? "residual_layernorm_bwd" : "layernorm_bwd", rows * C * (res.z ? 18 : 10), st);
+    LaunchScope scope(res.z ? tname<T>("residual_layernorm_bwd", "residual_layernorm_bwd_f16")
+                            : tname<T>("layernorm_bwd", "layernorm_bwd_f16"),
+                      rows * C * (res.z ? 18 : 10), st);
     if (smem > 150 * 1024) return fail(VAH_E_SHAPE, "%s: C too large for the fused form", fn);
-constexpr int kLnFly = VAH_LN_FLY;
+    constexpr int kLnFly = VAH_LN_FLY;
 #define VAH_LN_BWD(NV, WV, RS)                                                                     \
     do {                                                                                         \
         if (smem > 64 * 1024)                                                                    \
-            (void)hipFuncSetAttribute((const void *)ln_bwd_kernel<NV, WV, RS, kLnFly>,                   \
+            (void)hipFuncSetAttribute((const void *)ln_bwd_kernel<T, NV, WV, RS, kLnFly>,                \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);    \
-        hipLaunchKernelGGL((ln_bwd_kernel<NV, WV, RS, kLnFly>), dim3((unsigned)nblocks), dim3(64 * WV), smem, st, x, \
-                           (const __bf16 *)g, w, mean, rstd, gres, rows, (int)C, res, (__bf16 *)dz, dx, ws); \
+        hipLaunchKernelGGL((ln_bwd_kernel<T, NV, WV, RS, kLnFly>), dim3((unsigned)nblocks), dim3(64 * WV), smem, st, x, \
+                           (const T *)g, w, mean, rstd, gres, rows, (int)C, res, (T *)dz, dx, ws); \
     } while (0)
 #define VAH_LN_BWD_W(NV)        \
     do {                        \
@@ -897,50 +913,39 @@ constexpr int kLnFly = VAH_LN_FLY;
     return check_launch(fn);
 }
 
-// ws: vah_reduce_ws_floats(2*C) floats of scratch.  dw, db are overwritten.
-int vah_layernorm_bwd_f32_bf16(const float *x, const void *g, const float *w, const float *mean,
-                               const float *rstd, const float *gres, int64_t rows, int64_t C, float *dx,
-                               float *dw, float *db, float *ws, void *stream) {
-    return ln_bwd_launch("vah_layernorm_bwd_f32_bf16", x, g, w, mean, rstd, gres, rows, C,
-                         vah::ResidualIn{nullptr, nullptr, nullptr, 1, nullptr}, nullptr, dx, dw, db, nullptr, ws, stream);
-}
-
-// Backward of vah_residual_layernorm_fwd: dt = gt + LayerNorm'(gh) (the gradient of x as well),
-// dz = sc * gamma * dt (bf16), dgamma = sum sc * dt * z, dw, db.  gt (gradient of t along the residual
-// stream) and gamma / sc / dgamma optional.  ws: vah_reduce_ws_floats(3*C).
-int vah_residual_layernorm_bwd(const float *t, const void *gh, const float *w, const float *mean, const float *rstd,
-                               const float *gt, const void *z, const float *gamma, const float *sc, int64_t batch,
-                               int64_t rows_per_batch, int64_t C, float *dt, void *dz, float *dgamma, float *dw,
-                               float *db, float *ws, void *stream) {
-    using namespace vah;
-    const char *fn = "vah_residual_layernorm_bwd";
+// Backward of residual_ln_fwd: dt = gt + LayerNorm'(gh) (the gradient of x as well), dz = sc * gamma * dt (T),
+// dgamma = sum sc * dt * z, dw, db.  gt (gradient of t along the residual stream) and gamma / sc / dgamma
+// optional.  ws: vah_reduce_ws_floats(3*C).
+template <typename T>
+int residual_ln_bwd(const char *fn, const float *t, const void *gh, const float *w, const float *mean, const float *rstd,
+                    const float *gt, const void *z, const float *gamma, const float *sc, int64_t batch,
+                    int64_t rows_per_batch, int64_t C, float *dt, void *dz, float *dgamma, float *dw, float *db, float *ws,
+                    void *stream) {
     clear_error();
     if (batch < 0 || rows_per_batch < 0) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (batch * rows_per_batch > 0 && (!z || !dz)) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if ((gamma != nullptr) != (dgamma != nullptr)) return fail(VAH_E_NULL, "%s: gamma and dgamma go together", fn);
     if ((uintptr_t)gamma % 16 || ((uintptr_t)z | (uintptr_t)dz) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    return ln_bwd_launch(fn, t, gh, w, mean, rstd, gt, batch * rows_per_batch, C,
-                         ResidualIn{(const __bf16 *)z, gamma, sc, std::max<int64_t>(rows_per_batch, 1), nullptr}, dz, dt, dw,
-                         db, dgamma, ws, stream);
+    return ln_bwd_launch<T>(fn, t, gh, w, mean, rstd, gt, batch * rows_per_batch, C,
+                            ResidualIn<T>{(const T *)z, gamma, sc, std::max<int64_t>(rows_per_batch, 1), nullptr}, dz, dt, dw,
+                            db, dgamma, ws, stream);
 }
 
-// Two LayerNorms of the same fp32 rows (shared statistics, equal eps): ya, yb bf16.
-int vah_layernorm_dual_fwd(const float *x, const float *wa, const float *ba, const float *wb, const float *bb,
-                           int64_t rows, int64_t C, float eps, void *ya, void *yb, float *mean, float *rstd,
-                           void *stream) {
-    using namespace vah;
+// Two LayerNorms of the same fp32 rows (shared statistics, equal eps): ya, yb of type T.
+template <typename T>
+int ln_dual_fwd(const char *fn, const float *x, const float *wa, const float *ba, const float *wb, const float *bb,
+                int64_t rows, int64_t C, float eps, void *ya, void *yb, float *mean, float *rstd, void *stream) {
     clear_error();
-    const char *fn = "vah_layernorm_dual_fwd";
     if (rows < 0 || C < 4 || C % 4 || C > 64 * 4 * 4) return fail(VAH_E_SHAPE, "%s: C=%lld unsupported", fn, (long long)C);
     if (rows == 0) return VAH_OK;
     if (!x || !wa || !ba || !wb || !bb || !ya || !yb || !mean || !rstd) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (((uintptr_t)x | (uintptr_t)wa | (uintptr_t)ba | (uintptr_t)wb | (uintptr_t)bb) % 16 || ((uintptr_t)ya | (uintptr_t)yb) % 8)
         return fail(VAH_E_ALIGN, "%s: misaligned", fn);
     hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("layernorm_dual_fwd", rows * C * 8, st);
+    LaunchScope scope(tname<T>("layernorm_dual_fwd", "layernorm_dual_fwd_f16"), rows * C * 8, st);
 #define VAH_LND_FWD(NV)                                                                                            \
-    hipLaunchKernelGGL(ln_dual_fwd_kernel<NV>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, wa, ba, wb, bb, rows, \
-                       (int)C, eps, (__bf16 *)ya, (__bf16 *)yb, mean, rstd)
+    hipLaunchKernelGGL((ln_dual_fwd_kernel<T, NV>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, wa, ba, wb, bb, rows, \
+                       (int)C, eps, (T *)ya, (T *)yb, mean, rstd)
     if (C <= 256) VAH_LND_FWD(1);
     else if (C <= 512) VAH_LND_FWD(2);
     else if (C <= 768) VAH_LND_FWD(3);
@@ -951,12 +956,11 @@ int vah_layernorm_dual_fwd(const float *x, const float *wa, const float *ba, con
 
 // Backward of both: dx = gres + LN_a'(ga) + LN_b'(gb) in one pass (ga / gb / gres optional);
 // dparams (4, C) = [dwa | dba | dwb | dbb].  ws: vah_reduce_ws_floats(2 * C).
-int vah_layernorm_dual_bwd(const float *x, const void *ga, const void *gb, const float *wa, const float *wb,
-                           const float *mean, const float *rstd, const float *gres, int64_t rows, int64_t C, float *dx,
-                           float *dparams, float *ws, void *stream) {
-    using namespace vah;
+template <typename T>
+int ln_dual_bwd(const char *fn, const float *x, const void *ga, const void *gb, const float *wa, const float *wb,
+                const float *mean, const float *rstd, const float *gres, int64_t rows, int64_t C, float *dx, float *dparams,
+                float *ws, void *stream) {
     clear_error();
-    const char *fn = "vah_layernorm_dual_bwd";
     if (rows < 0 || C < 4 || C % 4 || C > 64 * 4 * 4) return fail(VAH_E_SHAPE, "%s: C=%lld unsupported", fn, (long long)C);
     if (!dparams || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
     hipStream_t st = (hipStream_t)stream;
@@ -970,10 +974,10 @@ int vah_layernorm_dual_bwd(const float *x, const void *ga, const void *gb, const
     const int64_t nblocks = std::min<int64_t>((rows + 3) / 4, kMaxParts / 2);       // the scratch holds kMaxParts * 2C floats
     const size_t smem = (size_t)4 * 4 * C * sizeof(float);
     if (smem > 64 * 1024) return fail(VAH_E_SHAPE, "%s: C too large", fn);
-    LaunchScope scope("layernorm_dual_bwd", rows * C * 16, st);
+    LaunchScope scope(tname<T>("layernorm_dual_bwd", "layernorm_dual_bwd_f16"), rows * C * 16, st);
 #define VAH_LND_BWD(NV)                                                                                              \
-    hipLaunchKernelGGL(ln_dual_bwd_kernel<NV>, dim3((unsigned)nblocks), dim3(256), smem, st, x, (const __bf16 *)ga,   \
-                       (const __bf16 *)gb, wa, wb, mean, rstd, gres, rows, (int)C, dx, ws)
+    hipLaunchKernelGGL((ln_dual_bwd_kernel<T, NV>), dim3((unsigned)nblocks), dim3(256), smem, st, x, (const T *)ga,   \
+                       (const T *)gb, wa, wb, mean, rstd, gres, rows, (int)C, dx, ws)
     if (C <= 256) VAH_LND_BWD(1);
     else if (C <= 512) VAH_LND_BWD(2);
     else if (C <= 768) VAH_LND_BWD(3);
@@ -984,6 +988,217 @@ int vah_layernorm_dual_bwd(const float *x, const void *ga, const void *gb, const
                        dparams, (int)(4 * C), (float *)nullptr, 1 << 30, (float *)nullptr);
     return check_launch(fn);
 }
+
+template <typename T>
+int scale_residual_fwd(const char *fn, const float *x, const void *z, const float *gamma, const float *s, int64_t batch,
+                       int64_t rows_per_batch, int64_t C, float *y, void *stream) {
+    clear_error();
+    if (batch < 0 || rows_per_batch < 0 || C < 4 || C % 4) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    const int64_t total_vec = batch * rows_per_batch * (C / 4);
+    if (total_vec == 0) return VAH_OK;
+    if (!x || !z || !y) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma) % 16 || (uintptr_t)z % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("scale_residual_fwd", "scale_residual_fwd_f16"), total_vec * 40, st);
+    hipLaunchKernelGGL(scale_residual_fwd_kernel<T>, dim3(grid_for(total_vec, 256 * 4)), dim3(256), 0, st, x,
+                       (const T *)z, gamma, s, rows_per_batch, (int)C, total_vec, y);
+    return check_launch(fn);
+}
+
+// dgamma (may be NULL when gamma is NULL) is overwritten; ws: vah_reduce_ws_floats(C) floats.
+template <typename T>
+int scale_residual_bwd(const char *fn, const float *g, const void *z, const float *gamma, const float *s, int64_t batch,
+                       int64_t rows_per_batch, int64_t C, void *dz, float *dgamma, float *ws, void *stream) {
+    clear_error();
+    if (batch < 0 || rows_per_batch < 0 || C < 4 || C % 4) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    const int64_t rows = batch * rows_per_batch;
+    hipStream_t st = (hipStream_t)stream;
+    if (rows == 0) {
+        if (dgamma) (void)hipMemsetAsync(dgamma, 0, C * 4, st);
+        return VAH_OK;
+    }
+    if (!g || !z || !dz || (dgamma && !ws)) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)g | (uintptr_t)gamma) % 16 || ((uintptr_t)z | (uintptr_t)dz) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    LaunchScope scope(tname<T>("scale_residual_bwd", "scale_residual_bwd_f16"), rows * C * 8, st);
+    if (!gamma && batch <= 65535) {
+        const int64_t vpb = rows_per_batch * C / 4;
+        const unsigned gx = (unsigned)std::min<int64_t>((vpb + 1023) / 1024, 8192);
+        hipLaunchKernelGGL(scale_only_bwd_kernel<T>, dim3(gx, (unsigned)batch), dim3(256), 0, st, g, s, vpb, (T *)dz);
+        return check_launch(fn);
+    }
+    const int rpb = (int)((rows + kMaxParts - 1) / kMaxParts);
+    const int64_t nblocks = (rows + rpb - 1) / rpb;
+    hipLaunchKernelGGL(scale_residual_bwd_kernel<T>, dim3((unsigned)nblocks), dim3(256), 0, st, g,
+                       (const T *)z, gamma, s, rows, rows_per_batch, (int)C, rpb, (T *)dz,
+                       dgamma ? ws : nullptr);
+    if (dgamma)
+        hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, ws,
+                           (int)nblocks, (int)C, dgamma, (int)C, (float *)nullptr, 1 << 30, (float *)nullptr);
+    return check_launch(fn);
+}
+
+// token ranges and sizes of the (2H,2W), (H,W), (H/2,W/2) maps of a (B, 21n, C) token tensor
+inline Maps maps_of(int64_t H, int64_t W) {
+    const int64_t n = (H / 2) * (W / 2);
+    Maps mp;
+    mp.t[0] = 0, mp.t[1] = (int)(16 * n), mp.t[2] = (int)(20 * n), mp.t[3] = (int)(21 * n);
+    mp.h[0] = (int)(2 * H), mp.w[0] = (int)(2 * W), mp.h[1] = (int)H, mp.w[1] = (int)W;
+    mp.h[2] = (int)(H / 2), mp.w[2] = (int)(W / 2);
+    return mp;
+}
+
+// x, y: T (B, N, C) with N = 16n + 4n + n tokens of maps (2H,2W), (H,W), (H/2,W/2); w fp32 (C,1,3,3).
+// mode 0: forward (+bias); mode 1: input gradient (x = grad_out, flipped taps, bias ignored).
+template <typename T>
+int dwconv_tokens(const char *fn, const void *x, const float *w, const float *bias, int64_t B, int64_t H, int64_t W,
+                  int64_t C, int mode, void *y, void *stream) {
+    clear_error();
+    if (B < 0 || H < 2 || W < 2 || (H % 2) || (W % 2) || C < 4 || C % 4 || C > 1024) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (B == 0) return VAH_OK;
+    if (!x || !w || !y) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)x | (uintptr_t)y) % 8 || (uintptr_t)bias % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    const Maps mp = maps_of(H, W);
+    const int N = mp.t[3];
+    const int64_t total_tok = B * N;
+    if (total_tok >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "%s: too many tokens", fn);
+    const int slots = 256 / (int)(C / 4);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(mode == 0 ? tname<T>("dwconv_tokens_fwd", "dwconv_tokens_fwd_f16")
+                                : tname<T>("dwconv_tokens_dgrad", "dwconv_tokens_dgrad_f16"),
+                      total_tok * C * 4, st);
+    if (mode == 0)
+        hipLaunchKernelGGL((dwconv_kernel<T, 0>), dim3(grid_for(total_tok, slots * 2)), dim3(256), 0, st,
+                           (const T *)x, w, bias, mp, N, (int)C, total_tok, (T *)y);
+    else
+        hipLaunchKernelGGL((dwconv_kernel<T, 1>), dim3(grid_for(total_tok, slots * 2)), dim3(256), 0, st,
+                           (const T *)x, w, bias, mp, N, (int)C, total_tok, (T *)y);
+    return check_launch(fn);
+}
+
+// dw (C*9) and db (C, may be NULL) are overwritten; ws: vah_reduce_ws_floats(10*C) floats.
+template <typename T>
+int dwconv_tokens_wgrad(const char *fn, const void *x, const void *g, int64_t B, int64_t H, int64_t W, int64_t C, float *dw,
+                        float *db, float *ws, void *stream) {
+    clear_error();
+    if (B < 0 || H < 2 || W < 2 || (H % 2) || (W % 2) || C < 4 || C % 4 || C > 1024) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (!dw || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0) {
+        (void)hipMemsetAsync(dw, 0, C * 9 * 4, st);
+        if (db) (void)hipMemsetAsync(db, 0, C * 4, st);
+        return VAH_OK;
+    }
+    if (!x || !g) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)x | (uintptr_t)g) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    const Maps mp = maps_of(H, W);
+    const int N = mp.t[3];
+    const int64_t total_tok = B * N;
+    const int slots = 256 / (int)(C / 4);
+    int64_t nblocks = (total_tok + slots * 16 - 1) / (slots * 16);
+    if (nblocks > kMaxParts) nblocks = kMaxParts;
+    if (nblocks < 1) nblocks = 1;
+    const size_t smem = (size_t)slots * C * 10 * sizeof(float);
+    if (smem > 150 * 1024) return fail(VAH_E_SHAPE, "%s: C too small for the LDS reduction layout", fn);
+    if (int rc = allow_dynamic_lds((const void *)dwconv_wgrad_kernel<T>, 160 * 1024 - 512, fn)) return rc;
+    LaunchScope scope(tname<T>("dwconv_tokens_wgrad", "dwconv_tokens_wgrad_f16"), total_tok * C * 4, st);
+    hipLaunchKernelGGL(dwconv_wgrad_kernel<T>, dim3((unsigned)nblocks), dim3(256), smem, st,
+                       (const T *)x, (const T *)g, mp, N, (int)C, total_tok, ws);
+    hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((10 * C + 31) / 32)), dim3(256), 0, st, ws,
+                       (int)nblocks, (int)(10 * C), dw, (int)(9 * C), db, 1 << 30, (float *)nullptr);
+    return check_launch(fn);
+}
+
+}  // namespace
+}  // namespace vah
+
+extern "C" {
+
+int64_t vah_reduce_ws_floats(int64_t K) { return (int64_t)vah::kMaxParts * K; }
+
+// Every entry point below exists once per 16-bit element type: the bf16 name and its fp16 twin (`_f16`) are the
+// same template above with another T, so their checks, codes and messages cannot drift apart.
+#define VAH_ENTRY_PAIR(M, BF16_NAME, F16_NAME) M(BF16_NAME, __bf16) M(F16_NAME, _Float16)
+
+#define VAH_LN_FWD_ENTRY(NAME, T)                                                                                       \
+    int NAME(const float *x, const float *w, const float *b, int64_t rows, int64_t C, float eps, void *y, float *mean,  \
+             float *rstd, void *stream) {                                                                               \
+        return vah::ln_fwd_launch<T>(#NAME, x, w, b, rows, C, eps, vah::ResidualIn<T>{nullptr, nullptr, nullptr, 1, nullptr}, \
+                                     y, mean, rstd, stream);                                                            \
+    }
+VAH_ENTRY_PAIR(VAH_LN_FWD_ENTRY, vah_layernorm_fwd_f32_bf16, vah_layernorm_fwd_f32_f16)
+
+// ws: vah_reduce_ws_floats(2*C) floats of scratch.  dw, db are overwritten.
+#define VAH_LN_BWD_ENTRY(NAME, T)                                                                                       \
+    int NAME(const float *x, const void *g, const float *w, const float *mean, const float *rstd, const float *gres,    \
+             int64_t rows, int64_t C, float *dx, float *dw, float *db, float *ws, void *stream) {                       \
+        return vah::ln_bwd_launch<T>(#NAME, x, g, w, mean, rstd, gres, rows, C,                                         \
+                                     vah::ResidualIn<T>{nullptr, nullptr, nullptr, 1, nullptr}, nullptr, dx, dw, db,    \
+                                     nullptr, ws, stream);                                                              \
+    }
+VAH_ENTRY_PAIR(VAH_LN_BWD_ENTRY, vah_layernorm_bwd_f32_bf16, vah_layernorm_bwd_f32_f16)
+
+#define VAH_RES_LN_FWD_ENTRY(NAME, T)                                                                                   \
+    int NAME(const float *x, const void *z, const float *gamma, const float *sc, int64_t batch, int64_t rows_per_batch, \
+             int64_t C, const float *w, const float *b, float eps, float *t, void *h, float *mean, float *rstd,         \
+             void *stream) {                                                                                            \
+        return vah::residual_ln_fwd<T>(#NAME, x, z, gamma, sc, batch, rows_per_batch, C, w, b, eps, t, h, mean, rstd,   \
+                                       stream);                                                                         \
+    }
+VAH_ENTRY_PAIR(VAH_RES_LN_FWD_ENTRY, vah_residual_layernorm_fwd, vah_residual_layernorm_fwd_f16)
+
+#define VAH_RES_LN_BWD_ENTRY(NAME, T)                                                                                   \
+    int NAME(const float *t, const void *gh, const float *w, const float *mean, const float *rstd, const float *gt,     \
+             const void *z, const float *gamma, const float *sc, int64_t batch, int64_t rows_per_batch, int64_t C,      \
+             float *dt, void *dz, float *dgamma, float *dw, float *db, float *ws, void *stream) {                       \
+        return vah::residual_ln_bwd<T>(#NAME, t, gh, w, mean, rstd, gt, z, gamma, sc, batch, rows_per_batch, C, dt, dz, \
+                                       dgamma, dw, db, ws, stream);                                                     \
+    }
+VAH_ENTRY_PAIR(VAH_RES_LN_BWD_ENTRY, vah_residual_layernorm_bwd, vah_residual_layernorm_bwd_f16)
+
+#define VAH_LN_DUAL_FWD_ENTRY(NAME, T)                                                                                  \
+    int NAME(const float *x, const float *wa, const float *ba, const float *wb, const float *bb, int64_t rows,          \
+             int64_t C, float eps, void *ya, void *yb, float *mean, float *rstd, void *stream) {                        \
+        return vah::ln_dual_fwd<T>(#NAME, x, wa, ba, wb, bb, rows, C, eps, ya, yb, mean, rstd, stream);                 \
+    }
+VAH_ENTRY_PAIR(VAH_LN_DUAL_FWD_ENTRY, vah_layernorm_dual_fwd, vah_layernorm_dual_fwd_f16)
+
+#define VAH_LN_DUAL_BWD_ENTRY(NAME, T)                                                                                  \
+    int NAME(const float *x, const void *ga, const void *gb, const float *wa, const float *wb, const float *mean,       \
+             const float *rstd, const float *gres, int64_t rows, int64_t C, float *dx, float *dparams, float *ws,       \
+             void *stream) {                                                                                            \
+        return vah::ln_dual_bwd<T>(#NAME, x, ga, gb, wa, wb, mean, rstd, gres, rows, C, dx, dparams, ws, stream);       \
+    }
+VAH_ENTRY_PAIR(VAH_LN_DUAL_BWD_ENTRY, vah_layernorm_dual_bwd, vah_layernorm_dual_bwd_f16)
+
+#define VAH_SCALE_RES_FWD_ENTRY(NAME, T)                                                                                \
+    int NAME(const float *x, const void *z, const float *gamma, const float *s, int64_t batch, int64_t rows_per_batch,  \
+             int64_t C, float *y, void *stream) {                                                                       \
+        return vah::scale_residual_fwd<T>(#NAME, x, z, gamma, s, batch, rows_per_batch, C, y, stream);                  \
+    }
+VAH_ENTRY_PAIR(VAH_SCALE_RES_FWD_ENTRY, vah_scale_residual_fwd, vah_scale_residual_fwd_f16)
+
+#define VAH_SCALE_RES_BWD_ENTRY(NAME, T)                                                                                \
+    int NAME(const float *g, const void *z, const float *gamma, const float *s, int64_t batch, int64_t rows_per_batch,  \
+             int64_t C, void *dz, float *dgamma, float *ws, void *stream) {                                             \
+        return vah::scale_residual_bwd<T>(#NAME, g, z, gamma, s, batch, rows_per_batch, C, dz, dgamma, ws, stream);     \
+    }
+VAH_ENTRY_PAIR(VAH_SCALE_RES_BWD_ENTRY, vah_scale_residual_bwd, vah_scale_residual_bwd_f16)
+
+#define VAH_DWCONV_ENTRY(NAME, T)                                                                                       \
+    int NAME(const void *x, const float *w, const float *bias, int64_t B, int64_t H, int64_t W, int64_t C, int mode,    \
+             void *y, void *stream) {                                                                                   \
+        return vah::dwconv_tokens<T>(#NAME, x, w, bias, B, H, W, C, mode, y, stream);                                   \
+    }
+VAH_ENTRY_PAIR(VAH_DWCONV_ENTRY, vah_dwconv3x3_tokens_bf16, vah_dwconv3x3_tokens_f16)
+
+#define VAH_DWCONV_WGRAD_ENTRY(NAME, T)                                                                                 \
+    int NAME(const void *x, const void *g, int64_t B, int64_t H, int64_t W, int64_t C, float *dw, float *db, float *ws, \
+             void *stream) {                                                                                            \
+        return vah::dwconv_tokens_wgrad<T>(#NAME, x, g, B, H, W, C, dw, db, ws, stream);                                \
+    }
+VAH_ENTRY_PAIR(VAH_DWCONV_WGRAD_ENTRY, vah_dwconv3x3_tokens_wgrad_bf16, vah_dwconv3x3_tokens_wgrad_f16)
+
+#undef VAH_ENTRY_PAIR
 
 // Partial rows of the column sums of a bf16 [rows, C] matrix, C % 8 == 0: ws (vah_reduce_ws_floats(C)) gets
 // *nparts rows of C floats; whoever sums them (vah_colsum_bf16 below, or the finalize job of
@@ -1055,126 +1270,6 @@ int vah_colsum_f32(const float *g, int64_t batch, int64_t batch_stride, int64_t 
                        (int)C, batch_stride, (int)rpb, ws);
     hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, ws, (int)(parts * batch),
                        (int)C, out, (int)C, (float *)nullptr, 1 << 30, (float *)nullptr);
-    return check_launch(fn);
-}
-
-int vah_scale_residual_fwd(const float *x, const void *z, const float *gamma, const float *s,
-                           int64_t batch, int64_t rows_per_batch, int64_t C, float *y, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_scale_residual_fwd";
-    if (batch < 0 || rows_per_batch < 0 || C < 4 || C % 4) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    const int64_t total_vec = batch * rows_per_batch * (C / 4);
-    if (total_vec == 0) return VAH_OK;
-    if (!x || !z || !y) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma) % 16 || (uintptr_t)z % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("scale_residual_fwd", total_vec * 40, st);
-    hipLaunchKernelGGL(scale_residual_fwd_kernel, dim3(grid_for(total_vec, 256 * 4)), dim3(256), 0, st, x,
-                       (const __bf16 *)z, gamma, s, rows_per_batch, (int)C, total_vec, y);
-    return check_launch(fn);
-}
-
-// dgamma (may be NULL when gamma is NULL) is overwritten; ws: vah_reduce_ws_floats(C) floats.
-int vah_scale_residual_bwd(const float *g, const void *z, const float *gamma, const float *s,
-                           int64_t batch, int64_t rows_per_batch, int64_t C, void *dz, float *dgamma,
-                           float *ws, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_scale_residual_bwd";
-    if (batch < 0 || rows_per_batch < 0 || C < 4 || C % 4) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    const int64_t rows = batch * rows_per_batch;
-    hipStream_t st = (hipStream_t)stream;
-    if (rows == 0) {
-        if (dgamma) (void)hipMemsetAsync(dgamma, 0, C * 4, st);
-        return VAH_OK;
-    }
-    if (!g || !z || !dz || (dgamma && !ws)) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)g | (uintptr_t)gamma) % 16 || ((uintptr_t)z | (uintptr_t)dz) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    LaunchScope scope("scale_residual_bwd", rows * C * 8, st);
-    if (!gamma && batch <= 65535) {
-        const int64_t vpb = rows_per_batch * C / 4;
-        const unsigned gx = (unsigned)std::min<int64_t>((vpb + 1023) / 1024, 8192);
-        hipLaunchKernelGGL(scale_only_bwd_kernel, dim3(gx, (unsigned)batch), dim3(256), 0, st, g, s, vpb, (__bf16 *)dz);
-        return check_launch(fn);
-    }
-    const int rpb = (int)((rows + kMaxParts - 1) / kMaxParts);
-    const int64_t nblocks = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(scale_residual_bwd_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, g,
-                       (const __bf16 *)z, gamma, s, rows, rows_per_batch, (int)C, rpb, (__bf16 *)dz,
-                       dgamma ? ws : nullptr);
-    if (dgamma)
-        hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, ws,
-                           (int)nblocks, (int)C, dgamma, (int)C, (float *)nullptr, 1 << 30, (float *)nullptr);
-    return check_launch(fn);
-}
-
-// x, y: bf16 (B, N, C) with N = 16n + 4n + n tokens of maps (2H,2W), (H,W), (H/2,W/2); w fp32 (C,1,3,3).
-// mode 0: forward (+bias); mode 1: input gradient (x = grad_out, flipped taps, bias ignored).
-int vah_dwconv3x3_tokens_bf16(const void *x, const float *w, const float *bias, int64_t B, int64_t H,
-                              int64_t W, int64_t C, int mode, void *y, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_dwconv3x3_tokens_bf16";
-    if (B < 0 || H < 2 || W < 2 || (H % 2) || (W % 2) || C < 4 || C % 4 || C > 1024) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (B == 0) return VAH_OK;
-    if (!x || !w || !y) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)x | (uintptr_t)y) % 8 || (uintptr_t)bias % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    const int64_t n = (H / 2) * (W / 2);
-    Maps mp;
-    mp.t[0] = 0, mp.t[1] = (int)(16 * n), mp.t[2] = (int)(20 * n), mp.t[3] = (int)(21 * n);
-    mp.h[0] = (int)(2 * H), mp.w[0] = (int)(2 * W), mp.h[1] = (int)H, mp.w[1] = (int)W;
-    mp.h[2] = (int)(H / 2), mp.w[2] = (int)(W / 2);
-    const int N = (int)(21 * n);
-    const int64_t total_tok = B * N;
-    if (total_tok >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "%s: too many tokens", fn);
-    const int slots = 256 / (int)(C / 4);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope(mode == 0 ? "dwconv_tokens_fwd" : "dwconv_tokens_dgrad", total_tok * C * 4, st);
-    if (mode == 0)
-        hipLaunchKernelGGL(dwconv_kernel<0>, dim3(grid_for(total_tok, slots * 2)), dim3(256), 0, st,
-                           (const __bf16 *)x, w, bias, mp, N, (int)C, total_tok, (__bf16 *)y);
-    else
-        hipLaunchKernelGGL(dwconv_kernel<1>, dim3(grid_for(total_tok, slots * 2)), dim3(256), 0, st,
-                           (const __bf16 *)x, w, bias, mp, N, (int)C, total_tok, (__bf16 *)y);
-    return check_launch(fn);
-}
-
-// dw (C*9) and db (C, may be NULL) are overwritten; ws: vah_reduce_ws_floats(10*C) floats.
-int vah_dwconv3x3_tokens_wgrad_bf16(const void *x, const void *g, int64_t B, int64_t H, int64_t W,
-                                    int64_t C, float *dw, float *db, float *ws, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_dwconv3x3_tokens_wgrad_bf16";
-    if (B < 0 || H < 2 || W < 2 || (H % 2) || (W % 2) || C < 4 || C % 4 || C > 1024) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (!dw || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    hipStream_t st = (hipStream_t)stream;
-    if (B == 0) {
-        (void)hipMemsetAsync(dw, 0, C * 9 * 4, st);
-        if (db) (void)hipMemsetAsync(db, 0, C * 4, st);
-        return VAH_OK;
-    }
-    if (!x || !g) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)x | (uintptr_t)g) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    const int64_t n = (H / 2) * (W / 2);
-    Maps mp;
-    mp.t[0] = 0, mp.t[1] = (int)(16 * n), mp.t[2] = (int)(20 * n), mp.t[3] = (int)(21 * n);
-    mp.h[0] = (int)(2 * H), mp.w[0] = (int)(2 * W), mp.h[1] = (int)H, mp.w[1] = (int)W;
-    mp.h[2] = (int)(H / 2), mp.w[2] = (int)(W / 2);
-    const int N = (int)(21 * n);
-    const int64_t total_tok = B * N;
-    const int slots = 256 / (int)(C / 4);
-    int64_t nblocks = (total_tok + slots * 16 - 1) / (slots * 16);
-    if (nblocks > kMaxParts) nblocks = kMaxParts;
-    if (nblocks < 1) nblocks = 1;
-    const size_t smem = (size_t)slots * C * 10 * sizeof(float);
-    if (smem > 150 * 1024) return fail(VAH_E_SHAPE, "%s: C too small for the LDS reduction layout", fn);
-    if (int rc = allow_dynamic_lds((const void *)dwconv_wgrad_kernel, 160 * 1024 - 512, fn)) return rc;
-    LaunchScope scope("dwconv_tokens_wgrad", total_tok * C * 4, st);
-    hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3((unsigned)nblocks), dim3(256), smem, st,
-                       (const __bf16 *)x, (const __bf16 *)g, mp, N, (int)C, total_tok, ws);
-    hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((10 * C + 31) / 32)), dim3(256), 0, st, ws,
-                       (int)nblocks, (int)(10 * C), dw, (int)(9 * C), db, 1 << 30, (float *)nullptr);
     return check_launch(fn);
 }
 

@@ -4,6 +4,12 @@ Each helper computes exactly what the reference's module code computes (cited at
 it takes the fused HIP path when the tensors are what bf16 autocast produces on the GPU (fp32
 residual stream, bf16 branch outputs) and otherwise evaluates the same expression with torch ops
 (fp32 runs, CPU host-logic tests).
+
+The row-streaming operators - LayerNorm (plain, keep, dual), residual, residual + LayerNorm, the token
+DWConv - also take fp16 autocast (the reference's AMP mode): the same kernels instantiated on fp16
+(`*_f16` entry points), fp32 math, fp32 -> fp16 rounded to nearest even with overflow to inf and
+subnormals kept.  Linear, conv1x1, patch embedding, up_from_tokens, the BN tail and the MSDA pair core
+stay bf16-only; under fp16 autocast they are torch's.
 """
 import os
 
@@ -13,7 +19,8 @@ import torch.nn.functional as F
 import _vah
 
 ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln': True, 'dwconv': True, 'linear': True, 'bn_tail': True,
-           'bn_relu': True, 'bias_fold': True, 'keep_feat': True, 'maps': True, 'maps_in': True, 'linear_pair': True, 'maxpool': True, 'conv1x1': True, 'ln_dual': True, 'wgrad_fin': True, 'spm_nhwc': True, 'up_gemm': True, 'patch_gemm': True, 'wgrad_overlap': True, 'drop_pool': True}
+           'bn_relu': True, 'bias_fold': True, 'keep_feat': True, 'maps': True, 'maps_in': True, 'linear_pair': True, 'maxpool': True, 'conv1x1': True, 'ln_dual': True, 'wgrad_fin': True, 'spm_nhwc': True, 'up_gemm': True, 'patch_gemm': True, 'wgrad_overlap': True, 'drop_pool': True,
+           'fp16_rows': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -33,28 +40,49 @@ def _bf16_autocast():
     return torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16
 
 
+def _rows_dtype(dtype):
+    """Is ``dtype`` a 16-bit type the row-streaming kernels are instantiated on?  bf16 always; fp16 unless switched off
+    (VAH_FUSED_DISABLE=fp16_rows: the torch expressions under fp16 autocast, for A/B runs)."""
+    return dtype == torch.bfloat16 or (dtype == torch.float16 and ENABLED['fp16_rows'])
+
+
+def _autocast_16():
+    """The 16-bit type the row-streaming kernels write under the active autocast: torch.bfloat16, torch.float16, or
+    None (no autocast, another autocast type, or fp16 with its switch off)."""
+    if not torch.is_autocast_enabled():
+        return None
+    dtype = torch.get_autocast_dtype('cuda')
+    return dtype if _rows_dtype(dtype) else None
+
+
+def _sym(name, dtype):
+    """The entry point ``name`` (its bf16 spelling) for 16-bit operands of ``dtype``: itself or its `_f16` twin."""
+    return getattr(_vah.lib, name if dtype == torch.bfloat16 else _vah.FUSED_F16_TWINS[name])
+
+
 class _LayerNormBF16(torch.autograd.Function):
-    """LayerNorm of the fp32 residual stream with bf16 output.  With ``keep`` the stream itself is
+    """LayerNorm of the fp32 residual stream with 16-bit output (``dtype``: bf16, or fp16 under fp16
+    autocast).  With ``keep`` the stream itself is
     returned next to the normalised copy, so the gradient of the residual branch and the LayerNorm
     gradient meet in ONE backward call and are summed inside the kernel (otherwise autograd adds
     them with a separate fp32 add per LayerNorm)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps, keep):
+    def forward(ctx, x, weight, bias, eps, keep, dtype=torch.bfloat16):
         C = x.shape[-1]
         xc = x.contiguous()
         x2 = xc.view(-1, C)
         rows = x2.shape[0]
-        y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+        y = torch.empty(x.shape, dtype=dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         w, b = weight.contiguous(), bias.contiguous()
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_layernorm_fwd_f32_bf16(
+            _vah.check(_sym('vah_layernorm_fwd_f32_bf16', dtype)(
                 x2.data_ptr(), w.data_ptr(), b.data_ptr(), rows, C, float(eps), y.data_ptr(),
                 mean.data_ptr(), rstd.data_ptr(), _stream(x)), 'layernorm_fwd')
         ctx.save_for_backward(x2, w, mean, rstd)
-        ctx.shape = x.shape
+        ctx.shape, ctx.dtype = x.shape, dtype
         ctx.set_materialize_grads(False)
         if keep:
             return xc, y
@@ -66,24 +94,24 @@ class _LayerNormBF16(torch.autograd.Function):
         x2, w, mean, rstd = ctx.saved_tensors
         rows, C = x2.shape
         if g is None:                      # the normalised copy was not used
-            return (gres, None, None, None, None)
-        g = g.contiguous().to(torch.bfloat16)
+            return (gres, None, None, None, None, None)
+        g = g.contiguous().to(ctx.dtype)
         if gres is not None:
             gres = gres.contiguous().float()
         dx = torch.empty_like(x2)
         dwb = torch.empty(2, C, dtype=torch.float32, device=x2.device)
         ws = _scratch(2 * C, x2.device)
         with _vah.on(x2.device):
-            _vah.check(_vah.lib.vah_layernorm_bwd_f32_bf16(
+            _vah.check(_sym('vah_layernorm_bwd_f32_bf16', ctx.dtype)(
                 x2.data_ptr(), g.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                 gres.data_ptr() if gres is not None else None, rows, C,
                 dx.data_ptr(), dwb[0].data_ptr(), dwb[1].data_ptr(), ws.data_ptr(), _stream(x2)),
                 'layernorm_bwd')
-        return dx.view(ctx.shape), dwb[0], dwb[1], None, None
+        return dx.view(ctx.shape), dwb[0], dwb[1], None, None, None
 
 
 def _ln_fusable(norm, x):
-    return (ENABLED['layer_norm'] and x.is_cuda and x.dtype == torch.float32 and _bf16_autocast()
+    return (ENABLED['layer_norm'] and x.is_cuda and x.dtype == torch.float32 and _autocast_16() is not None
             and isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine
             and x.shape[-1] % 4 == 0 and x.shape[-1] <= 2048 and x.numel() > 0)
 
@@ -94,22 +122,22 @@ class _LayerNormDualBF16(torch.autograd.Function):
     one pass."""
 
     @staticmethod
-    def forward(ctx, x, wa, ba, wb, bb, eps):
+    def forward(ctx, x, wa, ba, wb, bb, eps, dtype=torch.bfloat16):
         C = x.shape[-1]
         xc = x.contiguous()
         x2 = xc.view(-1, C)
         rows = x2.shape[0]
-        ya = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-        yb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+        ya = torch.empty(x.shape, dtype=dtype, device=x.device)
+        yb = torch.empty(x.shape, dtype=dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         wa, ba, wb, bb = (t.contiguous() for t in (wa, ba, wb, bb))
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_layernorm_dual_fwd(
+            _vah.check(_sym('vah_layernorm_dual_fwd', dtype)(
                 x2.data_ptr(), wa.data_ptr(), ba.data_ptr(), wb.data_ptr(), bb.data_ptr(), rows, C, float(eps),
                 ya.data_ptr(), yb.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(x)), 'layernorm_dual_fwd')
         ctx.save_for_backward(x2, wa, wb, mean, rstd)
-        ctx.shape = x.shape
+        ctx.shape, ctx.dtype = x.shape, dtype
         ctx.set_materialize_grads(False)
         return xc, ya, yb
 
@@ -118,21 +146,21 @@ class _LayerNormDualBF16(torch.autograd.Function):
         x2, wa, wb, mean, rstd = ctx.saved_tensors
         rows, C = x2.shape
         if ga is None and gb is None:
-            return (gres, None, None, None, None, None)
-        ga = ga.contiguous().to(torch.bfloat16) if ga is not None else None
-        gb = gb.contiguous().to(torch.bfloat16) if gb is not None else None
+            return (gres, None, None, None, None, None, None)
+        ga = ga.contiguous().to(ctx.dtype) if ga is not None else None
+        gb = gb.contiguous().to(ctx.dtype) if gb is not None else None
         if gres is not None:
             gres = gres.contiguous().float()
         dx = torch.empty_like(x2)
         dp = torch.empty(4, C, dtype=torch.float32, device=x2.device)
         ws = _scratch(2 * C, x2.device)
         with _vah.on(x2.device):
-            _vah.check(_vah.lib.vah_layernorm_dual_bwd(
+            _vah.check(_sym('vah_layernorm_dual_bwd', ctx.dtype)(
                 x2.data_ptr(), ga.data_ptr() if ga is not None else None, gb.data_ptr() if gb is not None else None,
                 wa.data_ptr(), wb.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                 gres.data_ptr() if gres is not None else None, rows, C, dx.data_ptr(), dp.data_ptr(), ws.data_ptr(),
                 _stream(x2)), 'layernorm_dual_bwd')
-        return dx.view(ctx.shape), dp[0], dp[1], dp[2], dp[3], None
+        return dx.view(ctx.shape), dp[0], dp[1], dp[2], dp[3], None, None
 
 
 def layer_norm_dual_ok(norm_a, norm_b, x):
@@ -143,16 +171,16 @@ def layer_norm_dual_ok(norm_a, norm_b, x):
 def layer_norm_dual_keep(norm_a, norm_b, x):
     """``(x, norm_a(x), norm_b(x))``; use the returned x downstream (see layer_norm_keep)."""
     if layer_norm_dual_ok(norm_a, norm_b, x):
-        return _LayerNormDualBF16.apply(x, norm_a.weight, norm_a.bias, norm_b.weight, norm_b.bias, norm_a.eps)
+        return _LayerNormDualBF16.apply(x, norm_a.weight, norm_a.bias, norm_b.weight, norm_b.bias, norm_a.eps, _autocast_16())
     x, ya = layer_norm_keep(norm_a, x, fan_out=True)
     x, yb = layer_norm_keep(norm_b, x)
     return x, ya, yb
 
 
 def layer_norm(norm, x):
-    """``norm(x)`` for an nn.LayerNorm; bf16 output when the consumer is a bf16 GEMM (autocast)."""
+    """``norm(x)`` for an nn.LayerNorm; output in the autocast type (bf16 / fp16) when the consumer is a 16-bit GEMM."""
     if _ln_fusable(norm, x):
-        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, False)
+        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, False, _autocast_16())
     return norm(x)
 
 
@@ -164,7 +192,7 @@ def layer_norm_keep(norm, x, fan_out=False):
     if fan_out and not ENABLED['keep_feat']:
         return x, layer_norm(norm, x)
     if _ln_fusable(norm, x):
-        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, True)
+        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, True, _autocast_16())
     return x, norm(x)
 
 
@@ -935,7 +963,7 @@ class _ScaleResidual(torch.autograd.Function):
         y = torch.empty_like(x)
         gp = gamma.contiguous() if gamma is not None else None
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_scale_residual_fwd(
+            _vah.check(_sym('vah_scale_residual_fwd', z.dtype)(
                 x.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
                 s.data_ptr() if s is not None else None, B, rpb, C, y.data_ptr(), _stream(x)),
                 'scale_residual_fwd')
@@ -952,7 +980,7 @@ class _ScaleResidual(torch.autograd.Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=g.device) if gp is not None else None
         ws = _scratch(C, g.device) if gp is not None else None
         with _vah.on(g.device):
-            _vah.check(_vah.lib.vah_scale_residual_bwd(
+            _vah.check(_sym('vah_scale_residual_bwd', z.dtype)(
                 g.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
                 s.data_ptr() if s is not None else None, B, rpb, C, dz.data_ptr(),
                 dgamma.data_ptr() if dgamma is not None else None,
@@ -965,7 +993,7 @@ def residual(x, z, gamma=None, drop_path=None):
     reference's Block / Injector / Extractor."""
     prob = float(getattr(drop_path, 'drop_prob', 0.) or 0.)
     training = bool(getattr(drop_path, 'training', False))
-    if (ENABLED['residual'] and x.is_cuda and x.dtype == torch.float32 and z.dtype == torch.bfloat16
+    if (ENABLED['residual'] and x.is_cuda and x.dtype == torch.float32 and _rows_dtype(z.dtype)
             and x.shape == z.shape and x.shape[-1] % 4 == 0 and x.numel() > 0
             and (gamma is None or gamma.dtype == torch.float32)):
         s = None
@@ -986,14 +1014,14 @@ class _ResidualLN(torch.autograd.Function):
         rpb = x.numel() // (B * C)
         x, z = x.contiguous(), z.contiguous()
         t = torch.empty_like(x)
-        h = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+        h = torch.empty(x.shape, dtype=z.dtype, device=x.device)       # the LayerNorm writes z's type (residual_ln checks)
         rows = B * rpb
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         gp = gamma.contiguous() if gamma is not None else None
         w, b = weight.contiguous(), bias.contiguous()
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_residual_layernorm_fwd(
+            _vah.check(_sym('vah_residual_layernorm_fwd', z.dtype)(
                 x.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
                 s.data_ptr() if s is not None else None, B, rpb, C, w.data_ptr(), b.data_ptr(), float(eps),
                 t.data_ptr(), h.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(x)), 'residual_layernorm_fwd')
@@ -1016,19 +1044,19 @@ class _ResidualLN(torch.autograd.Function):
             dgamma = torch.empty(C, dtype=torch.float32, device=dev) if gp is not None else None
             ws = _scratch(C, dev) if gp is not None else None
             with _vah.on(dev):
-                _vah.check(_vah.lib.vah_scale_residual_bwd(
+                _vah.check(_sym('vah_scale_residual_bwd', z.dtype)(
                     gt.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
                     s.data_ptr() if s is not None else None, B, rpb, C, dz.data_ptr(),
                     dgamma.data_ptr() if dgamma is not None else None,
                     ws.data_ptr() if ws is not None else None, _stream(gt)), 'scale_residual_bwd')
             return gt, dz, dgamma, None, None, None, None
-        gh = gh.contiguous().to(torch.bfloat16)
+        gh = gh.contiguous().to(z.dtype)
         dt = torch.empty_like(t)
         dz = torch.empty_like(z)
         grads = torch.empty(3, C, dtype=torch.float32, device=dev)
         ws = _scratch(3 * C, dev)
         with _vah.on(dev):
-            _vah.check(_vah.lib.vah_residual_layernorm_bwd(
+            _vah.check(_sym('vah_residual_layernorm_bwd', z.dtype)(
                 t.data_ptr(), gh.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                 gt.data_ptr() if gt is not None else None, z.data_ptr(),
                 gp.data_ptr() if gp is not None else None, s.data_ptr() if s is not None else None, B, rpb, C,
@@ -1047,10 +1075,17 @@ def _drop_path_scale(x, drop_path):
 def residual_ln(x, z, gamma, drop_path, norm):
     """``t = x + drop_path(gamma * z); return t, norm(t)`` - a residual update followed by the
     LayerNorm of the next sub-block (base/vit.py:301-306), one pass over the rows each way."""
-    if (ENABLED['residual'] and ENABLED['residual_ln'] and _ln_fusable(norm, x) and z.dtype == torch.bfloat16
+    # z in the type the LayerNorm will write: a bf16 z under fp16 autocast (or the reverse) takes the torch expression
+    if (ENABLED['residual'] and ENABLED['residual_ln'] and _ln_fusable(norm, x) and z.dtype == _autocast_16()
             and x.shape == z.shape
             and x.dim() >= 2 and (gamma is None or gamma.dtype == torch.float32) and x.shape[-1] <= 1024):
         return _ResidualLN.apply(x, z, gamma, _drop_path_scale(x, drop_path), norm.weight, norm.bias, norm.eps)
+    ac = _autocast_16()
+    if ENABLED['fp16_rows'] and ac is not None and z.dtype != ac and z.dtype in (torch.bfloat16, torch.float16):
+        # a branch output in the other 16-bit type than the one autocast is running: the torch expression, nothing fused
+        t = gamma * z if gamma is not None else z
+        t = x + (drop_path(t) if drop_path is not None else t)
+        return t, norm(t)
     return layer_norm_keep(norm, residual(x, z, gamma, drop_path))
 
 
@@ -1063,7 +1098,7 @@ class _DWConvTokens(torch.autograd.Function):
         b = bias.detach().float().contiguous() if bias is not None else None
         y = torch.empty_like(x)
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_dwconv3x3_tokens_bf16(
+            _vah.check(_sym('vah_dwconv3x3_tokens_bf16', x.dtype)(
                 x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, B, H, W, C, 0,
                 y.data_ptr(), _stream(x)), 'dwconv_fwd')
         ctx.save_for_backward(x, w)
@@ -1074,14 +1109,14 @@ class _DWConvTokens(torch.autograd.Function):
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         B, H, W, C, has_bias, wdtype = ctx.dims
-        g = g.contiguous().to(torch.bfloat16)
+        g = g.contiguous().to(x.dtype)
         dx = torch.empty_like(x)
         dw = torch.empty(C * 9 + C, dtype=torch.float32, device=x.device)
         ws = _scratch(10 * C, x.device)
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_dwconv3x3_tokens_bf16(
+            _vah.check(_sym('vah_dwconv3x3_tokens_bf16', x.dtype)(
                 g.data_ptr(), w.data_ptr(), None, B, H, W, C, 1, dx.data_ptr(), _stream(x)), 'dwconv_dgrad')
-            _vah.check(_vah.lib.vah_dwconv3x3_tokens_wgrad_bf16(
+            _vah.check(_sym('vah_dwconv3x3_tokens_wgrad_bf16', x.dtype)(
                 x.data_ptr(), g.data_ptr(), B, H, W, C, dw.data_ptr(),
                 dw[C * 9:].data_ptr() if has_bias else None, ws.data_ptr(), _stream(x)), 'dwconv_wgrad')
         return (dx, dw[:C * 9].view(C, 1, 3, 3).to(wdtype),
@@ -1091,7 +1126,7 @@ class _DWConvTokens(torch.autograd.Function):
 def dwconv_tokens(conv, x, H, W):
     """ConvFFN's DWConv on the concatenated token maps; None when the fused path does not apply."""
     B, N, C = x.shape
-    if (ENABLED['dwconv'] and x.is_cuda and x.dtype == torch.bfloat16 and C % 4 == 0 and C <= 1024
+    if (ENABLED['dwconv'] and x.is_cuda and _rows_dtype(x.dtype) and C % 4 == 0 and C <= 1024
             and H % 2 == 0 and W % 2 == 0 and N == 21 * (H // 2) * (W // 2) and x.numel() > 0
             and conv.weight.shape == (C, 1, 3, 3)):
         return _DWConvTokens.apply(x, conv.weight, conv.bias, H, W)
