@@ -477,6 +477,35 @@ int vah_maxpool3s2_nhwc_fwd_bf16(const void *x, int64_t N, int64_t H, int64_t W,
 int vah_maxpool3s2_nhwc_bwd_bf16(const void *gy, const void *idx, int64_t N, int64_t H, int64_t W, int64_t C, void *gx,
                                  void *stream);
 
+/* ---- fp16 twins of the SpatialPriorModule kernels (csrc/conv.hip, csrc/spm_nhwc.hip): fp16 autocast ------------
+ * The same kernels instantiated on _Float16 (the convolutions on v_mfma_f32_32x32x16_f16), same signatures, argument
+ * checks, error codes, launch geometry, LDS sizes and workspaces as the entry points above (each pair goes through
+ * one launch template); the 16-bit operands and outputs are fp16, every sum, the statistics and dw are fp32.  fp32 ->
+ * fp16 rounds to nearest even, overflows to inf (never 65504) and keeps subnormals, so loss-scaled gradients in
+ * fp16's subnormal range survive and an overflow reaches GradScaler as inf.  vah_conv3x3_wgrad_ws_floats,
+ * vah_bn_nhwc_ws_floats and vah_bn_finalize_stats are shared.  Profiler rows: "conv_taps_f16", "conv_dgrad_f16",
+ * "conv_wgrad_f16", and the spm_* names with an _f16 suffix ("spm_bn_stats_f16", "spm_maxpool_fwd_f16", ...), same
+ * byte accounting. */
+int vah_conv_taps_nhwc_f16(const void *in, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *w, int64_t Cout,
+                           int T, const int *ty, const int *tx, int S, void *out, int64_t ny, int64_t nx, int64_t OH,
+                           int64_t OW, int OS, int oy0, int ox0, void *stream);
+int vah_conv3x3_dgrad_nhwc_f16(const void *gy, int64_t N, int64_t OH, int64_t OW, int64_t Cout, const void *wt, int64_t Cin,
+                               int S, void *gx, int64_t H, int64_t W, void *stream);
+int vah_conv3x3_wgrad_nhwc_f16(const void *x, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *dy, int64_t OH,
+                               int64_t OW, int64_t Cout, int S, float *ws, int64_t ws_floats, float *dw, void *stream);
+int vah_image_to_nhwc16_f16(const float *x, int64_t N, int64_t H, int64_t W, void *y, void *stream);
+int vah_bn_nhwc_stats_f16(const void *x, int64_t rows, int64_t C, float *sums, float *ws, void *stream);
+int vah_bn_nhwc_apply_f16(const void *x, int64_t rows, int64_t C, const float *mean, const float *rstd, const float *w,
+                          const float *b, int relu, void *y, void *stream);
+int vah_bn_nhwc_bwd_stats_f16(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
+                              const float *w, const float *b, int relu, float *sums, float *ws, void *stream);
+int vah_bn_nhwc_bwd_apply_f16(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
+                              const float *w, const float *b, int relu, const float *mean_g, const float *mean_gx, void *dx,
+                              void *stream);
+int vah_maxpool3s2_nhwc_fwd_f16(const void *x, int64_t N, int64_t H, int64_t W, int64_t C, void *y, void *idx, void *stream);
+int vah_maxpool3s2_nhwc_bwd_f16(const void *gy, const void *idx, int64_t N, int64_t H, int64_t W, int64_t C, void *gx,
+                                void *stream);
+
 /* ---- bf16 GEMMs of the Linear layers (csrc/gemm.hip) ----------------------------------------
  * D (M x N, row-major, leading dimension ldd; bf16, or fp32 when d_is_f32) = op(A) op(B), bf16
  * operands, fp32 accumulation.  trans_a: A is stored (K x M) row-major and used transposed;

@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """fp16-autocast training step of a ViT-Adapter preset (the reference's AMP mode: GradScaler(init_scale=512)), eager:
 forward + backward + unscale per step, HIP-event timed.  bench.py has no fp16 mode; this is the A/B tool for the fp16
-row kernels:
+row kernels and the fp16 SpatialPriorModule kernels:
 
     python tools/bench_f16_step.py                                   # fused fp16 rows (default)
     VAH_FUSED_DISABLE=fp16_rows python tools/bench_f16_step.py       # torch's expressions: the behaviour before them
+    VAH_FUSED_DISABLE=fp16_spm python tools/bench_f16_step.py        # the SpatialPriorModule as torch's NCHW module
 
 Prints ms per step (median and mean of the timed steps) and, from one more profiled step, the GPU time of every
-profiler row of the row-kernel families (none with the switch off: torch's kernels are not timed by this library).
+profiler row of the row-kernel, conv_ and spm_ families (none with the switches off: torch's kernels are not timed by this library).
 """
 import argparse
 import json
@@ -19,7 +20,7 @@ for p in (ROOT, os.path.join(ROOT, 'vit-adapter_amd')):
     sys.path.insert(0, p)
 import torch  # noqa: E402
 
-FAMILIES = 'layernorm,residual_layernorm,scale_residual,dwconv_tokens'
+FAMILIES = 'layernorm,residual_layernorm,scale_residual,dwconv_tokens,conv_,spm_'
 
 
 def main():
@@ -63,7 +64,7 @@ def main():
     _vah.prof_enable(False)
     rows = {k: round(r['total_ms'], 4) for k, r in sorted(_vah.prof_report().items())}
     finite = all(bool(torch.isfinite(p.grad).all()) for p in model.parameters() if p.grad is not None)
-    print(json.dumps({'preset': args.preset, 'size': args.size, 'batch': args.batch, 'fp16_rows': fused.ENABLED['fp16_rows'],
+    print(json.dumps({'preset': args.preset, 'size': args.size, 'batch': args.batch, 'fp16_rows': fused.ENABLED['fp16_rows'], 'fp16_spm': fused.ENABLED['fp16_spm'],
                       'ms_per_step_median': round(ms[len(ms) // 2], 3), 'ms_per_step_mean': round(sum(ms) / len(ms), 3),
                       'ms_min': round(ms[0], 3), 'ms_max': round(ms[-1], 3), 'steps': args.steps, 'grads_finite': finite,
                       'row_ms_one_step': rows, 'row_ms_total': round(sum(rows.values()), 3)}))

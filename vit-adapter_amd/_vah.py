@@ -169,6 +169,18 @@ FUSED_F16_TWINS = {
 for _b16, _f16 in FUSED_F16_TWINS.items():
     getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
 
+# fp16 twins of the SpatialPriorModule kernels (csrc/conv.hip, csrc/spm_nhwc.hip); the workspace queries and
+# vah_bn_finalize_stats are shared
+SPM_F16_TWINS = {
+    'vah_conv_taps_nhwc_bf16': 'vah_conv_taps_nhwc_f16', 'vah_conv3x3_dgrad_nhwc_bf16': 'vah_conv3x3_dgrad_nhwc_f16',
+    'vah_conv3x3_wgrad_nhwc_bf16': 'vah_conv3x3_wgrad_nhwc_f16', 'vah_image_to_nhwc16_bf16': 'vah_image_to_nhwc16_f16',
+    'vah_bn_nhwc_stats': 'vah_bn_nhwc_stats_f16', 'vah_bn_nhwc_apply': 'vah_bn_nhwc_apply_f16',
+    'vah_bn_nhwc_bwd_stats': 'vah_bn_nhwc_bwd_stats_f16', 'vah_bn_nhwc_bwd_apply': 'vah_bn_nhwc_bwd_apply_f16',
+    'vah_maxpool3s2_nhwc_fwd_bf16': 'vah_maxpool3s2_nhwc_fwd_f16', 'vah_maxpool3s2_nhwc_bwd_bf16': 'vah_maxpool3s2_nhwc_bwd_f16',
+}
+for _b16, _f16 in SPM_F16_TWINS.items():
+    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))
@@ -198,6 +210,9 @@ EXPORTS = (
     'vah_image_to_nhwc16_bf16', 'vah_bn_nhwc_ws_floats', 'vah_bn_nhwc_stats', 'vah_bn_nhwc_apply', 'vah_bn_nhwc_bwd_stats',
     'vah_bn_nhwc_bwd_apply', 'vah_maxpool3s2_nhwc_fwd_bf16', 'vah_maxpool3s2_nhwc_bwd_bf16',
     'vah_conv_taps_nhwc_bf16', 'vah_conv3x3_dgrad_nhwc_bf16', 'vah_conv3x3_wgrad_ws_floats', 'vah_conv3x3_wgrad_nhwc_bf16',
+    'vah_conv_taps_nhwc_f16', 'vah_conv3x3_dgrad_nhwc_f16', 'vah_conv3x3_wgrad_nhwc_f16', 'vah_image_to_nhwc16_f16',
+    'vah_bn_nhwc_stats_f16', 'vah_bn_nhwc_apply_f16', 'vah_bn_nhwc_bwd_stats_f16', 'vah_bn_nhwc_bwd_apply_f16',
+    'vah_maxpool3s2_nhwc_fwd_f16', 'vah_maxpool3s2_nhwc_bwd_f16',
 )
 
 

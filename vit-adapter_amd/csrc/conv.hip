@@ -1,4 +1,10 @@
-// 3x3 convolutions of the spatial prior module as implicit GEMMs on the matrix cores, NHWC bf16, fp32 accumulate.
+// 3x3 convolutions of the spatial prior module as implicit GEMMs on the matrix cores, NHWC bf16 or fp16, fp32 accumulate.
+//
+// The kernels are templates on the 16-bit element type T of the activations, weights and output gradients: __bf16 (bf16
+// autocast) or _Float16 (fp16 autocast, the `_f16` entry points).  v_mfma_f32_32x32x16_bf16 and _f16 share operand layout
+// and cycles and ds_read_b64_tr_b16 reads either type: only the typedefs, mfma() and the fp32 -> T conversion of the
+// stores differ ((T)f: round to nearest even; fp16 overflows to inf and keeps subnormals).  Accumulators, the wgrad
+// partials and dW are fp32 for both.
 //
 // Reference: the conv -> SyncBatchNorm -> ReLU stack of SpatialPriorModule
 // (/root/reference/detection/mmdet_custom/models/backbones/adapter_modules.py:217-260): 3 -> 64 (stride 2), 64 -> 64,
@@ -29,11 +35,12 @@
 namespace vah {
 namespace {
 
-using attn::bf16x4;
-using attn::bf16x8;
 using attn::crow;
 using attn::f32x16;
 using attn::mfma;
+using attn::tname;
+using attn::vec4;
+using attn::vec8;
 using attn::zero16;
 
 constexpr int kMaxTaps = 9;
@@ -61,17 +68,17 @@ __host__ __device__ constexpr int w_stride(int CK, int T) { return T * CK * 2 + 
 
 // CK channels per chunk, WY x WC waves (pixel rows x 32-channel output blocks), MAXP staged pieces per thread,
 // TMAX = unrolled tap slots
-template <int CK, int WY, int WC, int MAXP, int TMAX>
-__global__ __launch_bounds__(64 * WY * WC) void conv_taps_kernel(const __bf16 *__restrict__ in, const __bf16 *__restrict__ w,
-                                                                 __bf16 *__restrict__ out, TapGeom g) {
+template <typename T, int CK, int WY, int WC, int MAXP, int TMAX>
+__global__ __launch_bounds__(64 * WY * WC) void conv_taps_kernel(const T *__restrict__ in, const T *__restrict__ w,
+                                                                 T *__restrict__ out, TapGeom g) {
     constexpr int NT = 64 * WY * WC;
     constexpr int NCB = 2 / WC;          // 32-channel blocks per wave
     constexpr int PXS = px_stride(CK);
     constexpr int C8 = CK / 8;           // 16-byte pieces per pixel
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const TapGroup &gr = g.grp[blockIdx.z];
-    const int T = gr.T;
-    const int WROW = w_stride(CK, T);
+    const int NTAP = gr.T;
+    const int WROW = w_stride(CK, NTAP);
     unsigned char *s_w = smem, *s_x = smem + kCoutTile * WROW;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = lane & 31, hf = lane >> 5;
@@ -92,39 +99,39 @@ __global__ __launch_bounds__(64 * WY * WC) void conv_taps_kernel(const __bf16 *_
         p_goff[i] = (hy * g.IW + hx) * g.Cin + c8 * 8;
     }
     auto stage_w = [&](int chunk) {
-        const int per_row = T * C8;                   // 16-byte pieces per output channel
+        const int per_row = NTAP * C8;                   // 16-byte pieces per output channel
         for (int p = threadIdx.x; p < kCoutTile * per_row; p += NT) {
             const int co = p / per_row, q = p - co * per_row;
             const int t = q / C8, c8 = q - t * C8;
-            const bf16x8 x = *reinterpret_cast<const bf16x8 *>(w + ((int64_t)(co0 + co) * g.WT + gr.wi[t]) * g.Cin + chunk * CK + c8 * 8);
-            *reinterpret_cast<bf16x8 *>(s_w + co * WROW + (t * CK + c8 * 8) * 2) = x;
+            const vec8<T> x = *reinterpret_cast<const vec8<T> *>(w + ((int64_t)(co0 + co) * g.WT + gr.wi[t]) * g.Cin + chunk * CK + c8 * 8);
+            *reinterpret_cast<vec8<T> *>(s_w + co * WROW + (t * CK + c8 * 8) * 2) = x;
         }
     };
-    bf16x8 xp[MAXP];
+    vec8<T> xp[MAXP];
     auto fetch = [&](int tile, int chunk) {
         const int n = tile / (gr.tiles_y * gr.tiles_x), tr = tile - n * gr.tiles_y * gr.tiles_x;
         const int tyi = tr / gr.tiles_x, txi = tr - tyi * gr.tiles_x;
         const int iy0 = tyi * WY * g.S + gr.tymin, ix0 = txi * kTX * g.S + gr.txmin;
-        const __bf16 *base = in + (((int64_t)n * g.IH + iy0) * g.IW + ix0) * g.Cin + chunk * CK;
+        const T *base = in + (((int64_t)n * g.IH + iy0) * g.IW + ix0) * g.Cin + chunk * CK;
 #pragma unroll
         for (int i = 0; i < MAXP; ++i) {
             const int iy = iy0 + (p_yx[i] >> 16), ix = ix0 + (p_yx[i] & 0xffff);
             const bool ok = p_lds[i] >= 0 && iy >= 0 && iy < g.IH && ix >= 0 && ix < g.IW;
-            const bf16x8 x = *reinterpret_cast<const bf16x8 *>(ok ? base + p_goff[i] : in);
+            const vec8<T> x = *reinterpret_cast<const vec8<T> *>(ok ? base + p_goff[i] : in);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) xp[i][j] = ok ? x[j] : (__bf16)0.f;
+            for (int j = 0; j < 8; ++j) xp[i][j] = ok ? x[j] : (T)0.f;
         }
     };
     auto commit = [&]() {
 #pragma unroll
         for (int i = 0; i < MAXP; ++i)
-            if (p_lds[i] >= 0) *reinterpret_cast<bf16x8 *>(s_x + p_lds[i]) = xp[i];
+            if (p_lds[i] >= 0) *reinterpret_cast<vec8<T> *>(s_x + p_lds[i]) = xp[i];
     };
     // per-tap LDS offsets of this lane's pixel (B operand) - the weights' are compile-time multiples of CK
     int xoff[TMAX];
 #pragma unroll
     for (int t = 0; t < TMAX; ++t)
-        xoff[t] = t < T ? ((wy * g.S + gr.ty[t] - gr.tymin) * gr.HX + r * g.S + gr.tx[t] - gr.txmin) * PXS + hf * 16 : 0;
+        xoff[t] = t < NTAP ? ((wy * g.S + gr.ty[t] - gr.tymin) * gr.HX + r * g.S + gr.tx[t] - gr.txmin) * PXS + hf * 16 : 0;
     const unsigned char *wb = s_w + (wc * NCB * 32 + r) * WROW + hf * 16;
 
     if (nchunks == 1) stage_w(0);
@@ -144,13 +151,13 @@ __global__ __launch_bounds__(64 * WY * WC) void conv_taps_kernel(const __bf16 *_
             else if (tile + (int)gridDim.x < gr.ntiles) fetch(tile + gridDim.x, 0);
 #pragma unroll
             for (int t = 0; t < TMAX; ++t) {
-                if (t < T) {
+                if (t < NTAP) {
 #pragma unroll
                     for (int ks = 0; ks < CK / 16; ++ks) {
-                        const bf16x8 b = *reinterpret_cast<const bf16x8 *>(s_x + xoff[t] + ks * 32);
+                        const vec8<T> b = *reinterpret_cast<const vec8<T> *>(s_x + xoff[t] + ks * 32);
 #pragma unroll
                         for (int cb = 0; cb < NCB; ++cb)
-                            acc[cb] = mfma(*reinterpret_cast<const bf16x8 *>(wb + cb * 32 * WROW + (t * CK + ks * 16) * 2), b, acc[cb]);
+                            acc[cb] = mfma(*reinterpret_cast<const vec8<T> *>(wb + cb * 32 * WROW + (t * CK + ks * 16) * 2), b, acc[cb]);
                     }
                 }
             }
@@ -159,21 +166,21 @@ __global__ __launch_bounds__(64 * WY * WC) void conv_taps_kernel(const __bf16 *_
         const int tyi = tr / gr.tiles_x, txi = tr - tyi * gr.tiles_x;
         const int oy = tyi * WY + wy, ox = txi * kTX + r;
         if (oy < gr.ny && ox < gr.nx) {
-            __bf16 *op = out + (((int64_t)n * g.OH + oy * g.OS + gr.oy0) * g.OW + ox * g.OS + gr.ox0) * g.Cout + co0 + wc * NCB * 32;
+            T *op = out + (((int64_t)n * g.OH + oy * g.OS + gr.oy0) * g.OW + ox * g.OS + gr.ox0) * g.Cout + co0 + wc * NCB * 32;
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    bf16x4 v;
+                    vec4<T> v;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = (__bf16)acc[cb][4 * q + j];
-                    *reinterpret_cast<bf16x4 *>(op + cb * 32 + 8 * q + 4 * hf) = v;
+                    for (int j = 0; j < 4; ++j) v[j] = (T)acc[cb][4 * q + j];
+                    *reinterpret_cast<vec4<T> *>(op + cb * 32 + 8 * q + 4 * hf) = v;
                 }
         }
     }
 }
 
-template <int CK, int WY, int WC, int MAXP, int TMAX>
+template <typename T, int CK, int WY, int WC, int MAXP, int TMAX>
 int launch_taps(const void *in, const void *w, void *out, TapGeom &g, hipStream_t st) {
     constexpr int NT = 64 * WY * WC;
     int lds = 0, ntiles = 0;
@@ -191,14 +198,14 @@ int launch_taps(const void *in, const void *w, void *out, TapGeom &g, hipStream_
             return fail(VAH_E_SHAPE, "conv_taps: halo tile %d x %d x %d channels / %d taps does not fit", gr.HY, gr.HX, CK, gr.T);
     }
     if (ntiles == 0) return VAH_OK;
-    if (int rc = allow_dynamic_lds((const void *)conv_taps_kernel<CK, WY, WC, MAXP, TMAX>, lds, "conv_taps")) return rc;
+    if (int rc = allow_dynamic_lds((const void *)conv_taps_kernel<T, CK, WY, WC, MAXP, TMAX>, lds, "conv_taps")) return rc;
     // persistent over pixel tiles: the weights of a one-chunk input are staged once per workgroup
     const int per_cu = lds > 80 * 1024 ? 1 : 2;
     const int others = (g.Cout / kCoutTile) * g.ngroups;
     int slots = (per_cu * kCUs + others - 1) / others;
     slots = slots < 1 ? 1 : (slots > ntiles ? ntiles : slots);
-    hipLaunchKernelGGL((conv_taps_kernel<CK, WY, WC, MAXP, TMAX>), dim3(slots, g.Cout / kCoutTile, g.ngroups), dim3(NT), lds, st,
-                       (const __bf16 *)in, (const __bf16 *)w, (__bf16 *)out, g);
+    hipLaunchKernelGGL((conv_taps_kernel<T, CK, WY, WC, MAXP, TMAX>), dim3(slots, g.Cout / kCoutTile, g.ngroups), dim3(NT), lds, st,
+                       (const T *)in, (const T *)w, (T *)out, g);
     return check_launch("conv_taps");
 }
 
@@ -214,13 +221,14 @@ int finish_group(TapGroup &gr) {
     return 0;
 }
 
+template <typename T>
 int dispatch_taps(const void *in, const void *w, void *out, TapGeom &g, hipStream_t st) {
-    if (g.Cin == 16) return g.S == 1 ? launch_taps<16, 8, 1, 2, 9>(in, w, out, g, st) : launch_taps<16, 2, 2, 3, 9>(in, w, out, g, st);
-    if (g.S == 2) return launch_taps<64, 2, 2, 11, 9>(in, w, out, g, st);
+    if (g.Cin == 16) return g.S == 1 ? launch_taps<T, 16, 8, 1, 2, 9>(in, w, out, g, st) : launch_taps<T, 16, 2, 2, 3, 9>(in, w, out, g, st);
+    if (g.S == 2) return launch_taps<T, 64, 2, 2, 11, 9>(in, w, out, g, st);
     // 8 rows of 32 pixels per workgroup: two waves per SIMD behind one copy of the weights
     int tmax = 0;
     for (int i = 0; i < g.ngroups; ++i) tmax = g.grp[i].T > tmax ? g.grp[i].T : tmax;
-    return tmax > 4 ? launch_taps<64, 8, 1, 6, 9>(in, w, out, g, st) : launch_taps<64, 8, 1, 6, 4>(in, w, out, g, st);
+    return tmax > 4 ? launch_taps<T, 64, 8, 1, 6, 9>(in, w, out, g, st) : launch_taps<T, 64, 8, 1, 6, 4>(in, w, out, g, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -243,14 +251,15 @@ struct WgradGeom {
 
 // transposed fragment: rows row0 + 4 * hf + q (q = 0..3) and 8 rows further, columns col0 + 16 * (grp & 1) + 4 p ..;
 // the lane receives column (lane & 31) of the 8 rows in the k order of a standard fragment pair (4 hf.., 8 + 4 hf..)
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char *p0, const unsigned char *p1) {
+template <typename T>
+__device__ __forceinline__ vec8<T> tr_frag(const unsigned char *p0, const unsigned char *p1) {
     const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p0);
     const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p1);
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
+    return __builtin_bit_cast(vec8<T>, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <int CK, int WY>
-__global__ __launch_bounds__(512) void conv_wgrad_kernel(const __bf16 *__restrict__ x, const __bf16 *__restrict__ dy,
+template <typename T, int CK, int WY>
+__global__ __launch_bounds__(512) void conv_wgrad_kernel(const T *__restrict__ x, const T *__restrict__ dy,
                                                          float *__restrict__ part, WgradGeom g) {
     constexpr int NT = 512, HW = 4;                                  // 8 waves: HW per 32-channel output block
     constexpr int PXS = px_stride(CK), PYS = px_stride(kCoutTile);
@@ -275,29 +284,29 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(const __bf16 *__restric
         p_yx[i] = (hy << 16) | hx;
         p_goff[i] = (hy * g.IW + hx) * g.Cin + c8 * 8;
     }
-    bf16x8 xp[MAXP], yp[DYP];
+    vec8<T> xp[MAXP], yp[DYP];
     auto fetch = [&](int tile) {
         const int n = tile / (g.tiles_y * g.tiles_x), tr = tile - n * g.tiles_y * g.tiles_x;
         const int tyi = tr / g.tiles_x, txi = tr - tyi * g.tiles_x;
         const int oy0 = tyi * WY, ox0 = txi * kTX;
         const int iy0 = oy0 * g.S - 1, ix0 = ox0 * g.S - 1;
-        const __bf16 *xb = x + (((int64_t)n * g.IH + iy0) * g.IW + ix0) * g.Cin + c0;
+        const T *xb = x + (((int64_t)n * g.IH + iy0) * g.IW + ix0) * g.Cin + c0;
 #pragma unroll
         for (int i = 0; i < MAXP; ++i) {
             const int iy = iy0 + (p_yx[i] >> 16), ix = ix0 + (p_yx[i] & 0xffff);
             const bool ok = p_lds[i] >= 0 && iy >= 0 && iy < g.IH && ix >= 0 && ix < g.IW;
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(ok ? xb + p_goff[i] : x);
+            const vec8<T> v = *reinterpret_cast<const vec8<T> *>(ok ? xb + p_goff[i] : x);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) xp[i][j] = ok ? v[j] : (__bf16)0.f;
+            for (int j = 0; j < 8; ++j) xp[i][j] = ok ? v[j] : (T)0.f;
         }
 #pragma unroll
         for (int i = 0; i < DYP; ++i) {
             const int p = threadIdx.x + NT * i, px = p >> 3, c8 = p & 7;
             const int oy = oy0 + px / kTX, ox = ox0 + px % kTX;
             const bool ok = px < NPIX && oy < g.OH && ox < g.OW;
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(ok ? dy + (((int64_t)n * g.OH + oy) * g.OW + ox) * g.Cout + co0 + c8 * 8 : dy);
+            const vec8<T> v = *reinterpret_cast<const vec8<T> *>(ok ? dy + (((int64_t)n * g.OH + oy) * g.OW + ox) * g.Cout + co0 + c8 * 8 : dy);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) yp[i][j] = ok ? v[j] : (__bf16)0.f;
+            for (int j = 0; j < 8; ++j) yp[i][j] = ok ? v[j] : (T)0.f;
         }
     };
     f32x16 acc[PER];
@@ -311,11 +320,11 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(const __bf16 *__restric
         __syncthreads();                                       // previous tile's reads are done
 #pragma unroll
         for (int i = 0; i < MAXP; ++i)
-            if (p_lds[i] >= 0) *reinterpret_cast<bf16x8 *>(s_x + p_lds[i]) = xp[i];
+            if (p_lds[i] >= 0) *reinterpret_cast<vec8<T> *>(s_x + p_lds[i]) = xp[i];
 #pragma unroll
         for (int i = 0; i < DYP; ++i) {
             const int p = threadIdx.x + NT * i;
-            if (p < NPIX * 8) *reinterpret_cast<bf16x8 *>(s_dy + (p >> 3) * PYS + (p & 7) * 16) = yp[i];
+            if (p < NPIX * 8) *reinterpret_cast<vec8<T> *>(s_dy + (p >> 3) * PYS + (p & 7) * 16) = yp[i];
         }
         __syncthreads();
         if (tile + (int)gridDim.x < g.ntiles) fetch(tile + gridDim.x);       // on its way while this tile is multiplied
@@ -325,7 +334,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(const __bf16 *__restric
             const int row = ks / (kTX / 16), col0 = (ks % (kTX / 16)) * 16;
             const int pa = row * kTX + col0 + 4 * hf + (i16 >> 2);                       // dY pixel of this lane's address
             const unsigned char *a0 = s_dy + pa * PYS + (cob * 32 + 16 * (grp & 1) + 4 * (i16 & 3)) * 2;
-            const bf16x8 a = tr_frag(a0, a0 + 8 * PYS);
+            const vec8<T> a = tr_frag<T>(a0, a0 + 8 * PYS);
             const unsigned char *bx = s_x + ((row * g.S) * g.HX + (col0 + 4 * hf + (i16 >> 2)) * g.S) * PXS + (16 * (grp & 1) + 4 * (i16 & 3)) * 2;
 #pragma unroll
             for (int j = 0; j < PER; ++j) {
@@ -334,7 +343,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(const __bf16 *__restric
                     const int t = rem / NCI, cib = rem - t * NCI;
                     const int dyo = t / 3, dxo = t - 3 * dyo;
                     const unsigned char *b0 = bx + (dyo * g.HX + dxo) * PXS + cib * 64;
-                    acc[j] = mfma(a, tr_frag(b0, b0 + 8 * g.S * PXS), acc[j]);
+                    acc[j] = mfma(a, tr_frag<T>(b0, b0 + 8 * g.S * PXS), acc[j]);
                 }
             }
         }
@@ -382,8 +391,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce(const float *__restrict
     if (q == 0 && i < total) dw[i] = (s_sum[0][e] + s_sum[1][e]) + (s_sum[2][e] + s_sum[3][e]);
 }
 
-template <int CK, int WY>
-int launch_wgrad(const void *x, const void *dy, float *ws, int64_t ws_floats, float *dw, WgradGeom &g, hipStream_t st) {
+template <typename T, int CK, int WY>
+int launch_wgrad(const char *fn, const void *x, const void *dy, float *ws, int64_t ws_floats, float *dw, WgradGeom &g, hipStream_t st) {
     g.HY = (WY - 1) * g.S + 3;
     g.HX = (kTX - 1) * g.S + 3;
     g.tiles_y = (g.OH + WY - 1) / WY;
@@ -395,10 +404,10 @@ int launch_wgrad(const void *x, const void *dy, float *ws, int64_t ws_floats, fl
     if (slots > g.ntiles) slots = g.ntiles;
     const int64_t psz = (int64_t)kCoutTile * 9 * CK;
     while (slots > 1 && (int64_t)slots * ncot * ncit * psz > ws_floats) --slots;
-    if ((int64_t)slots * ncot * ncit * psz > ws_floats) return fail(VAH_E_SHAPE, "vah_conv3x3_wgrad_nhwc_bf16: workspace too small");
-    if (int rc = allow_dynamic_lds((const void *)conv_wgrad_kernel<CK, WY>, lds, "conv_wgrad")) return rc;
-    hipLaunchKernelGGL((conv_wgrad_kernel<CK, WY>), dim3(slots, ncot, ncit), dim3(512), lds, st, (const __bf16 *)x,
-                       (const __bf16 *)dy, ws, g);
+    if ((int64_t)slots * ncot * ncit * psz > ws_floats) return fail(VAH_E_SHAPE, "%s: workspace too small", fn);
+    if (int rc = allow_dynamic_lds((const void *)conv_wgrad_kernel<T, CK, WY>, lds, "conv_wgrad")) return rc;
+    hipLaunchKernelGGL((conv_wgrad_kernel<T, CK, WY>), dim3(slots, ncot, ncit), dim3(512), lds, st, (const T *)x,
+                       (const T *)dy, ws, g);
     if (int rc = check_launch("conv_wgrad")) return rc;
     const int64_t total = (int64_t)g.Cout * 9 * g.Cin;
     hipLaunchKernelGGL(conv_wgrad_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, (const float *)ws, slots, ncot,
@@ -406,17 +415,13 @@ int launch_wgrad(const void *x, const void *dy, float *ws, int64_t ws_floats, fl
     return check_launch("conv_wgrad_reduce");
 }
 
-}  // namespace
-}  // namespace vah
-
-extern "C" {
-
-int vah_conv_taps_nhwc_bf16(const void *in, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *w, int64_t Cout,
-                            int T, const int *ty, const int *tx, int S, void *out, int64_t ny, int64_t nx, int64_t OH,
-                            int64_t OW, int OS, int oy0, int ox0, void *stream) {
-    using namespace vah;
+// Entry points: one copy of the argument checks, tap geometry and byte accounting for both element types.  `fn` is
+// the entry point's own name (messages), E its 16-bit type.
+template <typename E>
+int conv_taps_entry(const char *fn, const void *in, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *w, int64_t Cout,
+                    int T, const int *ty, const int *tx, int S, void *out, int64_t ny, int64_t nx, int64_t OH, int64_t OW,
+                    int OS, int oy0, int ox0, void *stream) {
     clear_error();
-    const char *fn = "vah_conv_taps_nhwc_bf16";
     if (T < 1 || T > kMaxTaps || (S != 1 && S != 2) || (OS != 1 && OS != 2) || !ty || !tx)
         return fail(VAH_E_SHAPE, "%s: 1 <= taps <= 9, strides 1 or 2", fn);
     if (N < 0 || IH < 1 || IW < 1 || ny < 0 || nx < 0 || OH < 1 || OW < 1 || (Cin != 16 && Cin % 64) || Cin < 16 || Cout < 64 ||
@@ -436,16 +441,15 @@ int vah_conv_taps_nhwc_bf16(const void *in, int64_t N, int64_t IH, int64_t IW, i
     if (finish_group(gr)) return fail(VAH_E_SHAPE, "%s: tap offsets within +-4", fn);
     hipStream_t st = (hipStream_t)stream;
     // algorithmic bytes: input and output once, weights once; flops: 2 * outputs * taps * Cin
-    LaunchScope scope("conv_taps_bf16", (N * IH * IW * Cin + N * ny * nx * Cout + Cout * T * Cin) * 2, st, 0,
+    LaunchScope scope(tname<E>("conv_taps_bf16", "conv_taps_f16"), (N * IH * IW * Cin + N * ny * nx * Cout + Cout * T * Cin) * 2, st, 0,
                       2 * N * ny * nx * Cout * T * Cin);
-    return dispatch_taps(in, w, out, g, st);
+    return dispatch_taps<E>(in, w, out, g, st);
 }
 
-int vah_conv3x3_dgrad_nhwc_bf16(const void *gy, int64_t N, int64_t OH, int64_t OW, int64_t Cout, const void *wt, int64_t Cin,
-                                int S, void *gx, int64_t H, int64_t W, void *stream) {
-    using namespace vah;
+template <typename E>
+int conv_dgrad_entry(const char *fn, const void *gy, int64_t N, int64_t OH, int64_t OW, int64_t Cout, const void *wt, int64_t Cin,
+                     int S, void *gx, int64_t H, int64_t W, void *stream) {
     clear_error();
-    const char *fn = "vah_conv3x3_dgrad_nhwc_bf16";
     if ((S != 1 && S != 2) || N < 0 || H < 1 || W < 1 || OH != (H - 1) / S + 1 || OW != (W - 1) / S + 1 || Cout % 64 || Cout < 64 ||
         Cin % 64 || Cin < 64 || H > 32767 || W > 32767 || N * H * W * Cin >= (1ll << 31) || N * OH * OW * Cout >= (1ll << 31))
         return fail(VAH_E_SHAPE, "%s: 3x3 / padding 1 / stride 1 or 2 shapes; Cin, Cout multiples of 64", fn);
@@ -482,23 +486,15 @@ int vah_conv3x3_dgrad_nhwc_bf16(const void *gy, int64_t N, int64_t OH, int64_t O
             }
     }
     hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("conv_dgrad_bf16", (N * OH * OW * Cout + N * H * W * Cin + Cout * 9 * Cin) * 2, st, 0,
+    LaunchScope scope(tname<E>("conv_dgrad_bf16", "conv_dgrad_f16"), (N * OH * OW * Cout + N * H * W * Cin + Cout * 9 * Cin) * 2, st, 0,
                       2 * N * OH * OW * Cout * 9 * Cin);
-    return dispatch_taps(gy, wt, gx, g, st);
+    return dispatch_taps<E>(gy, wt, gx, g, st);
 }
 
-int64_t vah_conv3x3_wgrad_ws_floats(int64_t Cin, int64_t Cout) {
-    // one workgroup slot per CU in all, each with a 64 x 9 x CK fp32 partial
-    const int64_t CK = Cin == 16 ? 16 : 64, pairs = (Cout / 64) * (Cin / CK);
-    const int64_t slots = (vah::kCUs + pairs - 1) / pairs;
-    return slots * pairs * 64 * 9 * CK;
-}
-
-int vah_conv3x3_wgrad_nhwc_bf16(const void *x, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *dy, int64_t OH,
-                                int64_t OW, int64_t Cout, int S, float *ws, int64_t ws_floats, float *dw, void *stream) {
-    using namespace vah;
+template <typename E>
+int conv_wgrad_entry(const char *fn, const void *x, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *dy, int64_t OH,
+                     int64_t OW, int64_t Cout, int S, float *ws, int64_t ws_floats, float *dw, void *stream) {
     clear_error();
-    const char *fn = "vah_conv3x3_wgrad_nhwc_bf16";
     if ((S != 1 && S != 2) || N < 0 || IH < 1 || IW < 1 || (Cin != 16 && Cin % 64) || Cin < 16 || Cout < 64 || Cout % 64 ||
         OH != (IH - 1) / S + 1 || OW != (IW - 1) / S + 1 || IH > 32767 || IW > 32767 || N * IH * IW * Cin >= (1ll << 31) ||
         N * OH * OW * Cout >= (1ll << 31))
@@ -510,10 +506,58 @@ int vah_conv3x3_wgrad_nhwc_bf16(const void *x, int64_t N, int64_t IH, int64_t IW
     if (((uintptr_t)x | (uintptr_t)dy) % 16) return fail(VAH_E_ALIGN, "%s: misaligned operand", fn);
     WgradGeom g{};
     g.S = S, g.N = (int)N, g.IH = (int)IH, g.IW = (int)IW, g.Cin = (int)Cin, g.OH = (int)OH, g.OW = (int)OW, g.Cout = (int)Cout;
-    LaunchScope scope("conv_wgrad_bf16", (N * IH * IW * Cin + N * OH * OW * Cout) * 2 + Cout * 9 * Cin * 4, st, 0,
+    LaunchScope scope(tname<E>("conv_wgrad_bf16", "conv_wgrad_f16"), (N * IH * IW * Cin + N * OH * OW * Cout) * 2 + Cout * 9 * Cin * 4, st, 0,
                       2 * N * OH * OW * Cout * 9 * Cin);
-    if (Cin == 16) return S == 1 ? launch_wgrad<16, 4>(x, dy, ws, ws_floats, dw, g, st) : launch_wgrad<16, 2>(x, dy, ws, ws_floats, dw, g, st);
-    return S == 1 ? launch_wgrad<64, 4>(x, dy, ws, ws_floats, dw, g, st) : launch_wgrad<64, 2>(x, dy, ws, ws_floats, dw, g, st);
+    if (Cin == 16) return S == 1 ? launch_wgrad<E, 16, 4>(fn, x, dy, ws, ws_floats, dw, g, st) : launch_wgrad<E, 16, 2>(fn, x, dy, ws, ws_floats, dw, g, st);
+    return S == 1 ? launch_wgrad<E, 64, 4>(fn, x, dy, ws, ws_floats, dw, g, st) : launch_wgrad<E, 64, 2>(fn, x, dy, ws, ws_floats, dw, g, st);
+}
+
+}  // namespace
+}  // namespace vah
+
+extern "C" {
+
+int vah_conv_taps_nhwc_bf16(const void *in, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *w, int64_t Cout,
+                            int T, const int *ty, const int *tx, int S, void *out, int64_t ny, int64_t nx, int64_t OH,
+                            int64_t OW, int OS, int oy0, int ox0, void *stream) {
+    return vah::conv_taps_entry<__bf16>("vah_conv_taps_nhwc_bf16", in, N, IH, IW, Cin, w, Cout, T, ty, tx, S, out, ny, nx, OH, OW,
+                                        OS, oy0, ox0, stream);
+}
+
+int vah_conv_taps_nhwc_f16(const void *in, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *w, int64_t Cout,
+                           int T, const int *ty, const int *tx, int S, void *out, int64_t ny, int64_t nx, int64_t OH,
+                           int64_t OW, int OS, int oy0, int ox0, void *stream) {
+    return vah::conv_taps_entry<_Float16>("vah_conv_taps_nhwc_f16", in, N, IH, IW, Cin, w, Cout, T, ty, tx, S, out, ny, nx, OH, OW,
+                                          OS, oy0, ox0, stream);
+}
+
+int vah_conv3x3_dgrad_nhwc_bf16(const void *gy, int64_t N, int64_t OH, int64_t OW, int64_t Cout, const void *wt, int64_t Cin,
+                                int S, void *gx, int64_t H, int64_t W, void *stream) {
+    return vah::conv_dgrad_entry<__bf16>("vah_conv3x3_dgrad_nhwc_bf16", gy, N, OH, OW, Cout, wt, Cin, S, gx, H, W, stream);
+}
+
+int vah_conv3x3_dgrad_nhwc_f16(const void *gy, int64_t N, int64_t OH, int64_t OW, int64_t Cout, const void *wt, int64_t Cin,
+                               int S, void *gx, int64_t H, int64_t W, void *stream) {
+    return vah::conv_dgrad_entry<_Float16>("vah_conv3x3_dgrad_nhwc_f16", gy, N, OH, OW, Cout, wt, Cin, S, gx, H, W, stream);
+}
+
+int64_t vah_conv3x3_wgrad_ws_floats(int64_t Cin, int64_t Cout) {
+    // one workgroup slot per CU in all, each with a 64 x 9 x CK fp32 partial
+    const int64_t CK = Cin == 16 ? 16 : 64, pairs = (Cout / 64) * (Cin / CK);
+    const int64_t slots = (vah::kCUs + pairs - 1) / pairs;
+    return slots * pairs * 64 * 9 * CK;
+}
+
+int vah_conv3x3_wgrad_nhwc_bf16(const void *x, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *dy, int64_t OH,
+                                int64_t OW, int64_t Cout, int S, float *ws, int64_t ws_floats, float *dw, void *stream) {
+    return vah::conv_wgrad_entry<__bf16>("vah_conv3x3_wgrad_nhwc_bf16", x, N, IH, IW, Cin, dy, OH, OW, Cout, S, ws, ws_floats, dw,
+                                         stream);
+}
+
+int vah_conv3x3_wgrad_nhwc_f16(const void *x, int64_t N, int64_t IH, int64_t IW, int64_t Cin, const void *dy, int64_t OH,
+                               int64_t OW, int64_t Cout, int S, float *ws, int64_t ws_floats, float *dw, void *stream) {
+    return vah::conv_wgrad_entry<_Float16>("vah_conv3x3_wgrad_nhwc_f16", x, N, IH, IW, Cin, dy, OH, OW, Cout, S, ws, ws_floats, dw,
+                                           stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,8 @@
-// Memory-bound operators of the SpatialPriorModule on NHWC bf16 activations - the layout the implicit-GEMM
-// convolutions of conv.hip read and write.  Reference: the conv -> SyncBatchNorm -> ReLU triples and the max-pool
+// Memory-bound operators of the SpatialPriorModule on NHWC bf16 (or, the `_f16` entry points, fp16) activations - the
+// layout the implicit-GEMM convolutions of conv.hip read and write.  The kernels are templates on that 16-bit type T:
+// it appears in loads, stores and converts only ((T)f: round to nearest even; fp16 overflows to inf and keeps
+// subnormals); arithmetic, partial rows, sums and statistics are fp32 for both.  bn_nhwc_sum_parts (fp32) and
+// patchify_kernel (bf16 only) are not templates.  Reference: the conv -> SyncBatchNorm -> ReLU triples and the max-pool
 // of /root/reference/detection/mmdet_custom/models/backbones/adapter_modules.py:217-260.
 //   * image (N, 3, H, W) fp32 -> (N, H, W, 16) bf16 (channels 3..15 zero: the first conv reads 16-channel pixels);
 //   * BatchNorm statistics: per-channel sum and sum of squares of a (rows, C) matrix - per-workgroup partial rows in a
@@ -21,23 +24,26 @@ namespace vah {
 namespace {
 
 using attn::bf16x8;
+using attn::tname;
+using attn::vec8;
 
 constexpr int kStatParts = 512;         // partial rows of the statistics passes (two workgroups per CU)
 
+template <typename T>
 __global__ __launch_bounds__(256) void image_to_nhwc16_kernel(const float *__restrict__ x, int64_t HW, int64_t total,
-                                                              __bf16 *__restrict__ y) {
+                                                              T *__restrict__ y) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // pixel over (n, hw)
     if (i >= total) return;
     const int64_t n = i / HW, p = i - n * HW;
     const float *px = x + n * 3 * HW + p;
-    bf16x8 a, z;
+    vec8<T> a, z;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = z[j] = (__bf16)0.f;
-    a[0] = (__bf16)px[0];
-    a[1] = (__bf16)px[HW];
-    a[2] = (__bf16)px[2 * HW];
-    *reinterpret_cast<bf16x8 *>(y + i * 16) = a;
-    *reinterpret_cast<bf16x8 *>(y + i * 16 + 8) = z;
+    for (int j = 0; j < 8; ++j) a[j] = z[j] = (T)0.f;
+    a[0] = (T)px[0];
+    a[1] = (T)px[HW];
+    a[2] = (T)px[2 * HW];
+    *reinterpret_cast<vec8<T> *>(y + i * 16) = a;
+    *reinterpret_cast<vec8<T> *>(y + i * 16 + 8) = z;
 }
 
 // image (N, C, H, W) fp32 -> patch rows (N * H/ps * W/ps, C * ps * ps) bf16, column = (c, ky, kx): the operand of the
@@ -82,8 +88,8 @@ __device__ __forceinline__ void load_affine(const BnParams &p, int c0, float (&s
 }
 
 // MODE 0: [sum x | sum x^2];  MODE 1: [sum g' | sum g' xhat], g' = dy where relu'(BN(x)) != 0 (all of dy when !relu)
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_nhwc_stats_kernel(const __bf16 *__restrict__ x, const __bf16 *__restrict__ dy,
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void bn_nhwc_stats_kernel(const T *__restrict__ x, const T *__restrict__ dy,
                                                             int64_t rows, int C, BnParams p, int relu,
                                                             float *__restrict__ part) {
     __shared__ float s_red[256][17];
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(256) void bn_nhwc_stats_kernel(const __bf16 *__rest
     // contiguous slab of rows per workgroup
     const int64_t per = (rows + gridDim.x - 1) / gridDim.x, r0 = per * blockIdx.x, r1 = r0 + per < rows ? r0 + per : rows;
     // 4 rows per step: the loads of a step are independent and in flight together
-    auto add = [&](const bf16x8 &xv, const bf16x8 &gv) {
+    auto add = [&](const vec8<T> &xv, const vec8<T> &gv) {
         if (MODE == 0) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -121,19 +127,19 @@ __global__ __launch_bounds__(256) void bn_nhwc_stats_kernel(const __bf16 *__rest
     };
     int64_t r = r0 + rl;
     for (; r + 3 * RL < r1; r += 4 * RL) {
-        bf16x8 xv[4], gv[4];
+        vec8<T> xv[4], gv[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            xv[u] = *reinterpret_cast<const bf16x8 *>(x + (r + u * RL) * C + c0);
-            if (MODE == 1) gv[u] = *reinterpret_cast<const bf16x8 *>(dy + (r + u * RL) * C + c0);
+            xv[u] = *reinterpret_cast<const vec8<T> *>(x + (r + u * RL) * C + c0);
+            if (MODE == 1) gv[u] = *reinterpret_cast<const vec8<T> *>(dy + (r + u * RL) * C + c0);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) add(xv[u], gv[u]);
     }
     for (; r < r1; r += RL) {
-        const bf16x8 xv = *reinterpret_cast<const bf16x8 *>(x + r * C + c0);
-        bf16x8 gv = xv;
-        if (MODE == 1) gv = *reinterpret_cast<const bf16x8 *>(dy + r * C + c0);
+        const vec8<T> xv = *reinterpret_cast<const vec8<T> *>(x + r * C + c0);
+        vec8<T> gv = xv;
+        if (MODE == 1) gv = *reinterpret_cast<const vec8<T> *>(dy + r * C + c0);
         add(xv, gv);
     }
 #pragma unroll
@@ -175,8 +181,9 @@ __global__ __launch_bounds__(256) void bn_nhwc_sum_parts(const float *__restrict
     }
 }
 
-__global__ __launch_bounds__(256) void bn_nhwc_apply_kernel(const __bf16 *__restrict__ x, int64_t pieces, int C, BnParams p,
-                                                            int relu, __bf16 *__restrict__ y) {
+template <typename T>
+__global__ __launch_bounds__(256) void bn_nhwc_apply_kernel(const T *__restrict__ x, int64_t pieces, int C, BnParams p,
+                                                            int relu, T *__restrict__ y) {
     const int C8 = C >> 3;
     const int64_t stride = (int64_t)gridDim.x * 256;              // a multiple of C8: the thread keeps its channels
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -184,22 +191,23 @@ __global__ __launch_bounds__(256) void bn_nhwc_apply_kernel(const __bf16 *__rest
     float sc[8], sh[8];
     load_affine(p, c0, sc, sh);
     for (; i < pieces; i += stride) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8 *>(x + i * 8);
-        bf16x8 o;
+        const vec8<T> v = *reinterpret_cast<const vec8<T> *>(x + i * 8);
+        vec8<T> o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float t = (float)v[j] * sc[j] + sh[j];
-            o[j] = (__bf16)(relu ? fmaxf(t, 0.f) : t);
+            o[j] = (T)(relu ? fmaxf(t, 0.f) : t);
         }
-        *reinterpret_cast<bf16x8 *>(y + i * 8) = o;
+        *reinterpret_cast<vec8<T> *>(y + i * 8) = o;
     }
 }
 
 // dx = w rstd (g' - mean(g') - xhat mean(g' xhat))
-__global__ __launch_bounds__(256) void bn_nhwc_bwd_apply_kernel(const __bf16 *__restrict__ x, const __bf16 *__restrict__ dy,
+template <typename T>
+__global__ __launch_bounds__(256) void bn_nhwc_bwd_apply_kernel(const T *__restrict__ x, const T *__restrict__ dy,
                                                                 int64_t pieces, int C, BnParams p, int relu,
                                                                 const float *__restrict__ mg, const float *__restrict__ mgx,
-                                                                __bf16 *__restrict__ dx) {
+                                                                T *__restrict__ dx) {
     const int C8 = C >> 3;
     const int64_t stride = (int64_t)gridDim.x * 256;
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -209,23 +217,24 @@ __global__ __launch_bounds__(256) void bn_nhwc_bwd_apply_kernel(const __bf16 *__
 #pragma unroll
     for (int j = 0; j < 8; ++j) mu[j] = p.mean[c0 + j], rs[j] = p.rstd[c0 + j], m0[j] = mg[c0 + j], m1[j] = mgx[c0 + j];
     for (; i < pieces; i += stride) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8 *>(x + i * 8);
-        const bf16x8 gv = *reinterpret_cast<const bf16x8 *>(dy + i * 8);
-        bf16x8 o;
+        const vec8<T> v = *reinterpret_cast<const vec8<T> *>(x + i * 8);
+        const vec8<T> gv = *reinterpret_cast<const vec8<T> *>(dy + i * 8);
+        vec8<T> o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float xv = (float)v[j];
             const float g = (!relu || xv * sc[j] + sh[j] > 0.f) ? (float)gv[j] : 0.f;
-            o[j] = (__bf16)(sc[j] * (g - m0[j] - (xv - mu[j]) * rs[j] * m1[j]));
+            o[j] = (T)(sc[j] * (g - m0[j] - (xv - mu[j]) * rs[j] * m1[j]));
         }
-        *reinterpret_cast<bf16x8 *>(dx + i * 8) = o;
+        *reinterpret_cast<vec8<T> *>(dx + i * 8) = o;
     }
 }
 
 // MaxPool2d(3, 2, 1) on (N, H, W, C): output piece = 8 channels of one output pixel; idx = window position 0..8 of the
 // first maximum in scan order (what torch's max_pool2d sends the gradient to)
-__global__ __launch_bounds__(256) void maxpool_nhwc_fwd_kernel(const __bf16 *__restrict__ x, int N, int H, int W, int C, int OH,
-                                                               int OW, __bf16 *__restrict__ y, uint8_t *__restrict__ idx) {
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool_nhwc_fwd_kernel(const T *__restrict__ x, int N, int H, int W, int C, int OH,
+                                                               int OW, T *__restrict__ y, uint8_t *__restrict__ idx) {
     const int C8 = C >> 3;
     const int64_t pieces = (int64_t)N * OH * OW * C8, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= pieces) return;
@@ -242,24 +251,25 @@ __global__ __launch_bounds__(256) void maxpool_nhwc_fwd_kernel(const __bf16 *__r
     for (int k = 0; k < 9; ++k) {
         const int iy = 2 * oy - 1 + k / 3, ix = 2 * ox - 1 + k % 3;
         if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-        const bf16x8 v = *reinterpret_cast<const bf16x8 *>(x + (((int64_t)n * H + iy) * W + ix) * C + c8 * 8);
+        const vec8<T> v = *reinterpret_cast<const vec8<T> *>(x + (((int64_t)n * H + iy) * W + ix) * C + c8 * 8);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float f = (float)v[j];
             if (f > best[j]) best[j] = f, bi[j] = (uint8_t)k;      // strict: ties keep the first position
         }
     }
-    bf16x8 o;
+    vec8<T> o;
     uint64_t packed = 0;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (__bf16)best[j], packed |= (uint64_t)bi[j] << (8 * j);
-    *reinterpret_cast<bf16x8 *>(y + i * 8) = o;
+    for (int j = 0; j < 8; ++j) o[j] = (T)best[j], packed |= (uint64_t)bi[j] << (8 * j);
+    *reinterpret_cast<vec8<T> *>(y + i * 8) = o;
     *reinterpret_cast<uint64_t *>(idx + i * 8) = packed;
 }
 
-__global__ __launch_bounds__(256) void maxpool_nhwc_bwd_kernel(const __bf16 *__restrict__ gy, const uint8_t *__restrict__ idx,
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool_nhwc_bwd_kernel(const T *__restrict__ gy, const uint8_t *__restrict__ idx,
                                                                int N, int H, int W, int C, int OH, int OW,
-                                                               __bf16 *__restrict__ gx) {
+                                                               T *__restrict__ gx) {
     const int C8 = C >> 3;
     const int64_t pieces = (int64_t)N * H * W * C8, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= pieces) return;
@@ -279,16 +289,16 @@ __global__ __launch_bounds__(256) void maxpool_nhwc_bwd_kernel(const __bf16 *__r
             const int k = (iy - (2 * oy - 1)) * 3 + (ix - (2 * ox - 1));
             const int64_t o = (((int64_t)n * OH + oy) * OW + ox) * C + c8 * 8;
             const uint64_t packed = *reinterpret_cast<const uint64_t *>(idx + o);
-            const bf16x8 g = *reinterpret_cast<const bf16x8 *>(gy + o);
+            const vec8<T> g = *reinterpret_cast<const vec8<T> *>(gy + o);
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if ((int)((packed >> (8 * j)) & 0xff) == k) acc[j] += (float)g[j];
         }
     }
-    bf16x8 o;
+    vec8<T> o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (__bf16)acc[j];
-    *reinterpret_cast<bf16x8 *>(gx + i * 8) = o;
+    for (int j = 0; j < 8; ++j) o[j] = (T)acc[j];
+    *reinterpret_cast<vec8<T> *>(gx + i * 8) = o;
 }
 
 int check_c(const char *fn, int64_t rows, int64_t C) {
@@ -306,72 +316,67 @@ unsigned apply_grid(int64_t pieces) {
     return (unsigned)(want < 8 * kCUs ? (want < 1 ? 1 : want) : 8 * kCUs);       // x 256 threads: a multiple of every C / 8
 }
 
-}  // namespace
-}  // namespace vah
 
-extern "C" {
-
-int vah_image_to_nhwc16_bf16(const float *x, int64_t N, int64_t H, int64_t W, void *y, void *stream) {
-    using namespace vah;
+// ---------------------------------------------------------------------------------------
+// Launch helpers: one copy of the argument checks, launch geometry, workspaces and byte accounting for both
+// element types.  `fn` is the entry point's own name (messages), T its 16-bit type.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+int image_to_nhwc16_launch(const char *fn, const float *x, int64_t N, int64_t H, int64_t W, void *y, void *stream) {
     clear_error();
-    if (N < 0 || H < 1 || W < 1) return fail(VAH_E_SHAPE, "vah_image_to_nhwc16_bf16: bad dims");
+    if (N < 0 || H < 1 || W < 1) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (N == 0) return VAH_OK;
-    if (!x || !y) return fail(VAH_E_NULL, "vah_image_to_nhwc16_bf16: null pointer");
-    if ((uintptr_t)y % 16) return fail(VAH_E_ALIGN, "vah_image_to_nhwc16_bf16: y needs 16-byte alignment");
+    if (!x || !y) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if ((uintptr_t)y % 16) return fail(VAH_E_ALIGN, "%s: y needs 16-byte alignment", fn);
     const int64_t total = N * H * W;
-    LaunchScope scope("spm_image_to_nhwc", total * (12 + 32), (hipStream_t)stream);
-    hipLaunchKernelGGL(image_to_nhwc16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, H * W,
-                       total, (__bf16 *)y);
+    LaunchScope scope(tname<T>("spm_image_to_nhwc", "spm_image_to_nhwc_f16"), total * (12 + 32), (hipStream_t)stream);
+    hipLaunchKernelGGL(image_to_nhwc16_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, H * W,
+                       total, (T *)y);
     return check_launch("image_to_nhwc16");
 }
 
-int64_t vah_bn_nhwc_ws_floats(int64_t C) { return vah::kStatParts * 2 * C; }
-
-/* sums[2C] = [sum x | sum x^2] over the rows of x (rows, C) bf16 */
-int vah_bn_nhwc_stats(const void *x, int64_t rows, int64_t C, float *sums, float *ws, void *stream) {
-    using namespace vah;
+/* sums[2C] = [sum x | sum x^2] over the rows of x (rows, C) */
+template <typename T>
+int bn_stats_launch(const char *fn, const void *x, int64_t rows, int64_t C, float *sums, float *ws, void *stream) {
     clear_error();
-    const char *fn = "vah_bn_nhwc_stats";
     if (int rc = check_c(fn, rows, C)) return rc;
     if (!x || !sums || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
     hipStream_t st = (hipStream_t)stream;
     const int parts = stat_parts(rows);
-    LaunchScope scope("spm_bn_stats", rows * C * 2, st);
-    hipLaunchKernelGGL(bn_nhwc_stats_kernel<0>, dim3(parts), dim3(256), 0, st, (const __bf16 *)x, (const __bf16 *)nullptr, rows,
-                       (int)C, BnParams{}, 0, ws);
+    LaunchScope scope(tname<T>("spm_bn_stats", "spm_bn_stats_f16"), rows * C * 2, st);
+    hipLaunchKernelGGL((bn_nhwc_stats_kernel<T, 0>), dim3(parts), dim3(256), 0, st, (const T *)x, (const T *)nullptr, rows, (int)C,
+                       BnParams{}, 0, ws);
     if (int rc = check_launch(fn)) return rc;
     hipLaunchKernelGGL(bn_nhwc_sum_parts, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, (const float *)ws, parts,
                        (int)(2 * C), sums);
     return check_launch(fn);
 }
 
-int vah_bn_nhwc_apply(const void *x, int64_t rows, int64_t C, const float *mean, const float *rstd, const float *w,
-                      const float *b, int relu, void *y, void *stream) {
-    using namespace vah;
+template <typename T>
+int bn_apply_launch(const char *fn, const void *x, int64_t rows, int64_t C, const float *mean, const float *rstd, const float *w,
+                    const float *b, int relu, void *y, void *stream) {
     clear_error();
-    const char *fn = "vah_bn_nhwc_apply";
     if (int rc = check_c(fn, rows, C)) return rc;
     if (rows == 0) return VAH_OK;
     if (!x || !y || !mean || !rstd) return fail(VAH_E_NULL, "%s: null pointer", fn);
     const int64_t pieces = rows * C / 8;
-    LaunchScope scope("spm_bn_apply", rows * C * 4, (hipStream_t)stream);
-    hipLaunchKernelGGL(bn_nhwc_apply_kernel, dim3(apply_grid(pieces)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)x, pieces,
-                       (int)C, BnParams{mean, rstd, w, b}, relu, (__bf16 *)y);
+    LaunchScope scope(tname<T>("spm_bn_apply", "spm_bn_apply_f16"), rows * C * 4, (hipStream_t)stream);
+    hipLaunchKernelGGL(bn_nhwc_apply_kernel<T>, dim3(apply_grid(pieces)), dim3(256), 0, (hipStream_t)stream, (const T *)x, pieces,
+                       (int)C, BnParams{mean, rstd, w, b}, relu, (T *)y);
     return check_launch(fn);
 }
 
 /* sums[2C] = [sum g' | sum g' xhat] */
-int vah_bn_nhwc_bwd_stats(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
-                          const float *w, const float *b, int relu, float *sums, float *ws, void *stream) {
-    using namespace vah;
+template <typename T>
+int bn_bwd_stats_launch(const char *fn, const void *x, const void *dy, int64_t rows, int64_t C, const float *mean,
+                        const float *rstd, const float *w, const float *b, int relu, float *sums, float *ws, void *stream) {
     clear_error();
-    const char *fn = "vah_bn_nhwc_bwd_stats";
     if (int rc = check_c(fn, rows, C)) return rc;
     if (!x || !dy || !sums || !ws || !mean || !rstd) return fail(VAH_E_NULL, "%s: null pointer", fn);
     hipStream_t st = (hipStream_t)stream;
     const int parts = stat_parts(rows);
-    LaunchScope scope("spm_bn_bwd_stats", rows * C * 4, st);
-    hipLaunchKernelGGL(bn_nhwc_stats_kernel<1>, dim3(parts), dim3(256), 0, st, (const __bf16 *)x, (const __bf16 *)dy, rows, (int)C,
+    LaunchScope scope(tname<T>("spm_bn_bwd_stats", "spm_bn_bwd_stats_f16"), rows * C * 4, st);
+    hipLaunchKernelGGL((bn_nhwc_stats_kernel<T, 1>), dim3(parts), dim3(256), 0, st, (const T *)x, (const T *)dy, rows, (int)C,
                        BnParams{mean, rstd, w, b}, relu, ws);
     if (int rc = check_launch(fn)) return rc;
     hipLaunchKernelGGL(bn_nhwc_sum_parts, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, (const float *)ws, parts,
@@ -379,51 +384,115 @@ int vah_bn_nhwc_bwd_stats(const void *x, const void *dy, int64_t rows, int64_t C
     return check_launch(fn);
 }
 
-int vah_bn_nhwc_bwd_apply(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
-                          const float *w, const float *b, int relu, const float *mean_g, const float *mean_gx, void *dx,
-                          void *stream) {
-    using namespace vah;
+template <typename T>
+int bn_bwd_apply_launch(const char *fn, const void *x, const void *dy, int64_t rows, int64_t C, const float *mean,
+                        const float *rstd, const float *w, const float *b, int relu, const float *mean_g, const float *mean_gx,
+                        void *dx, void *stream) {
     clear_error();
-    const char *fn = "vah_bn_nhwc_bwd_apply";
     if (int rc = check_c(fn, rows, C)) return rc;
     if (rows == 0) return VAH_OK;
     if (!x || !dy || !dx || !mean || !rstd || !mean_g || !mean_gx) return fail(VAH_E_NULL, "%s: null pointer", fn);
     const int64_t pieces = rows * C / 8;
-    LaunchScope scope("spm_bn_bwd_apply", rows * C * 6, (hipStream_t)stream);
-    hipLaunchKernelGGL(bn_nhwc_bwd_apply_kernel, dim3(apply_grid(pieces)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)x,
-                       (const __bf16 *)dy, pieces, (int)C, BnParams{mean, rstd, w, b}, relu, mean_g, mean_gx, (__bf16 *)dx);
+    LaunchScope scope(tname<T>("spm_bn_bwd_apply", "spm_bn_bwd_apply_f16"), rows * C * 6, (hipStream_t)stream);
+    hipLaunchKernelGGL(bn_nhwc_bwd_apply_kernel<T>, dim3(apply_grid(pieces)), dim3(256), 0, (hipStream_t)stream, (const T *)x,
+                       (const T *)dy, pieces, (int)C, BnParams{mean, rstd, w, b}, relu, mean_g, mean_gx, (T *)dx);
     return check_launch(fn);
 }
 
-int vah_maxpool3s2_nhwc_fwd_bf16(const void *x, int64_t N, int64_t H, int64_t W, int64_t C, void *y, void *idx, void *stream) {
-    using namespace vah;
+template <typename T>
+int maxpool_fwd_launch(const char *fn, const void *x, int64_t N, int64_t H, int64_t W, int64_t C, void *y, void *idx, void *stream) {
     clear_error();
-    const char *fn = "vah_maxpool3s2_nhwc_fwd_bf16";
     if (N < 0 || H < 1 || W < 1 || C < 8 || C % 8 || H > 32767 || W > 32767) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (N == 0) return VAH_OK;
     if (!x || !y || !idx) return fail(VAH_E_NULL, "%s: null pointer", fn);
     const int64_t OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, pieces = N * OH * OW * (C / 8);
-    LaunchScope scope("spm_maxpool_fwd", N * H * W * C * 2 + N * OH * OW * C * 3, (hipStream_t)stream);
-    hipLaunchKernelGGL(maxpool_nhwc_fwd_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const __bf16 *)x, (int)N, (int)H, (int)W, (int)C, (int)OH, (int)OW, (__bf16 *)y, (uint8_t *)idx);
+    LaunchScope scope(tname<T>("spm_maxpool_fwd", "spm_maxpool_fwd_f16"), N * H * W * C * 2 + N * OH * OW * C * 3, (hipStream_t)stream);
+    hipLaunchKernelGGL(maxpool_nhwc_fwd_kernel<T>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const T *)x, (int)N, (int)H, (int)W, (int)C, (int)OH, (int)OW, (T *)y, (uint8_t *)idx);
     return check_launch(fn);
 }
 
-int vah_maxpool3s2_nhwc_bwd_bf16(const void *gy, const void *idx, int64_t N, int64_t H, int64_t W, int64_t C, void *gx,
-                                 void *stream) {
-    using namespace vah;
+template <typename T>
+int maxpool_bwd_launch(const char *fn, const void *gy, const void *idx, int64_t N, int64_t H, int64_t W, int64_t C, void *gx,
+                       void *stream) {
     clear_error();
-    const char *fn = "vah_maxpool3s2_nhwc_bwd_bf16";
     if (N < 0 || H < 1 || W < 1 || C < 8 || C % 8 || H > 32767 || W > 32767) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (N == 0) return VAH_OK;
     if (!gy || !gx || !idx) return fail(VAH_E_NULL, "%s: null pointer", fn);
     const int64_t OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, pieces = N * H * W * (C / 8);
-    LaunchScope scope("spm_maxpool_bwd", N * H * W * C * 2 + N * OH * OW * C * 3, (hipStream_t)stream);
-    hipLaunchKernelGGL(maxpool_nhwc_bwd_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const __bf16 *)gy, (const uint8_t *)idx, (int)N, (int)H, (int)W, (int)C, (int)OH, (int)OW, (__bf16 *)gx);
+    LaunchScope scope(tname<T>("spm_maxpool_bwd", "spm_maxpool_bwd_f16"), N * H * W * C * 2 + N * OH * OW * C * 3, (hipStream_t)stream);
+    hipLaunchKernelGGL(maxpool_nhwc_bwd_kernel<T>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const T *)gy, (const uint8_t *)idx, (int)N, (int)H, (int)W, (int)C, (int)OH, (int)OW, (T *)gx);
     return check_launch(fn);
 }
 
+}  // namespace
+}  // namespace vah
+
+extern "C" {
+
+int vah_image_to_nhwc16_bf16(const float *x, int64_t N, int64_t H, int64_t W, void *y, void *stream) {
+    return vah::image_to_nhwc16_launch<__bf16>("vah_image_to_nhwc16_bf16", x, N, H, W, y, stream);
+}
+int vah_image_to_nhwc16_f16(const float *x, int64_t N, int64_t H, int64_t W, void *y, void *stream) {
+    return vah::image_to_nhwc16_launch<_Float16>("vah_image_to_nhwc16_f16", x, N, H, W, y, stream);
+}
+
+int64_t vah_bn_nhwc_ws_floats(int64_t C) { return vah::kStatParts * 2 * C; }
+
+int vah_bn_nhwc_stats(const void *x, int64_t rows, int64_t C, float *sums, float *ws, void *stream) {
+    return vah::bn_stats_launch<__bf16>("vah_bn_nhwc_stats", x, rows, C, sums, ws, stream);
+}
+int vah_bn_nhwc_stats_f16(const void *x, int64_t rows, int64_t C, float *sums, float *ws, void *stream) {
+    return vah::bn_stats_launch<_Float16>("vah_bn_nhwc_stats_f16", x, rows, C, sums, ws, stream);
+}
+
+int vah_bn_nhwc_apply(const void *x, int64_t rows, int64_t C, const float *mean, const float *rstd, const float *w,
+                      const float *b, int relu, void *y, void *stream) {
+    return vah::bn_apply_launch<__bf16>("vah_bn_nhwc_apply", x, rows, C, mean, rstd, w, b, relu, y, stream);
+}
+int vah_bn_nhwc_apply_f16(const void *x, int64_t rows, int64_t C, const float *mean, const float *rstd, const float *w,
+                          const float *b, int relu, void *y, void *stream) {
+    return vah::bn_apply_launch<_Float16>("vah_bn_nhwc_apply_f16", x, rows, C, mean, rstd, w, b, relu, y, stream);
+}
+
+int vah_bn_nhwc_bwd_stats(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
+                          const float *w, const float *b, int relu, float *sums, float *ws, void *stream) {
+    return vah::bn_bwd_stats_launch<__bf16>("vah_bn_nhwc_bwd_stats", x, dy, rows, C, mean, rstd, w, b, relu, sums, ws, stream);
+}
+int vah_bn_nhwc_bwd_stats_f16(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
+                              const float *w, const float *b, int relu, float *sums, float *ws, void *stream) {
+    return vah::bn_bwd_stats_launch<_Float16>("vah_bn_nhwc_bwd_stats_f16", x, dy, rows, C, mean, rstd, w, b, relu, sums, ws, stream);
+}
+
+int vah_bn_nhwc_bwd_apply(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
+                          const float *w, const float *b, int relu, const float *mean_g, const float *mean_gx, void *dx,
+                          void *stream) {
+    return vah::bn_bwd_apply_launch<__bf16>("vah_bn_nhwc_bwd_apply", x, dy, rows, C, mean, rstd, w, b, relu, mean_g, mean_gx, dx,
+                                            stream);
+}
+int vah_bn_nhwc_bwd_apply_f16(const void *x, const void *dy, int64_t rows, int64_t C, const float *mean, const float *rstd,
+                              const float *w, const float *b, int relu, const float *mean_g, const float *mean_gx, void *dx,
+                              void *stream) {
+    return vah::bn_bwd_apply_launch<_Float16>("vah_bn_nhwc_bwd_apply_f16", x, dy, rows, C, mean, rstd, w, b, relu, mean_g, mean_gx,
+                                              dx, stream);
+}
+
+int vah_maxpool3s2_nhwc_fwd_bf16(const void *x, int64_t N, int64_t H, int64_t W, int64_t C, void *y, void *idx, void *stream) {
+    return vah::maxpool_fwd_launch<__bf16>("vah_maxpool3s2_nhwc_fwd_bf16", x, N, H, W, C, y, idx, stream);
+}
+int vah_maxpool3s2_nhwc_fwd_f16(const void *x, int64_t N, int64_t H, int64_t W, int64_t C, void *y, void *idx, void *stream) {
+    return vah::maxpool_fwd_launch<_Float16>("vah_maxpool3s2_nhwc_fwd_f16", x, N, H, W, C, y, idx, stream);
+}
+
+int vah_maxpool3s2_nhwc_bwd_bf16(const void *gy, const void *idx, int64_t N, int64_t H, int64_t W, int64_t C, void *gx,
+                                 void *stream) {
+    return vah::maxpool_bwd_launch<__bf16>("vah_maxpool3s2_nhwc_bwd_bf16", gy, idx, N, H, W, C, gx, stream);
+}
+int vah_maxpool3s2_nhwc_bwd_f16(const void *gy, const void *idx, int64_t N, int64_t H, int64_t W, int64_t C, void *gx,
+                                void *stream) {
+    return vah::maxpool_bwd_launch<_Float16>("vah_maxpool3s2_nhwc_bwd_f16", gy, idx, N, H, W, C, gx, stream);
+}
 
 int vah_patchify_bf16(const float *x, int64_t N, int64_t C, int64_t H, int64_t W, int64_t ps, void *y, void *stream) {
     using namespace vah;

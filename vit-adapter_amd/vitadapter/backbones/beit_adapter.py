@@ -70,8 +70,8 @@ class BEiTAdapter(BEiT):
 
         # fused tail: the biases of spm.fc1 and self.up reach norm1 as a per-channel shift
         fold = self.add_vit_feature and fused.tail_takes_conv_bias(self.norm1, x)
-        if fold and spm_nhwc.usable(self.spm, x) and not (self.spm.with_cp and x.requires_grad):
-            c1, c = spm_nhwc.forward(self.spm, x, self.level_embed)
+        if spm_nhwc.takes(self.spm, x, fold):
+            c1, c = spm_nhwc.forward(self.spm, x, self.level_embed, c1_bias=not fold)
         elif fused.ENABLED['maps'] and fused.ENABLED['maps_in'] and x.is_cuda:
             # c2..c4 leave the SPM as bias-free maps; bias + level embedding are added while the token
             # sequence is laid out (one pass per map instead of bias add, level add and cat)

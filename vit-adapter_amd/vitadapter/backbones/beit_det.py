@@ -234,8 +234,8 @@ class BEiTAdapter(BEiT):
     def _forward(self, x):
         deform_inputs1, deform_inputs2 = deform_inputs(x)
         fold = self.add_vit_feature and fused.tail_takes_conv_bias(self.norm1, x)
-        if fold and spm_nhwc.usable(self.spm, x) and not (self.spm.with_cp and x.requires_grad):
-            c1, c = spm_nhwc.forward(self.spm, x, self.level_embed)
+        if spm_nhwc.takes(self.spm, x, fold):
+            c1, c = spm_nhwc.forward(self.spm, x, self.level_embed, c1_bias=not fold)
         else:
             c1, c2, c3, c4 = self.spm(x, bias_free_c1=fold)
             c = torch.cat([c2 + self.level_embed[0], c3 + self.level_embed[1], c4 + self.level_embed[2]], dim=1)

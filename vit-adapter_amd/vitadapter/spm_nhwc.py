@@ -1,11 +1,16 @@
-"""SpatialPriorModule on NHWC bf16 activations: implicit-GEMM 3x3 convolutions (csrc/conv.hip) with the
-BatchNorm + ReLU, max-pool and image-layout kernels of csrc/spm_nhwc.hip between them.
+"""SpatialPriorModule on NHWC 16-bit activations (bf16 under bf16 autocast, fp16 under fp16 autocast): implicit-GEMM
+3x3 convolutions (csrc/conv.hip) with the BatchNorm + ReLU, max-pool and image-layout kernels of csrc/spm_nhwc.hip
+between them.
 
 Reference: SpatialPriorModule.forward of
 /root/reference/detection/mmdet_custom/models/backbones/adapter_modules.py:217-268.  The arithmetic is the module's
 (convolutions with bf16 operands and fp32 accumulation as under autocast, batch statistics in fp32, SyncBatchNorm
 all-reduces of the sums); the layout is the kernels': no NCHW <-> NHWC conversion inside the module, and the
 stride-8/16/32 maps are already the (B, H*W, C) token rows the 1x1 projections and the adapter consume.
+Under fp16 autocast (the reference's AMP mode; VAH_FUSED_DISABLE=fp16_spm restores torch's NCHW module) the same
+kernels run instantiated on fp16 (`*_f16` entry points): fp32 sums and statistics, fp32 -> fp16 rounded to nearest
+even with overflow to inf and subnormals kept; the weight gradients stay fp32.  The four 1x1 projections then are
+torch's fp16 library GEMMs on the NHWC rows (as every other Linear is in that mode).
 There is no CPU path behind these functions."""
 import torch
 import torch.nn.functional as F
@@ -18,19 +23,25 @@ def _stream(t):
     return _vah.raw_stream(t.device)
 
 
-def image_to_nhwc16(x):
-    """(N, 3, H, W) fp32 -> (N, H, W, 16) bf16 with channels 3..15 zero (no gradient: the image is a leaf input)."""
+def _sym(name, dtype):
+    """The entry point ``name`` (its bf16 spelling) for 16-bit operands of ``dtype``: itself or its `_f16` twin."""
+    return conv._sym(name, dtype)[0]
+
+
+def image_to_nhwc16(x, dtype=torch.bfloat16):
+    """(N, 3, H, W) fp32 -> (N, H, W, 16) ``dtype`` (bf16 | fp16) with channels 3..15 zero (no gradient: the image is a
+    leaf input)."""
     N, C, H, W = x.shape
     assert C == 3 and x.dtype == torch.float32
     x = x.contiguous()
-    y = torch.empty((N, H, W, 16), dtype=torch.bfloat16, device=x.device)
+    y = torch.empty((N, H, W, 16), dtype=dtype, device=x.device)
     with _vah.on(x.device):
-        _vah.check(_vah.lib.vah_image_to_nhwc16_bf16(x.data_ptr(), N, H, W, y.data_ptr(), _stream(x)), 'image_to_nhwc16')
+        _vah.check(_sym('vah_image_to_nhwc16_bf16', dtype)(x.data_ptr(), N, H, W, y.data_ptr(), _stream(x)), 'image_to_nhwc16')
     return y
 
 
 class _Conv3x3(torch.autograd.Function):
-    """nn.Conv2d(k=3, padding=1, bias=False) on NHWC bf16; weight (Cout, Cin, 3, 3) fp32.  An input with more channels
+    """nn.Conv2d(k=3, padding=1, bias=False) on NHWC bf16 | fp16; weight (Cout, Cin, 3, 3) fp32.  An input with more channels
     than the weight (the 16-channel image) is matched by zero weight columns."""
 
     @staticmethod
@@ -39,18 +50,18 @@ class _Conv3x3(torch.autograd.Function):
         w = weight.detach()
         if w.shape[1] != cin:
             w = F.pad(w, (0, 0, 0, 0, 0, cin - w.shape[1]))
-        wb = w.to(torch.bfloat16)
+        wb = w.to(x.dtype)
         ctx.save_for_backward(x, wb)
         ctx.stride, ctx.wcin = stride, weight.shape[1]
-        return conv.conv3x3_forward(x, conv.forward_weight(wb), stride)
+        return conv.conv3x3_forward(x, conv.forward_weight(wb, x.dtype), stride)
 
     @staticmethod
     def backward(ctx, gy):
         x, wb = ctx.saved_tensors
-        gy = gy.contiguous()
+        gy = gy.contiguous().to(x.dtype)
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            gx = conv.conv3x3_input_grad(gy, conv.dgrad_weight(wb), ctx.stride, x.shape[1:3])
+            gx = conv.conv3x3_input_grad(gy, conv.dgrad_weight(wb, x.dtype), ctx.stride, x.shape[1:3])
         if ctx.needs_input_grad[1]:
             gw = conv.conv3x3_weight_grad(x, gy, ctx.stride).permute(0, 3, 1, 2)[:, :ctx.wcin].contiguous()
         return gx, gw, None
@@ -73,7 +84,7 @@ class _BNRelu(torch.autograd.Function):
             if training:
                 sums = torch.empty(2 * C + 1, dtype=torch.float32, device=dev)
                 ws = torch.empty(_vah.lib.vah_bn_nhwc_ws_floats(C), dtype=torch.float32, device=dev)
-                _vah.check(_vah.lib.vah_bn_nhwc_stats(x.data_ptr(), rows, C, sums.data_ptr(), ws.data_ptr(), st), 'bn_nhwc_stats')
+                _vah.check(_sym('vah_bn_nhwc_stats', x.dtype)(x.data_ptr(), rows, C, sums.data_ptr(), ws.data_ptr(), st), 'bn_nhwc_stats')
                 sums[2 * C:].fill_(float(rows))
                 if group is not None:
                     import torch.distributed as dist
@@ -94,9 +105,9 @@ class _BNRelu(torch.autograd.Function):
                 mean = norm.running_mean.float().contiguous()
                 rstd = torch.rsqrt(norm.running_var.float() + norm.eps)
             y = torch.empty_like(x)
-            _vah.check(_vah.lib.vah_bn_nhwc_apply(x.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(),
-                                                  w.data_ptr() if w is not None else None,
-                                                  b.data_ptr() if b is not None else None, int(relu), y.data_ptr(), st),
+            _vah.check(_sym('vah_bn_nhwc_apply', x.dtype)(x.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(),
+                                                          w.data_ptr() if w is not None else None,
+                                                          b.data_ptr() if b is not None else None, int(relu), y.data_ptr(), st),
                        'bn_nhwc_apply')
         ctx.save_for_backward(x, mean, rstd, w, b, count)
         ctx.meta = (training, group, weight is not None, bias is not None, relu)
@@ -108,15 +119,16 @@ class _BNRelu(torch.autograd.Function):
         training, group, has_w, has_b, relu = ctx.meta
         C = x.shape[-1]
         rows = x.numel() // C
-        dy = dy.contiguous().to(torch.bfloat16)
+        dy = dy.contiguous().to(x.dtype)
         dev, st = x.device, _stream(x)
         wp = w.data_ptr() if w is not None else None
         bp = b.data_ptr() if b is not None else None
         with _vah.on(dev):
             sums = torch.empty(2 * C, dtype=torch.float32, device=dev)
             ws = torch.empty(_vah.lib.vah_bn_nhwc_ws_floats(C), dtype=torch.float32, device=dev)
-            _vah.check(_vah.lib.vah_bn_nhwc_bwd_stats(x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(), wp,
-                                                      bp, int(relu), sums.data_ptr(), ws.data_ptr(), st), 'bn_nhwc_bwd_stats')
+            _vah.check(_sym('vah_bn_nhwc_bwd_stats', x.dtype)(x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(),
+                                                              rstd.data_ptr(), wp, bp, int(relu), sums.data_ptr(), ws.data_ptr(),
+                                                              st), 'bn_nhwc_bwd_stats')
             local = sums.clone() if (training and group is not None) else sums      # dweight / dbias are per-rank sums
             dweight = local[C:] if has_w else None
             dbias = local[:C] if has_b else None
@@ -130,14 +142,14 @@ class _BNRelu(torch.autograd.Function):
                 else:
                     means = torch.zeros_like(sums)          # running statistics are constants
                 dx = torch.empty_like(x)
-                _vah.check(_vah.lib.vah_bn_nhwc_bwd_apply(x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(),
-                                                          wp, bp, int(relu), means[:C].data_ptr(), means[C:].data_ptr(),
-                                                          dx.data_ptr(), st), 'bn_nhwc_bwd_apply')
+                _vah.check(_sym('vah_bn_nhwc_bwd_apply', x.dtype)(x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(),
+                                                                  rstd.data_ptr(), wp, bp, int(relu), means[:C].data_ptr(),
+                                                                  means[C:].data_ptr(), dx.data_ptr(), st), 'bn_nhwc_bwd_apply')
         return dx, dweight, dbias, None, None
 
 
 class _MaxPool(torch.autograd.Function):
-    """MaxPool2d(3, stride 2, padding 1) on NHWC bf16."""
+    """MaxPool2d(3, stride 2, padding 1) on NHWC bf16 | fp16."""
 
     @staticmethod
     def forward(ctx, x):
@@ -146,21 +158,21 @@ class _MaxPool(torch.autograd.Function):
         y = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
         idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_maxpool3s2_nhwc_fwd_bf16(x.data_ptr(), N, H, W, C, y.data_ptr(), idx.data_ptr(), _stream(x)),
-                       'maxpool_nhwc_fwd')
+            _vah.check(_sym('vah_maxpool3s2_nhwc_fwd_bf16', x.dtype)(x.data_ptr(), N, H, W, C, y.data_ptr(), idx.data_ptr(),
+                                                                     _stream(x)), 'maxpool_nhwc_fwd')
         ctx.save_for_backward(idx)
-        ctx.in_shape = x.shape
+        ctx.in_shape, ctx.in_dtype = x.shape, x.dtype
         return y
 
     @staticmethod
     def backward(ctx, gy):
         idx, = ctx.saved_tensors
         N, H, W, C = ctx.in_shape
-        gy = gy.contiguous().to(torch.bfloat16)
-        gx = torch.empty(ctx.in_shape, dtype=torch.bfloat16, device=gy.device)
+        gy = gy.contiguous().to(ctx.in_dtype)
+        gx = torch.empty(ctx.in_shape, dtype=ctx.in_dtype, device=gy.device)
         with _vah.on(gy.device):
-            _vah.check(_vah.lib.vah_maxpool3s2_nhwc_bwd_bf16(gy.data_ptr(), idx.data_ptr(), N, H, W, C, gx.data_ptr(), _stream(gy)),
-                       'maxpool_nhwc_bwd')
+            _vah.check(_sym('vah_maxpool3s2_nhwc_bwd_bf16', ctx.in_dtype)(gy.data_ptr(), idx.data_ptr(), N, H, W, C, gx.data_ptr(),
+                                                                          _stream(gy)), 'maxpool_nhwc_bwd')
         return gx
 
 
@@ -198,12 +210,32 @@ class _Conv1x1ToPlanes(torch.autograd.Function):
         return dx, dw
 
 
+def autocast_dtype():
+    """The 16-bit type the NHWC path runs in under the active autocast: torch.bfloat16, torch.float16, or None (no
+    autocast, another autocast type, or fp16 with its switch off: VAH_FUSED_DISABLE=fp16_spm, for A/B runs)."""
+    if not torch.is_autocast_enabled():
+        return None
+    dtype = torch.get_autocast_dtype('cuda')
+    if dtype == torch.bfloat16 or (dtype == torch.float16 and fused.ENABLED['fp16_spm']):
+        return dtype
+    return None
+
+
+def takes(spm, x, fold):
+    """Does the backbone hand the module to forward()?  Under bf16 autocast when the BatchNorm tail takes fc1's bias
+    (``fold``); under fp16 autocast whenever usable() holds (the tail is bf16-only: forward() then adds the bias)."""
+    if not (fold or autocast_dtype() == torch.float16):
+        return False
+    return usable(spm, x) and not (spm.with_cp and x.requires_grad)
+
+
 def usable(spm, x):
     """The NHWC path serves the module as the reference builds it (3x3 / padding 1 / bias-free convolutions with
-    64-multiple widths, (Sync)BatchNorm + ReLU, the 3/2/1 max-pool) on a CUDA fp32 image under bf16 autocast."""
+    64-multiple widths, (Sync)BatchNorm + ReLU, the 3/2/1 max-pool) on a CUDA fp32 image under bf16 or fp16
+    autocast."""
     # the image's own gradient is not produced by this path: an input that requires grad takes the module as written
     if not (fused.ENABLED.get('spm_nhwc', True) and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad and x.dim() == 4 and x.shape[1] == 3
-            and fused._bf16_autocast() and x.shape[2] % 32 == 0 and x.shape[3] % 32 == 0 and x.numel() > 0):
+            and autocast_dtype() is not None and x.shape[2] % 32 == 0 and x.shape[3] % 32 == 0 and x.numel() > 0):
         return False
     convs = [spm.stem[0], spm.stem[3], spm.stem[6], spm.conv2[0], spm.conv3[0], spm.conv4[0]]
     for i, c in enumerate(convs):
@@ -222,10 +254,26 @@ def _cbr(conv_mod, norm, x):
     return _BNRelu.apply(y, norm.weight, norm.bias, norm, True)
 
 
-def forward(spm, x, level_embed):
-    """-> (c1, c): c1 = fc1's output WITHOUT its bias as NCHW bf16 planes (the caller folds the bias into the
-    BatchNorm tail), c = cat([fc_l(c_l) + level_embed[l-2] for l = 2, 3, 4]) as (B, T, E) fp32 token rows."""
-    t = image_to_nhwc16(x)
+def _fc1_planes_f16(fc1, c1, with_bias):
+    """fc1 (1x1 convolution) of the NHWC fp16 map c1 as NCHW fp16 planes: out[b] (Co x HW) = W (Co x Ci) x[b]^T, one
+    batched library GEMM on the token rows (no layout copy of the activations), plain autograd."""
+    B, H, W, Ci = c1.shape
+    Co = fc1.weight.shape[0]
+    w = fc1.weight.view(1, Co, Ci).expand(B, Co, Ci)
+    rows_t = c1.view(B, H * W, Ci).transpose(1, 2)
+    if with_bias and fc1.bias is not None:
+        out = torch.baddbmm(fc1.bias.view(1, Co, 1), w, rows_t)
+    else:
+        out = torch.bmm(w, rows_t)
+    return out.view(B, Co, H, W)
+
+
+def forward(spm, x, level_embed, c1_bias=False):
+    """-> (c1, c): c1 = fc1's output as NCHW 16-bit planes, WITHOUT its bias unless ``c1_bias`` (bf16: the caller folds
+    the bias into the BatchNorm tail; fp16: the tail is torch's and the caller asks for the bias),
+    c = cat([fc_l(c_l) + level_embed[l-2] for l = 2, 3, 4]) as (B, T, E) fp32 token rows."""
+    dtype = autocast_dtype() or torch.bfloat16
+    t = image_to_nhwc16(x, dtype)
     t = _cbr(spm.stem[0], spm.stem[1], t)
     t = _cbr(spm.stem[3], spm.stem[4], t)
     t = _cbr(spm.stem[6], spm.stem[7], t)
@@ -235,6 +283,13 @@ def forward(spm, x, level_embed):
     c4 = _cbr(spm.conv4[0], spm.conv4[1], c3)
     B = x.shape[0]
     toks = []
+    if dtype == torch.float16:
+        # the 1x1 projections are GEMMs: torch's fp16 library calls on the NHWC rows, as every Linear in this mode
+        for l, (fc, c) in enumerate(((spm.fc2, c2), (spm.fc3, c3), (spm.fc4, c4))):
+            w = fc.weight.view(fc.weight.shape[0], fc.weight.shape[1])
+            toks.append(F.linear(c.view(B, -1, c.shape[-1]), w, fc.bias + level_embed[l]))
+        return _fc1_planes_f16(spm.fc1, c1, c1_bias), torch.cat(toks, dim=1).float()
+    assert not c1_bias, 'bf16: fc1.bias travels to the BatchNorm tail'
     for l, (fc, c) in enumerate(((spm.fc2, c2), (spm.fc3, c3), (spm.fc4, c4))):
         w = fc.weight.view(fc.weight.shape[0], fc.weight.shape[1])
         toks.append(fused._LinearBF16.apply(c.view(B, -1, c.shape[-1]), w, fc.bias + level_embed[l]))
