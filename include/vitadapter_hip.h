@@ -138,6 +138,9 @@ int vah_msda_fused_backward(const void *value, int value_dtype, const int64_t *s
  *                   deform inputs): only the forward kernel runs.  The forward kernel does not write to ws.
  * A workgroup walks (n, group, head) items: it stages the window once, then one lane per query evaluates its four
  * samples against it (replaces ms_deform_im2col_cuda.cuh:237-299 + the module's softmax / location lines).
+ * out (N, Lq, M*32) is fully written by every call that returns VAH_OK: if the level is no valid window of the S value
+ * rows (level guard above: H < 1, W < 1, start < 0, start + H*W > S) the schedule is empty and the forward kernel
+ * writes zeros, as vah_msda_fused_forward does - with ws_holds_schedule = 1 on such a schedule as well.
  * ------------------------------------------------------------------------------------ */
 int64_t vah_msda_win_ws_bytes(int64_t S, int64_t Lq);      /* < 0: not supported (Lq > 2^18) */
 int vah_msda_fused_forward_win(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,

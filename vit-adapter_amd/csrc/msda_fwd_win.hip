@@ -230,6 +230,15 @@ __global__ __launch_bounds__(kWinThreads) void msda_fused_fwd_win(
     const int *group_off = reinterpret_cast<const int *>(ws + sizeof(WinHeader));
     const int *perm = group_off + Gmax + 1 + Gmax;
     const int H = hd.H, W = hd.W, G = hd.G;
+    if (!hd.valid) {
+        // the level is no window of the value rows: it contributes nothing, and out is still fully written (as
+        // msda_fused_fwd does).  Rows are 64 / 128 bytes: whole 16-byte words.
+        uint4 *o = reinterpret_cast<uint4 *>(out);
+        const int64_t words = (int64_t)N * Lq * M * (ROWB / 16);
+        for (int64_t i = (int64_t)blockIdx.x * kWinThreads + threadIdx.x; i < words; i += (int64_t)gridDim.x * kWinThreads)
+            o[i] = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
     const int64_t start = hd.start;
     const int64_t items = (int64_t)N * G * M;
     // work items (n, group, head), heads of a group adjacent; XCD b % 8 walks a contiguous eighth
