@@ -351,6 +351,29 @@ int vah_colsum_bf16(const void *g_bf16, int64_t rows, int64_t C, float *out, flo
 /* Only the partial rows (ws: vah_reduce_ws_floats(C), *nparts rows of C floats), for a consumer that sums them
  * itself: vah_gemm_bf16_fin does it on its last launch. */
 int vah_colsum_bf16_partials(const void *g_bf16, int64_t rows, int64_t C, float *ws, int64_t *nparts, void *stream);
+/* Bias gradients from the kernels that write dY (bf16 only, like Linear): the row-streaming backward kernels below
+ * produce the dY of an nn.Linear, and carry the partial rows of dY's column sums in the same pass, so the Linear's
+ * backward hands them to vah_gemm_bf16_fin and launches no column-sum kernel.
+ *   bpart   caller-owned, vah_reduce_ws_floats(C) floats; on return rows [0, *nparts) are fully written (row stride
+ *           C), *nparts <= 512, and 0 when there are no rows
+ * What is summed is each dY element after its rounding to bf16 - the term vah_colsum_bf16_partials adds; only the
+ * order of the summation differs.  All other outputs are bit-identical to the entry point without `_bsum`.
+ *   vah_residual_layernorm_bwd_bsum   without a layer scale only (gamma != NULL: VAH_E_SHAPE); ws K = 3C as before,
+ *                                     z is not read
+ *   vah_scale_residual_bwd_bsum       with or without gamma / s (never the flat no-gamma pass: it has no columns to sum
+ *                                     over); ws (K = C) only for dgamma
+ *   vah_gelu_bwd_bsum_bf16            dh = bf16(da * (Phi(h) + h * phi(h))), exact (erf) GELU evaluated in fp32 from the
+ *                                     bf16 operands as torch's GeluBackward does; da, h, dh (rows, C), C % 8 == 0 */
+int vah_residual_layernorm_bwd_bsum(const float *t, const void *gh_bf16, const float *w, const float *mean,
+                                    const float *rstd, const float *gt, const void *z_bf16, const float *gamma,
+                                    const float *sc, int64_t batch, int64_t rows_per_batch, int64_t C, float *dt,
+                                    void *dz_bf16, float *dgamma, float *dw, float *db, float *ws, float *bpart,
+                                    int64_t *nparts, void *stream);
+int vah_scale_residual_bwd_bsum(const float *g, const void *z_bf16, const float *gamma, const float *s,
+                                int64_t batch, int64_t rows_per_batch, int64_t C, void *dz_bf16, float *dgamma,
+                                float *ws, float *bpart, int64_t *nparts, void *stream);
+int vah_gelu_bwd_bsum_bf16(const void *da_bf16, const void *h_bf16, int64_t rows, int64_t C, void *dh_bf16,
+                           float *bpart, int64_t *nparts, void *stream);
 /* fp32, over `batch` row blocks of a strided tensor: out[c] = sum_{b, r < rows} g[b * batch_stride + r * C + c]
  * (the gradient of a per-channel vector added to a token range of a (B, T, C) tensor); C % 4 == 0. */
 int vah_colsum_f32(const float *g, int64_t batch, int64_t batch_stride, int64_t rows, int64_t C, float *out,

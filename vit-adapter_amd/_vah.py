@@ -105,6 +105,12 @@ lib.vah_gemm_bf16.argtypes = [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, 
 lib.vah_gemm_bf16_fin.argtypes = [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _int, _p, _i64, _p, _i64, _i64,
                                   _p, _p]
 lib.vah_colsum_bf16_partials.argtypes = [_p, _i64, _i64, _p, ctypes.POINTER(_i64), _p]
+# the producers of a Linear's dY that carry its bias-gradient partials (bf16 only: no _f16 twins)
+lib.vah_residual_layernorm_bwd_bsum.argtypes = [_p] * 9 + [_i64] * 3 + [_p] * 6 + [_p, ctypes.POINTER(_i64), _p]
+lib.vah_scale_residual_bwd_bsum.argtypes = [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, ctypes.POINTER(_i64), _p]
+lib.vah_gelu_bwd_bsum_bf16.argtypes = [_p, _p, _i64, _i64, _p, _p, ctypes.POINTER(_i64), _p]
+for _n in ('vah_residual_layernorm_bwd_bsum', 'vah_scale_residual_bwd_bsum', 'vah_gelu_bwd_bsum_bf16'):
+    getattr(lib, _n).restype = ctypes.c_int
 lib.vah_gemm_table_dump.argtypes = [ctypes.c_char_p, _i64]
 lib.vah_gemm_table_dump.restype = _i64
 lib.vah_gemm_table_load.argtypes = [ctypes.c_char_p]
@@ -204,6 +210,7 @@ EXPORTS = (
     'vah_layernorm_fwd_f32_f16', 'vah_layernorm_bwd_f32_f16', 'vah_residual_layernorm_fwd_f16', 'vah_residual_layernorm_bwd_f16',
     'vah_layernorm_dual_fwd_f16', 'vah_layernorm_dual_bwd_f16', 'vah_scale_residual_fwd_f16', 'vah_scale_residual_bwd_f16',
     'vah_dwconv3x3_tokens_f16', 'vah_dwconv3x3_tokens_wgrad_f16',
+    'vah_residual_layernorm_bwd_bsum', 'vah_scale_residual_bwd_bsum', 'vah_gelu_bwd_bsum_bf16',
     'vah_gemm_set_tuning', 'vah_gemm_bf16', 'vah_gemm_bf16_fin', 'vah_colsum_bf16_partials', 'vah_gemm_table_dump', 'vah_gemm_table_load', 'vah_gemm_library_version', 'vah_gemm_rejected_candidates',
     'vah_bn_tail_ws_floats', 'vah_bn_tail_supported', 'vah_bn_tail_stats', 'vah_bn_tail_apply', 'vah_bn_tail_bwd_stats', 'vah_bn_tail_bwd_apply',
     'vah_bn_finalize_stats', 'vah_transpose_tokens', 'vah_maxpool3s2_fwd_bf16', 'vah_maxpool3s2_bwd_bf16',

@@ -187,7 +187,12 @@ __global__ __launch_bounds__(256) void finalize_partials(const float *__restrict
 // 512-workgroup grid ran as two back-to-back rounds, each a full load -> reduce -> store latency
 // chain).  The accumulators now live in the wave's own LDS row (plain read-add-write, no atomics:
 // nobody else touches it; ~100 LDS clocks per row) and the weights are read from LDS where used.
-template <typename T, int kMaxVec, int kWaves, bool kRes, int kFly>
+//
+// kBsum (with kRes and no gamma only): dz is the gradient a Linear reads next, and its bias gradient is the column
+// sum of dz.  Without a gamma the third LDS column would hold a dgamma nobody reads; it sums the rounded dz
+// instead and goes out as one row of `bpart` (stride C), the rows [dw | db] of `part` then have stride 2C.  z is
+// not read at all in this form.
+template <typename T, int kMaxVec, int kWaves, bool kRes, int kFly, bool kBsum = false>
 __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__restrict__ x,
                                                      const T *__restrict__ g,
                                                      const float *__restrict__ w,
@@ -195,7 +200,9 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
                                                      const float *__restrict__ rstd,
                                                      const float *__restrict__ gres, int64_t rows, int C,
                                                      ResidualIn<T> res, T *__restrict__ dz,
-                                                     float *__restrict__ dx, float *__restrict__ part) {
+                                                     float *__restrict__ dx, float *__restrict__ part,
+                                                     float *__restrict__ bpart = nullptr) {
+    static_assert(kRes || !kBsum, "the bias partials ride on the residual form");
     constexpr int ncol = kRes ? 3 : 2;       // kRes: res.z != nullptr (compile time: its registers)
     extern __shared__ __attribute__((aligned(16))) float s_red[];      // [kWaves][ncol * C] | w[C] | gamma[C]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -235,7 +242,7 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
                     gv[u][j] = *reinterpret_cast<const vec4<T> *>(g + rws[u] * C + 4 * i);
                     rv[u][j] = gres ? *reinterpret_cast<const float4 *>(gres + rws[u] * C + 4 * i)
                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (kRes) zv[u][j] = *reinterpret_cast<const vec4<T> *>(res.z + rws[u] * C + 4 * i);
+                    if constexpr (kRes && !kBsum) zv[u][j] = *reinterpret_cast<const vec4<T> *>(res.z + rws[u] * C + 4 * i);
                 }
             }
         }
@@ -294,10 +301,17 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
                         *reinterpret_cast<vec4<T> *>(dz + rws[u] * C + 4 * i) = o;
                         float4 *pg = reinterpret_cast<float4 *>(acc + 2 * C + 4 * i);
                         float4 ag = *pg;
-                        ag.x += sb[u] * d.x * (float)zv[u][j][0];
-                        ag.y += sb[u] * d.y * (float)zv[u][j][1];
-                        ag.z += sb[u] * d.z * (float)zv[u][j][2];
-                        ag.w += sb[u] * d.w * (float)zv[u][j][3];
+                        if constexpr (kBsum) {            // the bias gradient's term: dz as the Linear will read it
+                            ag.x += (float)o[0];
+                            ag.y += (float)o[1];
+                            ag.z += (float)o[2];
+                            ag.w += (float)o[3];
+                        } else {
+                            ag.x += sb[u] * d.x * (float)zv[u][j][0];
+                            ag.y += sb[u] * d.y * (float)zv[u][j][1];
+                            ag.z += sb[u] * d.z * (float)zv[u][j][2];
+                            ag.w += sb[u] * d.w * (float)zv[u][j][3];
+                        }
                         *pg = ag;
                     }
                 }
@@ -306,12 +320,13 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
     }
     __syncthreads();
     const int K = ncol * C;
-    float *pr = part + (int64_t)blockIdx.x * K;
+    float *pr = part + (int64_t)blockIdx.x * (kBsum ? 2 * C : K);
     for (int k = threadIdx.x; k < K; k += 64 * kWaves) {
         float t = 0.f;
 #pragma unroll
         for (int u = 0; u < kWaves; ++u) t += s_red[u * K + k];
-        pr[k] = t;
+        if (kBsum && k >= 2 * C) bpart[(int64_t)blockIdx.x * C + (k - 2 * C)] = t;
+        else pr[k] = t;
     }
 }
 
@@ -590,12 +605,15 @@ __global__ __launch_bounds__(256) void scale_residual_fwd_kernel(
 // (1 KB of a row), the 4 waves of a workgroup take every 4th row of the strip with 4 rows in flight
 // each (a thread-per-column-group walk with one row in flight ran at 1.5 TB/s); dgamma partials stay
 // in registers and are summed over the 4 waves through LDS.
-template <typename T>
+// kBsum: a second register accumulator sums the rounded dz (the bias gradient of the Linear that made z), reduced
+// like the first into row blockIdx.x of `bpart`; kDg = false (no gamma: no dgamma) leaves z unread.
+template <typename T, bool kBsum = false, bool kDg = true>
 __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
     const float *__restrict__ g, const T *__restrict__ z, const float *__restrict__ gamma,
     const float *__restrict__ s, int64_t rows, int64_t rows_per_batch, int C, int rows_per_block,
-    T *__restrict__ dz, float *__restrict__ part) {
+    T *__restrict__ dz, float *__restrict__ part, float *__restrict__ bpart = nullptr) {
     __shared__ float4 s_acc[4][64];
+    __shared__ float4 s_bacc[kBsum ? 4 : 1][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nvec = C >> 2;
     const int64_t row0 = (int64_t)blockIdx.x * rows_per_block;
@@ -605,7 +623,7 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
         const bool on = cv < nvec;
         float4 gm = make_float4(1.f, 1.f, 1.f, 1.f);
         if (gamma && on) gm = *reinterpret_cast<const float4 *>(gamma + 4 * cv);
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), bacc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int64_t r = row0 + wv; r < row1; r += 16) {
             float4 gv[4];
             vec4<T> zv[4];
@@ -618,7 +636,7 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
                 if (ok[u]) {
                     const int64_t off = rr * C + 4 * cv;
                     gv[u] = *reinterpret_cast<const float4 *>(g + off);
-                    zv[u] = *reinterpret_cast<const vec4<T> *>(z + off);
+                    if constexpr (kDg) zv[u] = *reinterpret_cast<const vec4<T> *>(z + off);
                     sb[u] = s ? s[rr / rows_per_batch] : 1.f;
                 }
             }
@@ -632,13 +650,38 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
                 o[2] = (T)(sb[u] * gm.z * gv[u].z);
                 o[3] = (T)(sb[u] * gm.w * gv[u].w);
                 *reinterpret_cast<vec4<T> *>(dz + off) = o;
-                acc.x += sb[u] * gv[u].x * (float)zv[u][0];
-                acc.y += sb[u] * gv[u].y * (float)zv[u][1];
-                acc.z += sb[u] * gv[u].z * (float)zv[u][2];
-                acc.w += sb[u] * gv[u].w * (float)zv[u][3];
+                if constexpr (kDg) {
+                    acc.x += sb[u] * gv[u].x * (float)zv[u][0];
+                    acc.y += sb[u] * gv[u].y * (float)zv[u][1];
+                    acc.z += sb[u] * gv[u].z * (float)zv[u][2];
+                    acc.w += sb[u] * gv[u].w * (float)zv[u][3];
+                }
+                if constexpr (kBsum) {
+                    bacc.x += (float)o[0];
+                    bacc.y += (float)o[1];
+                    bacc.z += (float)o[2];
+                    bacc.w += (float)o[3];
+                }
             }
         }
-        if (part) {
+        if constexpr (kBsum) {
+            if constexpr (kDg) s_acc[wv][lane] = acc;
+            s_bacc[wv][lane] = bacc;
+            __syncthreads();
+            if (wv == 0 && on && kDg && part) {
+                const float4 a = s_acc[0][lane], b = s_acc[1][lane], c = s_acc[2][lane], d = s_acc[3][lane];
+                *reinterpret_cast<float4 *>(part + (int64_t)blockIdx.x * C + 4 * cv) =
+                    make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z),
+                                (a.w + b.w) + (c.w + d.w));
+            }
+            if (wv == 1 && on) {
+                const float4 a = s_bacc[0][lane], b = s_bacc[1][lane], c = s_bacc[2][lane], d = s_bacc[3][lane];
+                *reinterpret_cast<float4 *>(bpart + (int64_t)blockIdx.x * C + 4 * cv) =
+                    make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z),
+                                (a.w + b.w) + (c.w + d.w));
+            }
+            __syncthreads();
+        } else if (part) {
             s_acc[wv][lane] = acc;
             __syncthreads();
             if (wv == 0 && on) {
@@ -855,10 +898,10 @@ int residual_ln_fwd(const char *fn, const float *x, const void *z, const float *
                             stream);
 }
 
-template <typename T>
+template <typename T, bool kBsumT = false>
 int ln_bwd_launch(const char *fn, const float *x, const void *g, const float *w, const float *mean, const float *rstd,
                   const float *gres, int64_t rows, int64_t C, ResidualIn<T> res, void *dz, float *dx, float *dw, float *db,
-                  float *dgamma, float *ws, void *stream) {
+                  float *dgamma, float *ws, void *stream, float *bpart = nullptr, int64_t *nparts = nullptr) {
     clear_error();
     if (rows < 0 || C < 4 || C % 4 || C > 64 * 4 * kMaxVecAll) return fail(VAH_E_SHAPE, "%s: C=%lld unsupported", fn, (long long)C);
     if (!dw || !db || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
@@ -867,11 +910,13 @@ int ln_bwd_launch(const char *fn, const float *x, const void *g, const float *w,
         (void)hipMemsetAsync(dw, 0, C * 4, st);
         (void)hipMemsetAsync(db, 0, C * 4, st);
         if (dgamma) (void)hipMemsetAsync(dgamma, 0, C * 4, st);
+        if (nparts) *nparts = 0;
         return VAH_OK;
     }
     if (!x || !g || !w || !mean || !rstd || !dx) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)dx | (uintptr_t)gres) % 16 || (uintptr_t)g % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
     const int ncol = res.z ? 3 : 2;
+    const bool bsum = bpart != nullptr;          // residual form without gamma (checked by the entry point)
     // 8 waves per workgroup when their LDS reduction buffer leaves room for two workgroups per CU:
     // the partial-row cap bounds the grid at 512 workgroups, and with 4 waves each that is 2 waves per
     // SIMD - too few to cover the latency of this kernel's load -> reduce -> store chain
@@ -885,20 +930,24 @@ int ln_bwd_launch(const char *fn, const float *x, const void *g, const float *w,
                       rows * C * (res.z ? 18 : 10), st);
     if (smem > 150 * 1024) return fail(VAH_E_SHAPE, "%s: C too large for the fused form", fn);
     constexpr int kLnFly = VAH_LN_FLY;
-#define VAH_LN_BWD(NV, WV, RS)                                                                     \
+#define VAH_LN_BWD(NV, WV, RS, BS)                                                                 \
     do {                                                                                         \
         if (smem > 64 * 1024)                                                                    \
-            (void)hipFuncSetAttribute((const void *)ln_bwd_kernel<T, NV, WV, RS, kLnFly>,                \
+            (void)hipFuncSetAttribute((const void *)ln_bwd_kernel<T, NV, WV, RS, kLnFly, BS>,            \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);    \
-        hipLaunchKernelGGL((ln_bwd_kernel<T, NV, WV, RS, kLnFly>), dim3((unsigned)nblocks), dim3(64 * WV), smem, st, x, \
-                           (const T *)g, w, mean, rstd, gres, rows, (int)C, res, (T *)dz, dx, ws); \
+        hipLaunchKernelGGL((ln_bwd_kernel<T, NV, WV, RS, kLnFly, BS>), dim3((unsigned)nblocks), dim3(64 * WV), smem, st, x, \
+                           (const T *)g, w, mean, rstd, gres, rows, (int)C, res, (T *)dz, dx, ws, bpart); \
     } while (0)
 #define VAH_LN_BWD_W(NV)        \
     do {                        \
-        if (waves == 8 && res.z) VAH_LN_BWD(NV, 8, true); \
-        else if (waves == 8) VAH_LN_BWD(NV, 8, false); \
-        else if (res.z) VAH_LN_BWD(NV, 4, true); \
-        else VAH_LN_BWD(NV, 4, false); \
+        if constexpr (kBsumT) {                               \
+            if (bsum && waves == 8) { VAH_LN_BWD(NV, 8, true, true); break; }  \
+            if (bsum) { VAH_LN_BWD(NV, 4, true, true); break; }                \
+        }                                                     \
+        if (waves == 8 && res.z) VAH_LN_BWD(NV, 8, true, false); \
+        else if (waves == 8) VAH_LN_BWD(NV, 8, false, false); \
+        else if (res.z) VAH_LN_BWD(NV, 4, true, false); \
+        else VAH_LN_BWD(NV, 4, false, false); \
     } while (0)
     if (C <= 256) VAH_LN_BWD_W(1);
     else if (C <= 512) VAH_LN_BWD_W(2);
@@ -907,28 +956,37 @@ int ln_bwd_launch(const char *fn, const float *x, const void *g, const float *w,
     else VAH_LN_BWD_W(8);
 #undef VAH_LN_BWD_W
 #undef VAH_LN_BWD
-    // partial row = [dw | db | dgamma]
-    hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((ncol * C + 31) / 32)), dim3(256), 0, st, ws,
-                       (int)nblocks, (int)(ncol * C), dw, (int)C, db, (int)C, dgamma);
+    // partial row = [dw | db | dgamma], or [dw | db] beside the bias partials
+    const int fcol = bsum ? 2 : ncol;
+    hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((fcol * C + 31) / 32)), dim3(256), 0, st, ws,
+                       (int)nblocks, (int)(fcol * C), dw, (int)C, db, (int)C, dgamma);
+    if (nparts) *nparts = nblocks;
     return check_launch(fn);
 }
 
 // Backward of residual_ln_fwd: dt = gt + LayerNorm'(gh) (the gradient of x as well), dz = sc * gamma * dt (T),
 // dgamma = sum sc * dt * z, dw, db.  gt (gradient of t along the residual stream) and gamma / sc / dgamma
 // optional.  ws: vah_reduce_ws_floats(3*C).
-template <typename T>
+// kBsum: also the partial rows of the column sums of dz (the bias gradient of the Linear that made z) - *nparts rows
+// of C floats in bpart (vah_reduce_ws_floats(C)); without a gamma only.
+template <typename T, bool kBsum = false>
 int residual_ln_bwd(const char *fn, const float *t, const void *gh, const float *w, const float *mean, const float *rstd,
                     const float *gt, const void *z, const float *gamma, const float *sc, int64_t batch,
                     int64_t rows_per_batch, int64_t C, float *dt, void *dz, float *dgamma, float *dw, float *db, float *ws,
-                    void *stream) {
+                    void *stream, float *bpart = nullptr, int64_t *nparts = nullptr) {
     clear_error();
     if (batch < 0 || rows_per_batch < 0) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (batch * rows_per_batch > 0 && (!z || !dz)) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if ((gamma != nullptr) != (dgamma != nullptr)) return fail(VAH_E_NULL, "%s: gamma and dgamma go together", fn);
     if ((uintptr_t)gamma % 16 || ((uintptr_t)z | (uintptr_t)dz) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    return ln_bwd_launch<T>(fn, t, gh, w, mean, rstd, gt, batch * rows_per_batch, C,
-                            ResidualIn<T>{(const T *)z, gamma, sc, std::max<int64_t>(rows_per_batch, 1), nullptr}, dz, dt, dw,
-                            db, dgamma, ws, stream);
+    if constexpr (kBsum) {
+        if (gamma) return fail(VAH_E_SHAPE, "%s: bias partials are not carried beside a layer scale (gamma)", fn);
+        if (!bpart || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
+        if ((uintptr_t)bpart % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    }
+    return ln_bwd_launch<T, kBsum>(fn, t, gh, w, mean, rstd, gt, batch * rows_per_batch, C,
+                                   ResidualIn<T>{(const T *)z, gamma, sc, std::max<int64_t>(rows_per_batch, 1), nullptr}, dz,
+                                   dt, dw, db, dgamma, ws, stream, bpart, nparts);
 }
 
 // Two LayerNorms of the same fp32 rows (shared statistics, equal eps): ya, yb of type T.
@@ -1035,6 +1093,170 @@ int scale_residual_bwd(const char *fn, const float *g, const void *z, const floa
         hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, ws,
                            (int)nblocks, (int)C, dgamma, (int)C, (float *)nullptr, 1 << 30, (float *)nullptr);
     return check_launch(fn);
+}
+
+// dz = s[b] * g (no layer scale) with the column sums of the rounded dz: the flat scale_only pass has no column
+// structure to carry a sum, and the row-strip kernel above (a wave per 1 KB of a row, column groups one after the
+// other) streams at half its rate when there is no dgamma to reduce (measured 77 vs 35 us at 43008 x 768).  The
+// tiling of colsum_bf16_kernel instead: 32 column lanes x 8 columns x 8 row lanes over a strip of rows, 4 rows
+// (8 x 16 bytes of g per thread) requested before the first is used, one partial row per workgroup.
+// rows_per_block % 32 == 0, so only the last strip has dead slots (clamped loads, results unused).
+__global__ __launch_bounds__(256) void scale_bsum_bwd_kernel(const float *__restrict__ g, const float *__restrict__ s,
+                                                             unsigned rows, unsigned rows_per_batch, int C,
+                                                             int rows_per_block, __bf16 *__restrict__ dz,
+                                                             float *__restrict__ bpart) {
+    __shared__ float s_acc[8][256 + 8];
+    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const int c0 = blockIdx.x * 256 + cl * 8;
+    const unsigned r0 = blockIdx.y * (unsigned)rows_per_block;
+    const unsigned r1 = min(rows, r0 + (unsigned)rows_per_block);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c0 < C) {
+        for (unsigned r = r0 + rl; r < r1; r += 32) {
+            float4 lo[4], hi[4];
+            float sb[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const unsigned rr = min(r + 8 * u, r1 - 1);
+                const float *gp = g + (int64_t)rr * C + c0;
+                lo[u] = *reinterpret_cast<const float4 *>(gp);
+                hi[u] = *reinterpret_cast<const float4 *>(gp + 4);
+                sb[u] = s ? s[rr / rows_per_batch] : 1.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (r + 8 * u >= r1) break;
+                bf16x8 o;
+                o[0] = (__bf16)(sb[u] * lo[u].x);
+                o[1] = (__bf16)(sb[u] * lo[u].y);
+                o[2] = (__bf16)(sb[u] * lo[u].z);
+                o[3] = (__bf16)(sb[u] * lo[u].w);
+                o[4] = (__bf16)(sb[u] * hi[u].x);
+                o[5] = (__bf16)(sb[u] * hi[u].y);
+                o[6] = (__bf16)(sb[u] * hi[u].z);
+                o[7] = (__bf16)(sb[u] * hi[u].w);
+                *reinterpret_cast<bf16x8 *>(dz + (int64_t)(r + 8 * u) * C + c0) = o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += (float)o[e];
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s_acc[rl][cl * 8 + e] = acc[e];
+    __syncthreads();
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) {
+        float t = 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t += s_acc[u][threadIdx.x];
+        bpart[(int64_t)blockIdx.y * C + c] = t;
+    }
+}
+
+// strips of a multiple of 32 rows (the 8 row lanes x 4 rows in flight of the column-tiled kernels), at most kMaxParts
+inline void strips_of_32(int64_t rows, int64_t *rpb, int64_t *parts) {
+    *rpb = std::max<int64_t>(32, ((rows + kMaxParts - 1) / kMaxParts + 31) / 32 * 32);
+    *parts = (rows + *rpb - 1) / *rpb;
+}
+
+// scale_residual_bwd plus the partial rows of the column sums of dz (*nparts = the launch's workgroups along the
+// rows): with a gamma the row-strip kernel with a second accumulator, without one the column-tiled kernel above
+// (the strip kernel where that one does not apply: C % 8 != 0 or 2^31 rows).  bpart: vah_reduce_ws_floats(C).
+inline int scale_residual_bwd_bsum(const char *fn, const float *g, const void *z, const float *gamma, const float *s,
+                                   int64_t batch, int64_t rows_per_batch, int64_t C, void *dz, float *dgamma, float *ws,
+                                   float *bpart, int64_t *nparts, void *stream) {
+    typedef __bf16 T;
+    clear_error();
+    if (batch < 0 || rows_per_batch < 0 || C < 4 || C % 4) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (!bpart || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    const int64_t rows = batch * rows_per_batch;
+    hipStream_t st = (hipStream_t)stream;
+    if (rows == 0) {
+        if (dgamma) (void)hipMemsetAsync(dgamma, 0, C * 4, st);
+        *nparts = 0;
+        return VAH_OK;
+    }
+    if (!g || !z || !dz || (dgamma && !ws)) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)g | (uintptr_t)gamma | (uintptr_t)bpart) % 16 || ((uintptr_t)z | (uintptr_t)dz) % 8)
+        return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    LaunchScope scope("scale_residual_bwd", rows * C * 8, st);
+    const bool dg = gamma && dgamma;
+    if (!gamma && C % 8 == 0 && rows < ((int64_t)1 << 31)) {
+        int64_t srows, parts;
+        strips_of_32(rows, &srows, &parts);
+        hipLaunchKernelGGL(scale_bsum_bwd_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)parts), dim3(256), 0, st, g, s,
+                           (unsigned)rows, (unsigned)std::max<int64_t>(rows_per_batch, 1), (int)C, (int)srows, (T *)dz, bpart);
+        *nparts = parts;
+        return check_launch(fn);
+    }
+    const int rpb = (int)((rows + kMaxParts - 1) / kMaxParts);
+    const int64_t nblocks = (rows + rpb - 1) / rpb;
+    if (dg)
+        hipLaunchKernelGGL((scale_residual_bwd_kernel<T, true, true>), dim3((unsigned)nblocks), dim3(256), 0, st, g,
+                           (const T *)z, gamma, s, rows, rows_per_batch, (int)C, rpb, (T *)dz, ws, bpart);
+    else
+        hipLaunchKernelGGL((scale_residual_bwd_kernel<T, true, false>), dim3((unsigned)nblocks), dim3(256), 0, st, g,
+                           (const T *)z, gamma, s, rows, rows_per_batch, (int)C, rpb, (T *)dz, (float *)nullptr, bpart);
+    if (dg)
+        hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, ws,
+                           (int)nblocks, (int)C, dgamma, (int)C, (float *)nullptr, 1 << 30, (float *)nullptr);
+    *nparts = nblocks;
+    return check_launch(fn);
+}
+
+// ---------------------------------------------------------------------------------------
+// GELU backward (exact, erf) of a bf16 [rows, C] matrix with the column sums of its result: the gradient of
+// trunk mlp.fc1's output.  dh = bf16(da * (Phi(h) + h * phi(h))), fp32 math from the bf16 operands in the
+// operation order of torch's GeluBackward kernel (so the two agree to the bit wherever erff / expf do).
+// The tiling of colsum_bf16_kernel: 32 column lanes x 8 bf16 x 8 row lanes over a strip of rows; the loads of
+// 4 rows are requested before the math of the first.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gelu_bwd_bsum_kernel(const __bf16 *__restrict__ da, const __bf16 *__restrict__ h,
+                                                            int64_t rows, int C, int rows_per_block,
+                                                            __bf16 *__restrict__ dh, float *__restrict__ part) {
+    __shared__ float s_acc[8][256 + 8];
+    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const int c0 = blockIdx.x * 256 + cl * 8;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
+    const int64_t r1 = min(rows, r0 + rows_per_block);
+    constexpr float kAlpha = (float)0.70710678118654752440;                              // sqrt(1/2)
+    constexpr float kBeta = (float)(1.12837916709551257390 * 0.70710678118654752440 * 0.5);   // 1 / sqrt(2 pi)
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c0 < C) {
+        for (int64_t r = r0 + rl; r < r1; r += 32) {
+            bf16x8 av[4], hv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t rr = min(r + 8 * u, r1 - 1);          // clamped: a dead slot re-reads a live row
+                av[u] = *reinterpret_cast<const bf16x8 *>(da + rr * C + c0);
+                hv[u] = *reinterpret_cast<const bf16x8 *>(h + rr * C + c0);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (r + 8 * u >= r1) break;
+                bf16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float x = (float)hv[u][e];
+                    const float cdf = 0.5f * (1.f + erff(x * kAlpha));
+                    const float pdf = expf(-0.5f * x * x) * kBeta;
+                    o[e] = (__bf16)((float)av[u][e] * (cdf + x * pdf));
+                    acc[e] += (float)o[e];
+                }
+                *reinterpret_cast<bf16x8 *>(dh + (r + 8 * u) * C + c0) = o;
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s_acc[rl][cl * 8 + e] = acc[e];
+    __syncthreads();
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) {
+        float t = 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t += s_acc[u][threadIdx.x];
+        part[(int64_t)blockIdx.y * C + c] = t;
+    }
 }
 
 // token ranges and sizes of the (2H,2W), (H,W), (H/2,W/2) maps of a (B, 21n, C) token tensor
@@ -1199,6 +1421,52 @@ VAH_ENTRY_PAIR(VAH_DWCONV_ENTRY, vah_dwconv3x3_tokens_bf16, vah_dwconv3x3_tokens
 VAH_ENTRY_PAIR(VAH_DWCONV_WGRAD_ENTRY, vah_dwconv3x3_tokens_wgrad_bf16, vah_dwconv3x3_tokens_wgrad_f16)
 
 #undef VAH_ENTRY_PAIR
+
+// The row-streaming backward kernels that write the dY of a Linear, carrying the partial rows of dY's column sums
+// (that Linear's bias gradient) in the same pass: bpart (caller-owned, vah_reduce_ws_floats(C) floats) gets *nparts
+// <= 512 rows of C floats, for the finalize job of vah_gemm_bf16_fin.  Summed is every dY element after its rounding
+// to bf16 - the term vah_colsum_bf16_partials adds.  Every other output is that of the entry point without _bsum.
+int vah_residual_layernorm_bwd_bsum(const float *t, const void *gh, const float *w, const float *mean, const float *rstd,
+                                    const float *gt, const void *z, const float *gamma, const float *sc, int64_t batch,
+                                    int64_t rows_per_batch, int64_t C, float *dt, void *dz, float *dgamma, float *dw,
+                                    float *db, float *ws, float *bpart, int64_t *nparts, void *stream) {
+    return vah::residual_ln_bwd<__bf16, true>("vah_residual_layernorm_bwd_bsum", t, gh, w, mean, rstd, gt, z, gamma, sc,
+                                              batch, rows_per_batch, C, dt, dz, dgamma, dw, db, ws, stream, bpart, nparts);
+}
+
+int vah_scale_residual_bwd_bsum(const float *g, const void *z, const float *gamma, const float *s, int64_t batch,
+                                int64_t rows_per_batch, int64_t C, void *dz, float *dgamma, float *ws, float *bpart,
+                                int64_t *nparts, void *stream) {
+    return vah::scale_residual_bwd_bsum("vah_scale_residual_bwd_bsum", g, z, gamma, s, batch, rows_per_batch, C, dz,
+                                        dgamma, ws, bpart, nparts, stream);
+}
+
+int vah_gelu_bwd_bsum_bf16(const void *da, const void *h, int64_t rows, int64_t C, void *dh, float *bpart,
+                           int64_t *nparts, void *stream) {
+    using namespace vah;
+    clear_error();
+    const char *fn = "vah_gelu_bwd_bsum_bf16";
+    if (rows < 0 || C < 8 || C % 8 || C > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (!bpart || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (rows == 0) {
+        *nparts = 0;
+        return VAH_OK;
+    }
+    if (!da || !h || !dh) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)da | (uintptr_t)h | (uintptr_t)dh) % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    const int ctiles = (int)((C + 255) / 256);
+    // colsum_bf16's tiling, not its strip rule: that one sizes strips to 2048 workgroups whatever the row count
+    // (8192 x 3072: 49 rows, 6.1 per row lane = a second, ragged batch of loads), which costs a kernel with this
+    // much math per element a quarter of its rate; strips of 32 rows are whole batches
+    int64_t parts, rpb;
+    strips_of_32(rows, &rpb, &parts);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope("gelu_bwd", rows * C * 6, st);
+    hipLaunchKernelGGL(gelu_bwd_bsum_kernel, dim3((unsigned)ctiles, (unsigned)parts), dim3(256), 0, st, (const __bf16 *)da,
+                       (const __bf16 *)h, rows, (int)C, (int)rpb, (__bf16 *)dh, bpart);
+    *nparts = parts;
+    return check_launch(fn);
+}
 
 // Partial rows of the column sums of a bf16 [rows, C] matrix, C % 8 == 0: ws (vah_reduce_ws_floats(C)) gets
 // *nparts rows of C floats; whoever sums them (vah_colsum_bf16 below, or the finalize job of

@@ -53,7 +53,7 @@ class Mlp(nn.Module):
         self.drop = nn.Dropout(drop)
 
     def forward(self, x):
-        return self.drop(fused.linear(self.fc2, self.drop(self.act(fused.linear(self.fc1, x)))))
+        return self.drop(fused.linear(self.fc2, self.drop(fused.gelu(self.act, fused.linear(self.fc1, x)))))
 
 
 class PatchEmbed(nn.Module):

@@ -20,7 +20,7 @@ import _vah
 
 ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln': True, 'dwconv': True, 'linear': True, 'bn_tail': True,
            'bn_relu': True, 'bias_fold': True, 'keep_feat': True, 'maps': True, 'maps_in': True, 'linear_pair': True, 'maxpool': True, 'conv1x1': True, 'ln_dual': True, 'wgrad_fin': True, 'spm_nhwc': True, 'up_gemm': True, 'patch_gemm': True, 'wgrad_overlap': True, 'drop_pool': True,
-           'fp16_rows': True, 'fp16_spm': True}
+           'fp16_rows': True, 'fp16_spm': True, 'bias_partials': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -320,6 +320,7 @@ class forward_epoch:
         if live:
             BF16_COPIES.begin(live)
             SIDE.begin_epoch()
+            BIAS_PARTIALS.begin_epoch()
             if module.training:
                 DROP_POOL.begin(module, live[0].device)
         return self
@@ -395,9 +396,11 @@ def gemm_bf16(a, b, trans_a=False, trans_b=False, out_dtype=torch.bfloat16, bias
     return d
 
 
-def _wgrad_bgrad(g2, x2):
+def _wgrad_bgrad(g2, x2, partials=None):
     """(dW, db) = (g2^T x2 in fp32, column sums of g2) of a Linear backward: column-sum partials, the
-    (split-K) GEMM and ONE launch that both reduces the GEMM's slices and sums the partials."""
+    (split-K) GEMM and ONE launch that both reduces the GEMM's slices and sums the partials.  ``partials``:
+    (rows of partial column sums of g2, their number) left by the kernel that wrote g2 (_BiasPartials) - no
+    column-sum launch and no second read of g2 then."""
     import ctypes
     R, N = g2.shape
     K = x2.shape[1]
@@ -406,14 +409,16 @@ def _wgrad_bgrad(g2, x2):
     dev = g2.device
     gw = torch.empty((N, K), dtype=torch.float32, device=dev)
     gb = torch.empty(N, dtype=torch.float32, device=dev)
-    cws = _scratch(N, dev)
     ws_bytes = _GEMM_WS_BYTES + (min(64 * N * K * 4, 160 << 20) if R >= 4096 else 0)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    nparts = ctypes.c_int64(0)
     with _vah.on(dev):
         st = _stream(g2)
-        _vah.check(_vah.lib.vah_colsum_bf16_partials(g2.data_ptr(), R, N, cws.data_ptr(), ctypes.byref(nparts), st),
-                   'colsum_partials')
+        if partials is not None:
+            cws, nparts = partials[0], ctypes.c_int64(partials[1])
+        else:
+            cws, nparts = _scratch(N, dev), ctypes.c_int64(0)
+            _vah.check(_vah.lib.vah_colsum_bf16_partials(g2.data_ptr(), R, N, cws.data_ptr(), ctypes.byref(nparts), st),
+                       'colsum_partials')
         _vah.check(_vah.lib.vah_gemm_bf16_fin(1, 0, N, K, R, g2.data_ptr(), N, x2.data_ptr(), K, gw.data_ptr(), K, 1,
                                               ws.data_ptr(), ws_bytes, cws.data_ptr(), nparts.value, N, gb.data_ptr(), st),
                    'gemm_bf16_fin')
@@ -525,6 +530,87 @@ class _SideStream:
 SIDE = _SideStream()
 
 
+class _BiasPartials:
+    """Bias-gradient partials from the kernels that write a Linear's dY.  The bias gradient of a Linear is the column sum
+    of dY; where dY comes out of one of our own row-streaming backward kernels (residual + LayerNorm, residual, GELU) that
+    kernel sums the columns of what it writes and leaves the partial rows here, and the Linear's backward hands them to the
+    finalize job of its weight-gradient GEMM instead of launching a column-sum kernel over dY.
+      forward:   fused.linear marks its output (``mark``); residual / residual_ln / gelu see the mark on their branch input
+                 (``wanted``) and remember it
+      backward:  the producer records (dz, partial rows, count); _LinearBF16.backward takes them (``take``) when its
+                 gradient IS that tensor: same storage, offset, element count, row width, contiguous, and the version
+                 recorded - a gradient autograd summed, a dropout in between, a hook's copy or an in-place edit all
+                 miss, and a miss runs the column-sum kernel as before.  What is looked up is the tensor, not the
+                 layer: whichever Linear reads exactly these bytes wants exactly their column sums.
+    An entry holds a reference to dz (its address cannot be recycled while the entry lives) and is dropped when taken;
+    whatever is left goes at the end of the backward pass (an engine callback, as _SideStream's join) and when the next
+    forward epoch begins.  Nothing here waits for the device."""
+
+    ATTR = '_vah_bias_dy'
+
+    def __init__(self):
+        self.passes = {}          # device index (None: CPU) -> {(storage pointer, offset): (dz, version, partial rows, count)}
+
+    @staticmethod
+    def mark(y, bias):
+        if ENABLED['bias_partials'] and bias is not None and bias.requires_grad and torch.is_grad_enabled():
+            setattr(y, _BiasPartials.ATTR, True)
+        return y
+
+    @staticmethod
+    def wanted(z):
+        return bool(ENABLED['bias_partials'] and getattr(z, _BiasPartials.ATTR, False) and z.dtype == torch.bfloat16
+                    and z.shape[-1] % 8 == 0)
+
+    @staticmethod
+    def _key(t):
+        return (t.untyped_storage().data_ptr(), t.storage_offset())
+
+    def record(self, dz, bpart, nparts):
+        idx = dz.device.index
+        entries = self.passes.get(idx)
+        if entries is None:
+            entries = self.passes[idx] = {}
+            try:                    # the engine runs it after the last node of this backward pass
+                torch.autograd.Variable._execution_engine.queue_callback(lambda: self.end_pass(idx))
+            except RuntimeError:    # not inside a backward pass: the next epoch clears
+                pass
+        entries[self._key(dz)] = (dz, dz._version, bpart, int(nparts))
+
+    def take(self, g2):
+        """-> (partial rows, count) for the contiguous (R, N) gradient ``g2``, or None."""
+        entries = self.passes.get(g2.device.index)
+        if not entries:
+            return None
+        key = self._key(g2)
+        e = entries.get(key)
+        if e is None:
+            return None
+        dz, version, bpart, nparts = e
+        if (g2.dim() != 2 or not g2.is_contiguous() or not dz.is_contiguous() or dz.dtype != g2.dtype
+                or dz.shape[-1] != g2.shape[1] or dz.numel() != g2.numel() or dz._version != version
+                or g2._version != version or nparts < 1):
+            return None
+        del entries[key]
+        return bpart, nparts
+
+    def end_pass(self, idx):
+        self.passes.pop(idx, None)
+
+    def begin_epoch(self):
+        self.passes.clear()
+
+
+BIAS_PARTIALS = _BiasPartials()
+
+
+def _bias_partials_out(C, device):
+    """The partial rows a producer leaves for a Linear: an allocation of its own (they outlive the call, unlike _scratch)
+    and the slot for their count."""
+    import ctypes
+    return torch.empty(_vah.lib.vah_reduce_ws_floats(C), dtype=torch.float32, device=device), ctypes.c_int64(0)
+
+
 class _LinearBF16(torch.autograd.Function):
     """y = x W^T + b with bf16 operands and fp32 accumulation (what autocast makes of F.linear).
     Backward: dX in bf16, dW straight into fp32 from the GEMM (no bf16 rounding, no cast kernel),
@@ -557,10 +643,12 @@ class _LinearBF16(torch.autograd.Function):
         gx = gw = gb = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         fin = ctx.needs_input_grad[1] and want_b and WGRAD_F32 and g2.shape[0] > 0 and ENABLED['wgrad_fin']
+        partials = BIAS_PARTIALS.take(g2) if fin else None       # the kernel that wrote g2 summed its columns
         deferred = fin and SIDE.may_defer(ctx.side, g2.device)
         if deferred:                    # weight / bias gradients beside the input gradient, on the side stream
-            with torch.cuda.stream(SIDE.fork(g2.device, (g2, x2))):
-                SIDE.deliver(g2.device, ctx.side, _wgrad_bgrad(g2, x2))
+            keep = (g2, x2) if partials is None else (g2, x2, partials[0])
+            with torch.cuda.stream(SIDE.fork(g2.device, keep)):
+                SIDE.deliver(g2.device, ctx.side, _wgrad_bgrad(g2, x2, partials))
         if ctx.needs_input_grad[0]:
             gx = gemm_bf16(g2, wb).view(ctx.in_shape)
             if gx.dtype != ctx.in_dtype:
@@ -568,7 +656,7 @@ class _LinearBF16(torch.autograd.Function):
         if deferred:
             pass
         elif fin:
-            gw, gb = _wgrad_bgrad(g2, x2)
+            gw, gb = _wgrad_bgrad(g2, x2, partials)
         else:
             if ctx.needs_input_grad[1]:
                 if WGRAD_F32:
@@ -950,13 +1038,69 @@ def linear(lin, x):
     if (ENABLED['linear'] and x.is_cuda and _bf16_autocast() and w.dtype == torch.float32
             and x.dtype in (torch.bfloat16, torch.float32) and w.shape[0] % 8 == 0
             and w.shape[1] % 8 == 0 and x.numel() > 0 and type(lin) is torch.nn.Linear):
-        return _LinearBF16.apply(x, w, lin.bias)
+        return BIAS_PARTIALS.mark(_LinearBF16.apply(x, w, lin.bias), lin.bias)
     return lin(x)
+
+
+class _GeluBF16(torch.autograd.Function):
+    """Exact GELU on the bf16 output of a fused Linear: torch's forward kernel; the backward is one kernel that writes
+    dh and the partial column sums of dh - the Linear's bias gradient (_BiasPartials)."""
+
+    @staticmethod
+    def forward(ctx, h):
+        ctx.save_for_backward(h)
+        return F.gelu(h)
+
+    @staticmethod
+    def backward(ctx, da):
+        (h,) = ctx.saved_tensors
+        C = h.shape[-1]
+        hc = h.contiguous()
+        da = da.contiguous().to(torch.bfloat16)
+        dh = torch.empty(h.shape, dtype=torch.bfloat16, device=h.device)
+        bpart, nparts = _bias_partials_out(C, h.device)
+        import ctypes
+        with _vah.on(h.device):
+            _vah.check(_vah.lib.vah_gelu_bwd_bsum_bf16(da.data_ptr(), hc.data_ptr(), h.numel() // C, C, dh.data_ptr(),
+                                                       bpart.data_ptr(), ctypes.byref(nparts), _stream(h)), 'gelu_bwd_bsum')
+        BIAS_PARTIALS.record(dh, bpart, nparts.value)
+        return dh
+
+
+def gelu(act, h):
+    """``act(h)`` for the activation between two Linears (base/vit.py Mlp): an exact nn.GELU on the marked bf16 output
+    of a fused Linear under bf16 autocast takes the backward kernel that also sums fc1's bias gradient."""
+    if (isinstance(act, torch.nn.GELU) and act.approximate == 'none' and h.is_cuda and _bf16_autocast()
+            and BIAS_PARTIALS.wanted(h) and h.numel() > 0 and h.requires_grad and torch.is_grad_enabled()):
+        return _GeluBF16.apply(h)
+    return act(h)
+
+
+def _scale_residual_bwd(g, z, gp, s, dims, bias_partials):
+    """(dz, dgamma) of y = x + s * gamma * z for the contiguous fp32 gradient g of y; with ``bias_partials`` the kernel
+    also leaves the partial column sums of dz for the Linear that made z (_BiasPartials)."""
+    import ctypes
+    B, rpb, C = dims
+    dz = torch.empty_like(z)
+    dgamma = torch.empty(C, dtype=torch.float32, device=g.device) if gp is not None else None
+    ws = _scratch(C, g.device) if gp is not None else None
+    args = (g.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
+            s.data_ptr() if s is not None else None, B, rpb, C, dz.data_ptr(),
+            dgamma.data_ptr() if dgamma is not None else None, ws.data_ptr() if ws is not None else None)
+    with _vah.on(g.device):
+        if bias_partials:
+            bpart, nparts = _bias_partials_out(C, g.device)
+            _vah.check(_vah.lib.vah_scale_residual_bwd_bsum(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(g)),
+                       'scale_residual_bwd_bsum')
+            BIAS_PARTIALS.record(dz, bpart, nparts.value)
+        else:
+            _vah.check(_sym('vah_scale_residual_bwd', z.dtype)(*args, _stream(g)), 'scale_residual_bwd')
+    return dz, dgamma
 
 
 class _ScaleResidual(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, z, gamma, s):
+    def forward(ctx, x, z, gamma, s, bias_partials=False):
         B, C = x.shape[0], x.shape[-1]
         rpb = x.numel() // (B * C)
         x, z = x.contiguous(), z.contiguous()
@@ -969,23 +1113,15 @@ class _ScaleResidual(torch.autograd.Function):
                 'scale_residual_fwd')
         ctx.save_for_backward(z, gp, s)
         ctx.dims = (B, rpb, C)
+        ctx.bias_partials = bias_partials
         return y
 
     @staticmethod
     def backward(ctx, g):
         z, gp, s = ctx.saved_tensors
-        B, rpb, C = ctx.dims
         g = g.contiguous()
-        dz = torch.empty_like(z)
-        dgamma = torch.empty(C, dtype=torch.float32, device=g.device) if gp is not None else None
-        ws = _scratch(C, g.device) if gp is not None else None
-        with _vah.on(g.device):
-            _vah.check(_sym('vah_scale_residual_bwd', z.dtype)(
-                g.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
-                s.data_ptr() if s is not None else None, B, rpb, C, dz.data_ptr(),
-                dgamma.data_ptr() if dgamma is not None else None,
-                ws.data_ptr() if ws is not None else None, _stream(g)), 'scale_residual_bwd')
-        return g, dz, dgamma, None
+        dz, dgamma = _scale_residual_bwd(g, z, gp, s, ctx.dims, ctx.bias_partials)
+        return g, dz, dgamma, None, None
 
 
 def residual(x, z, gamma=None, drop_path=None):
@@ -999,7 +1135,7 @@ def residual(x, z, gamma=None, drop_path=None):
         s = None
         if prob > 0. and training:
             s = DROP_POOL.take(x, 1.0 - prob)
-        return _ScaleResidual.apply(x, z, gamma, s)
+        return _ScaleResidual.apply(x, z, gamma, s, BIAS_PARTIALS.wanted(z))
     t = gamma * z if gamma is not None else z
     return x + (drop_path(t) if drop_path is not None else t)
 
@@ -1009,7 +1145,7 @@ class _ResidualLN(torch.autograd.Function):
     along the residual stream and through the LayerNorm in-kernel and emits dz, dgamma with it."""
 
     @staticmethod
-    def forward(ctx, x, z, gamma, s, weight, bias, eps):
+    def forward(ctx, x, z, gamma, s, weight, bias, eps, bias_partials=False):
         B, C = x.shape[0], x.shape[-1]
         rpb = x.numel() // (B * C)
         x, z = x.contiguous(), z.contiguous()
@@ -1027,6 +1163,7 @@ class _ResidualLN(torch.autograd.Function):
                 t.data_ptr(), h.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(x)), 'residual_layernorm_fwd')
         ctx.save_for_backward(t, z, gp, s, w, mean, rstd)
         ctx.dims = (B, rpb, C)
+        ctx.bias_partials = bias_partials      # residual_ln asks only without a gamma
         ctx.set_materialize_grads(False)
         return t, h
 
@@ -1039,30 +1176,29 @@ class _ResidualLN(torch.autograd.Function):
             gt = gt.contiguous().float()
         if gh is None:                       # the normalised copy was not used: plain residual backward
             if gt is None:
-                return (None,) * 7
-            dz = torch.empty_like(z)
-            dgamma = torch.empty(C, dtype=torch.float32, device=dev) if gp is not None else None
-            ws = _scratch(C, dev) if gp is not None else None
-            with _vah.on(dev):
-                _vah.check(_sym('vah_scale_residual_bwd', z.dtype)(
-                    gt.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
-                    s.data_ptr() if s is not None else None, B, rpb, C, dz.data_ptr(),
-                    dgamma.data_ptr() if dgamma is not None else None,
-                    ws.data_ptr() if ws is not None else None, _stream(gt)), 'scale_residual_bwd')
-            return gt, dz, dgamma, None, None, None, None
+                return (None,) * 8
+            dz, dgamma = _scale_residual_bwd(gt, z, gp, s, ctx.dims, ctx.bias_partials)
+            return gt, dz, dgamma, None, None, None, None, None
         gh = gh.contiguous().to(z.dtype)
         dt = torch.empty_like(t)
         dz = torch.empty_like(z)
         grads = torch.empty(3, C, dtype=torch.float32, device=dev)
         ws = _scratch(3 * C, dev)
-        with _vah.on(dev):
-            _vah.check(_sym('vah_residual_layernorm_bwd', z.dtype)(
-                t.data_ptr(), gh.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+        args = (t.data_ptr(), gh.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                 gt.data_ptr() if gt is not None else None, z.data_ptr(),
                 gp.data_ptr() if gp is not None else None, s.data_ptr() if s is not None else None, B, rpb, C,
                 dt.data_ptr(), dz.data_ptr(), grads[2].data_ptr() if gp is not None else None,
-                grads[0].data_ptr(), grads[1].data_ptr(), ws.data_ptr(), _stream(t)), 'residual_layernorm_bwd')
-        return dt, dz, grads[2] if gp is not None else None, None, grads[0], grads[1], None
+                grads[0].data_ptr(), grads[1].data_ptr(), ws.data_ptr())
+        with _vah.on(dev):
+            if ctx.bias_partials and gp is None:
+                import ctypes
+                bpart, nparts = _bias_partials_out(C, dev)
+                _vah.check(_vah.lib.vah_residual_layernorm_bwd_bsum(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(t)),
+                           'residual_layernorm_bwd_bsum')
+                BIAS_PARTIALS.record(dz, bpart, nparts.value)
+            else:
+                _vah.check(_sym('vah_residual_layernorm_bwd', z.dtype)(*args, _stream(t)), 'residual_layernorm_bwd')
+        return dt, dz, grads[2] if gp is not None else None, None, grads[0], grads[1], None, None
 
 
 def _drop_path_scale(x, drop_path):
@@ -1079,7 +1215,8 @@ def residual_ln(x, z, gamma, drop_path, norm):
     if (ENABLED['residual'] and ENABLED['residual_ln'] and _ln_fusable(norm, x) and z.dtype == _autocast_16()
             and x.shape == z.shape
             and x.dim() >= 2 and (gamma is None or gamma.dtype == torch.float32) and x.shape[-1] <= 1024):
-        return _ResidualLN.apply(x, z, gamma, _drop_path_scale(x, drop_path), norm.weight, norm.bias, norm.eps)
+        return _ResidualLN.apply(x, z, gamma, _drop_path_scale(x, drop_path), norm.weight, norm.bias, norm.eps,
+                                 gamma is None and BIAS_PARTIALS.wanted(z))
     ac = _autocast_16()
     if ENABLED['fp16_rows'] and ac is not None and z.dtype != ac and z.dtype in (torch.bfloat16, torch.float16):
         # a branch output in the other 16-bit type than the one autocast is running: the torch expression, nothing fused
