@@ -450,6 +450,37 @@ int vah_maxpool3s2_fwd_bf16(const void *x, int64_t planes, int64_t H, int64_t W,
 int vah_maxpool3s2_bwd_bf16(const void *gy, const void *idx, int64_t planes, int64_t H, int64_t W, void *gx,
                             void *stream);
 
+/* fp16 twins of the output-tail kernels above (fp16 autocast): the same signatures, checks, messages (function name
+ * apart), launch geometry, LDS and workspaces - each pair is one entry / launch template - with _Float16 where the bf16
+ * entry has a bf16 operand.  A flag in the position of a_bf16 / b_bf16 / y_bf16 / dy_bf16 / planes_bf16 reads "fp16 (1) or
+ * fp32 (0)".  All arithmetic, statistics, sums, mean, rstd, dxlo and ws are fp32; fp16 -> fp32 is exact (subnormals
+ * included); fp32 -> fp16 rounds to nearest even, overflows to inf and keeps subnormals, bit for bit what
+ * torch.Tensor.to(torch.float16) gives.  vah_bn_tail_ws_floats, vah_bn_tail_supported and vah_bn_finalize_stats serve
+ * both.  Profiler rows: the bf16 rows with `_f16` appended. */
+int vah_bn_tail_stats_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale,
+                          int64_t N, int64_t C, int64_t H, int64_t W, const float *shift, float *sums, float *ws,
+                          void *stream);
+int vah_bn_tail_apply_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale,
+                          int64_t N, int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd,
+                          const float *gamma, const float *beta, int relu, const float *shift, void *y, int y_f16,
+                          void *stream);
+int vah_bn_tail_bwd_stats_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale,
+                              int64_t N, int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd,
+                              const float *gamma, const float *beta, int relu, const float *shift, const void *dy,
+                              int dy_f16, float *sums, float *ws, void *stream);
+int vah_bn_tail_bwd_apply_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale,
+                              int64_t N, int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd,
+                              const float *gamma, const float *beta, int relu, const float *shift, const void *dy,
+                              int dy_f16, const float *mdy, const float *mdyx, void *da, void *db, float *dxlo,
+                              void *stream);
+int vah_pixel_shuffle2_f16(const void *src, int64_t B, int64_t C, int64_t h, int64_t w, void *dst, int inverse, const void *add,
+                           void *stream);
+int vah_transpose_tokens_f16(const void *src, int64_t B, int64_t T_total, int64_t t0, int64_t T, int64_t C, void *dst,
+                             int to_planes, int planes_f16, const float *vec, void *stream);
+int vah_maxpool3s2_fwd_f16(const void *x, int64_t planes, int64_t H, int64_t W, void *y, void *idx, void *stream);
+int vah_maxpool3s2_bwd_f16(const void *gy, const void *idx, int64_t planes, int64_t H, int64_t W, void *gx,
+                           void *stream);
+
 /* ---- 3x3 convolutions of the SpatialPriorModule as implicit GEMMs (csrc/conv.hip) -----------------------------
  * Replaces nn.Conv2d(k=3, padding=1, stride 1 | 2, bias=False) forward and both gradients of the stem / conv2-4
  * (adapter_modules.py:217-260), NHWC bf16 operands, fp32 accumulation.

@@ -187,6 +187,17 @@ SPM_F16_TWINS = {
 for _b16, _f16 in SPM_F16_TWINS.items():
     getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
 
+# fp16 twins of the output-tail kernels (csrc/tail_ops.hip); in the twins the `*_bf16` flags read "fp16 (1) or fp32 (0)".
+# vah_bn_tail_supported, vah_bn_tail_ws_floats and vah_bn_finalize_stats are shared
+TAIL_F16_TWINS = {
+    'vah_bn_tail_stats': 'vah_bn_tail_stats_f16', 'vah_bn_tail_apply': 'vah_bn_tail_apply_f16',
+    'vah_bn_tail_bwd_stats': 'vah_bn_tail_bwd_stats_f16', 'vah_bn_tail_bwd_apply': 'vah_bn_tail_bwd_apply_f16',
+    'vah_transpose_tokens': 'vah_transpose_tokens_f16', 'vah_maxpool3s2_fwd_bf16': 'vah_maxpool3s2_fwd_f16',
+    'vah_maxpool3s2_bwd_bf16': 'vah_maxpool3s2_bwd_f16', 'vah_pixel_shuffle2_bf16': 'vah_pixel_shuffle2_f16',
+}
+for _b16, _f16 in TAIL_F16_TWINS.items():
+    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))
@@ -220,6 +231,8 @@ EXPORTS = (
     'vah_conv_taps_nhwc_f16', 'vah_conv3x3_dgrad_nhwc_f16', 'vah_conv3x3_wgrad_nhwc_f16', 'vah_image_to_nhwc16_f16',
     'vah_bn_nhwc_stats_f16', 'vah_bn_nhwc_apply_f16', 'vah_bn_nhwc_bwd_stats_f16', 'vah_bn_nhwc_bwd_apply_f16',
     'vah_maxpool3s2_nhwc_fwd_f16', 'vah_maxpool3s2_nhwc_bwd_f16',
+    'vah_bn_tail_stats_f16', 'vah_bn_tail_apply_f16', 'vah_bn_tail_bwd_stats_f16', 'vah_bn_tail_bwd_apply_f16',
+    'vah_transpose_tokens_f16', 'vah_maxpool3s2_fwd_f16', 'vah_maxpool3s2_bwd_f16', 'vah_pixel_shuffle2_f16',
 )
 
 

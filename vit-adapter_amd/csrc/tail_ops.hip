@@ -13,18 +13,27 @@
 // x: optional fp32 (N, C, H / s, W / s), s in {1, 2, 4, 8} (s = 1: plain add).  W % 4 == 0.
 // Bilinear taps follow torch's upsample_bilinear2d with align_corners = False and an explicit
 // scale factor:  src = (dst + 0.5) / s - 0.5, clamped at 0;  i1 = min(i0 + 1, n - 1).
+//
+// Every kernel that touches a 16-bit operand is a template on its element type T (__bf16, or _Float16 for the `_f16`
+// entry points).  T appears in loads, stores and converts only: 16-bit -> fp32 is exact (fp16 subnormals included) and
+// fp32 -> 16-bit is the plain (T)f cast (round to nearest even; fp16 overflows to inf and keeps subnormals, as
+// torch.Tensor.to(torch.float16) does).  Arithmetic, statistics, partial rows, dxlo and the workspaces are fp32 for
+// both.  The runtime `*_bf16` flags keep their meaning "16-bit (of type T) or fp32".
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
 #include "../../include/vitadapter_hip.h"
+#include "attn_common.h"
 #include "common.h"
 
 namespace vah {
 namespace {
 
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
+using attn::tname;
+using attn::vec4;
+using attn::vec8;
 
 constexpr int kTilePx = 8192;           // hi-res pixels of one plane per workgroup
 constexpr int kTailParts = 512;         // partial rows of the channel sums (finalised below)
@@ -57,16 +66,8 @@ __device__ __forceinline__ Tap tap_of(int d, int n_lo, int s) {
     return t;
 }
 
-__device__ __forceinline__ float4 load4(const void *p, int64_t idx, int is_bf16) {
-    if (is_bf16) {
-        const bf16x4 v = *reinterpret_cast<const bf16x4 *>(reinterpret_cast<const __bf16 *>(p) + idx);
-        return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-    }
-    return *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(p) + idx);
-}
-
-// Raw 4-element load (4 fp32 or 4 bf16, dtype uniform) and its decode, kept apart so that a kernel can
-// request all of its operands before it touches the first: with the conversion next to the load (load4)
+// Raw 4-element load (4 fp32 or 4 16-bit values, dtype uniform) and its decode, kept apart so that a kernel can
+// request all of its operands before it touches the first: with the conversion next to the load
 // every operand sat in its own uniform branch with its own s_waitcnt vmcnt(0).
 struct Raw4 {
     uint32_t w0, w1, w2, w3;
@@ -76,7 +77,7 @@ __device__ __forceinline__ Raw4 load_raw(const void *p, int64_t idx, int is_bf16
     Raw4 r;
     r.w0 = r.w1 = r.w2 = r.w3 = 0u;
     if (is_bf16) {
-        const uint2 v = *reinterpret_cast<const uint2 *>(reinterpret_cast<const __bf16 *>(p) + idx);
+        const uint2 v = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(p) + idx);
         r.w0 = v.x;
         r.w1 = v.y;
     } else {
@@ -89,22 +90,39 @@ __device__ __forceinline__ Raw4 load_raw(const void *p, int64_t idx, int is_bf16
     return r;
 }
 
+// The four 16-bit values of (w0, w1) as fp32: bf16 is the upper half of an fp32 word; fp16 takes v_cvt_f32_f16
+// (exact, subnormals included).
+template <typename T>
+__device__ __forceinline__ float4 widen4(uint32_t w0, uint32_t w1);
+template <>
+__device__ __forceinline__ float4 widen4<__bf16>(uint32_t w0, uint32_t w1) {
+    return make_float4(__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xffff0000u), __uint_as_float(w1 << 16),
+                       __uint_as_float(w1 & 0xffff0000u));
+}
+template <>
+__device__ __forceinline__ float4 widen4<_Float16>(uint32_t w0, uint32_t w1) {
+    typedef __attribute__((__vector_size__(2 * sizeof(_Float16)))) _Float16 f16x2;
+    const f16x2 lo = __builtin_bit_cast(f16x2, w0), hi = __builtin_bit_cast(f16x2, w1);
+    return make_float4((float)lo[0], (float)lo[1], (float)hi[0], (float)hi[1]);
+}
+
+template <typename T>
 __device__ __forceinline__ float4 decode(const Raw4 &r, int is_bf16) {
-    const float4 h = make_float4(__uint_as_float(r.w0 << 16), __uint_as_float(r.w0 & 0xffff0000u),
-                                 __uint_as_float(r.w1 << 16), __uint_as_float(r.w1 & 0xffff0000u));
+    const float4 h = widen4<T>(r.w0, r.w1);
     const float4 f = make_float4(__uint_as_float(r.w0), __uint_as_float(r.w1), __uint_as_float(r.w2),
                                  __uint_as_float(r.w3));
     return is_bf16 ? h : f;
 }
 
+template <typename T>
 __device__ __forceinline__ void store4(void *p, int64_t idx, int is_bf16, float4 v) {
     if (is_bf16) {
-        bf16x4 o;
-        o[0] = (__bf16)v.x;
-        o[1] = (__bf16)v.y;
-        o[2] = (__bf16)v.z;
-        o[3] = (__bf16)v.w;
-        *reinterpret_cast<bf16x4 *>(reinterpret_cast<__bf16 *>(p) + idx) = o;
+        vec4<T> o;
+        o[0] = (T)v.x;
+        o[1] = (T)v.y;
+        o[2] = (T)v.z;
+        o[3] = (T)v.w;
+        *reinterpret_cast<vec4<T> *>(reinterpret_cast<T *>(p) + idx) = o;
     } else {
         *reinterpret_cast<float4 *>(reinterpret_cast<float *>(p) + idx) = v;
     }
@@ -113,6 +131,7 @@ __device__ __forceinline__ void store4(void *p, int64_t idx, int is_bf16, float4
 // t = a + b + up(x) for 4 consecutive pixels (row y, columns x4 .. x4 + 3) of plane `plane`.
 // Every load (a, b, the 8 low-res values, and the caller's dy when `dy` is given) is requested before the
 // first is decoded.
+template <typename T>
 __device__ __forceinline__ float4 sum4(const Operands &o, int64_t plane, int y, int x4, const void *dy = nullptr,
                                        Raw4 *dy_raw = nullptr) {
     const int64_t idx = (plane * o.H + y) * o.W + x4;
@@ -152,8 +171,8 @@ __device__ __forceinline__ float4 sum4(const Operands &o, int64_t plane, int y, 
         }
     }
     __builtin_amdgcn_sched_barrier(0);                       // loads above, arithmetic below
-    float4 t = decode(ra, o.a_bf16);
-    const float4 vb = decode(rb, o.b_bf16);
+    float4 t = decode<T>(ra, o.a_bf16);
+    const float4 vb = decode<T>(rb, o.b_bf16);
     t.x += sft + vb.x;
     t.y += sft + vb.y;
     t.z += sft + vb.z;
@@ -224,6 +243,7 @@ __device__ __forceinline__ float block_sum(float v, float *s_red) {      // 256 
 // part[(n * chunks + chunk)][2C]: (sum t | sum t^2) of the block's pixels, for its channel only.  The C planes of
 // one (n, chunk) between them write every column of its row and tail_finalize reads the N * chunks (<= kTailParts)
 // rows that were written and no other, so the partial buffer needs no initialisation.
+template <typename T>
 __global__ __launch_bounds__(256) void tail_stats_kernel(Operands o, float *__restrict__ part) {
     __shared__ float s_red[4];
     const int64_t plane = blockIdx.x / o.chunks;
@@ -235,7 +255,7 @@ __global__ __launch_bounds__(256) void tail_stats_kernel(Operands o, float *__re
     float s1 = 0.f, s2 = 0.f;
     for (int i = threadIdx.x; i < (r1 - r0) * wv4; i += 256) {
         const int iy = wv4 == 1 ? i : (int)__umulhi((unsigned)i, o.quad_magic), y = r0 + iy, x4 = (i - iy * wv4) * 4;
-        const float4 t = sum4(o, plane, y, x4);
+        const float4 t = sum4<T>(o, plane, y, x4);
         s1 += (t.x + t.y) + (t.z + t.w);
         s2 += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
     }
@@ -248,6 +268,7 @@ __global__ __launch_bounds__(256) void tail_stats_kernel(Operands o, float *__re
     }
 }
 
+template <typename T>
 __global__ __launch_bounds__(256) void tail_apply_kernel(Operands o, const float *__restrict__ mean,
                                                          const float *__restrict__ rstd,
                                                          const float *__restrict__ gamma,
@@ -262,16 +283,17 @@ __global__ __launch_bounds__(256) void tail_apply_kernel(Operands o, const float
     const float lo = o.relu ? 0.f : -INFINITY;
     for (int i = threadIdx.x; i < (r1 - r0) * wv4; i += 256) {
         const int iy = wv4 == 1 ? i : (int)__umulhi((unsigned)i, o.quad_magic), yy = r0 + iy, x4 = (i - iy * wv4) * 4;
-        const float4 t = sum4(o, plane, yy, x4);
-        store4(y, (plane * o.H + yy) * o.W + x4, o.y_bf16,
+        const float4 t = sum4<T>(o, plane, yy, x4);
+        store4<T>(y, (plane * o.H + yy) * o.W + x4, o.y_bf16,
                make_float4(fmaxf(t.x * sc + sh, lo), fmaxf(t.y * sc + sh, lo), fmaxf(t.z * sc + sh, lo),
                            fmaxf(t.w * sc + sh, lo)));
     }
 }
 
 // Gradient reaching the normalisation output: dy, masked by the fused ReLU (y recomputed, not stored).
+template <typename T>
 __device__ __forceinline__ float4 grad4(const Operands &o, const Raw4 &dy_raw, const float4 &t, float sc, float sh) {
-    float4 g = decode(dy_raw, o.dy_bf16);
+    float4 g = decode<T>(dy_raw, o.dy_bf16);
     if (o.relu) {
         g.x = t.x * sc + sh > 0.f ? g.x : 0.f;
         g.y = t.y * sc + sh > 0.f ? g.y : 0.f;
@@ -282,6 +304,7 @@ __device__ __forceinline__ float4 grad4(const Operands &o, const Raw4 &dy_raw, c
 }
 
 // part row: (sum dy | sum dy * xhat) for the block's channel.
+template <typename T>
 __global__ __launch_bounds__(256) void tail_bwd_stats_kernel(Operands o, const float *__restrict__ mean,
                                                              const float *__restrict__ rstd,
                                                              const float *__restrict__ gamma,
@@ -301,8 +324,8 @@ __global__ __launch_bounds__(256) void tail_bwd_stats_kernel(Operands o, const f
     for (int i = threadIdx.x; i < (r1 - r0) * wv4; i += 256) {
         const int iy = wv4 == 1 ? i : (int)__umulhi((unsigned)i, o.quad_magic), yy = r0 + iy, x4 = (i - iy * wv4) * 4;
         Raw4 rdy;
-        const float4 t = sum4(o, plane, yy, x4, dy, &rdy);
-        const float4 g = grad4(o, rdy, t, sc, sh);
+        const float4 t = sum4<T>(o, plane, yy, x4, dy, &rdy);
+        const float4 g = grad4<T>(o, rdy, t, sc, sh);
         s1 += (g.x + g.y) + (g.z + g.w);
         s2 += (g.x * (t.x - mu) + g.y * (t.y - mu)) + (g.z * (t.z - mu) + g.w * (t.w - mu));
     }
@@ -319,6 +342,7 @@ __global__ __launch_bounds__(256) void tail_bwd_stats_kernel(Operands o, const f
 // dx_lo += upsample^T(dt): the tile of dt is staged in LDS and every low-res pixel gathers its
 // (2s x 2s) footprint, separably (columns, then rows); rows shared with the neighbouring tile go
 // through fp32 atomics on the small low-res map.
+template <typename T>
 __global__ __launch_bounds__(256) void tail_bwd_apply_kernel(Operands o, const float *__restrict__ mean,
                                                              const float *__restrict__ rstd,
                                                              const float *__restrict__ gamma,
@@ -342,12 +366,12 @@ __global__ __launch_bounds__(256) void tail_bwd_apply_kernel(Operands o, const f
         const int iy = wv4 == 1 ? i : (int)__umulhi((unsigned)i, o.quad_magic), yy = r0 + iy, x4 = (i - iy * wv4) * 4;
         const int64_t idx = (plane * o.H + yy) * o.W + x4;
         Raw4 rdy;
-        const float4 t = sum4(o, plane, yy, x4, dy, &rdy);
-        const float4 g = grad4(o, rdy, t, k, sh);
+        const float4 t = sum4<T>(o, plane, yy, x4, dy, &rdy);
+        const float4 g = grad4<T>(o, rdy, t, k, sh);
         const float4 d = make_float4(k * (g.x - m1 - (t.x - mu) * rs * m2), k * (g.y - m1 - (t.y - mu) * rs * m2),
                                      k * (g.z - m1 - (t.z - mu) * rs * m2), k * (g.w - m1 - (t.w - mu) * rs * m2));
-        if (da) store4(da, idx, o.a_bf16, d);
-        if (db) store4(db, idx, o.b_bf16, d);
+        if (da) store4<T>(da, idx, o.a_bf16, d);
+        if (db) store4<T>(db, idx, o.b_bf16, d);
         if (want_lo) {
             if (o.scale == 1) *reinterpret_cast<float4 *>(dxlo + idx) = d;      // same grid: plain store
             else *reinterpret_cast<float4 *>(s_tile + (yy - r0) * o.W + x4) = d;
@@ -429,10 +453,10 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float *__restric
     }
 }
 
-// (B, T_total, C) fp32 token rows [t0, t0 + T)  <->  (B, C, T) planes (fp32 or bf16), through a
+// (B, T_total, C) fp32 token rows [t0, t0 + T)  <->  (B, C, T) planes (fp32 or the 16-bit type E), through a
 // 32 x 33 LDS tile (both sides coalesced).  TO_PLANES: planes <- tokens; else tokens <- planes
 // (+ an optional per-channel vector: conv bias + level embedding of the SPM maps).
-template <bool TO_PLANES>
+template <typename E, bool TO_PLANES>
 __global__ __launch_bounds__(256) void transpose_tokens_kernel(const void *__restrict__ src, void *__restrict__ dst,
                                                                int64_t T_total, int64_t t0, int T, int C,
                                                                int planes_bf16, const float *__restrict__ vec) {
@@ -456,7 +480,7 @@ __global__ __launch_bounds__(256) void transpose_tokens_kernel(const void *__res
         for (int r = ly; r < 32; r += 8)                              // write plane rows: token fastest
             if (cc + r < C && tt + lx < T) {
                 const int64_t o = plane_base + (int64_t)(cc + r) * T + tt + lx;
-                if (planes_bf16) reinterpret_cast<__bf16 *>(dst)[o] = (__bf16)tile[lx][r];
+                if (planes_bf16) reinterpret_cast<E *>(dst)[o] = (E)tile[lx][r];
                 else reinterpret_cast<float *>(dst)[o] = tile[lx][r];
             }
     } else {
@@ -467,7 +491,7 @@ __global__ __launch_bounds__(256) void transpose_tokens_kernel(const void *__res
             o4[u] = plane_base + (int64_t)min(cc + ly + 8 * u, C - 1) * T + min(tt + lx, T - 1);
         if (planes_bf16) {                                            // dtype branch around the 4 loads, not inside
 #pragma unroll
-            for (int u = 0; u < 4; ++u) v4[u] = (float)reinterpret_cast<const __bf16 *>(src)[o4[u]];
+            for (int u = 0; u < 4; ++u) v4[u] = (float)reinterpret_cast<const E *>(src)[o4[u]];
         } else {
 #pragma unroll
             for (int u = 0; u < 4; ++u) v4[u] = reinterpret_cast<const float *>(src)[o4[u]];
@@ -484,19 +508,20 @@ __global__ __launch_bounds__(256) void transpose_tokens_kernel(const void *__res
     }
 }
 
-// MaxPool2d(kernel 3, stride 2, padding 1) of the SPM stem (adapter_modules.py:229-230), bf16 NCHW.
+// MaxPool2d(kernel 3, stride 2, padding 1) of the SPM stem (adapter_modules.py:229-230), 16-bit NCHW.
 // Forward keeps the window position (0..8) of the FIRST maximum in row-major scan order - the element
 // torch's max_pool2d routes the gradient to - in one byte per output; backward is a gather: every
 // input pixel lies in at most 4 windows and takes their gradients where it is the recorded maximum
 // (torch's backward scatters with atomics: 222 us for the 2 x 64 x 512 x 512 stem map).
-__global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(const __bf16 *__restrict__ x, int H, int W, int Ho, int Wo,
-                                                             __bf16 *__restrict__ y, unsigned char *__restrict__ idx) {
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(const T *__restrict__ x, int H, int W, int Ho, int Wo,
+                                                             T *__restrict__ y, unsigned char *__restrict__ idx) {
     // block = 64 output columns x 4 output rows of one plane (blockIdx.z): no index divisions
     const int ox = blockIdx.x * 64 + (threadIdx.x & 63);
     const int oy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (ox >= Wo || oy >= Ho) return;
     const int64_t plane = blockIdx.z;
-    const __bf16 *xp = x + plane * H * W;
+    const T *xp = x + plane * H * W;
     // the 9 window values are requested together (clamped coordinates), validity applied afterwards: loads
     // under `if (inside)` were waited on one by one
     float win[9];
@@ -521,19 +546,20 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(const __bf16 *__res
         }
     }
     const int64_t o = (plane * Ho + oy) * Wo + ox;
-    y[o] = (__bf16)best;
+    y[o] = (T)best;
     idx[o] = (unsigned char)pos;
 }
 
 // thread = 8 consecutive input columns of one input row (one 16-byte store); block = 64 x 4 such threads
-__global__ __launch_bounds__(256) void maxpool3s2_bwd_kernel(const __bf16 *__restrict__ gy,
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool3s2_bwd_kernel(const T *__restrict__ gy,
                                                              const unsigned char *__restrict__ idx, int H, int W, int Ho,
-                                                             int Wo, __bf16 *__restrict__ gx) {
+                                                             int Wo, T *__restrict__ gx) {
     const int ix0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 8;
     const int iy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (ix0 >= W || iy >= H) return;
     const int64_t plane = blockIdx.z;
-    const __bf16 *gp = gy + plane * Ho * Wo;
+    const T *gp = gy + plane * Ho * Wo;
     const unsigned char *ip = idx + plane * Ho * Wo;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int oy0 = iy >> 1, oy1 = (iy + 1) >> 1;                  // the one or two window rows that contain iy
@@ -572,15 +598,14 @@ __global__ __launch_bounds__(256) void maxpool3s2_bwd_kernel(const __bf16 *__res
                 if (p[a][u0 + 1] == ky3 + 0) acc[e] += g[a][u0 + 1];
         }
     }
-    __bf16 *o = gx + (plane * H + iy) * (int64_t)W + ix0;
+    T *o = gx + (plane * H + iy) * (int64_t)W + ix0;
     if (ix0 + 8 <= W && (W & 7) == 0) {
-        typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8_t;
-        bf16x8_t v;
+        vec8<T> v;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (__bf16)acc[e];
-        *reinterpret_cast<bf16x8_t *>(o) = v;
+        for (int e = 0; e < 8; ++e) v[e] = (T)acc[e];
+        *reinterpret_cast<vec8<T> *>(o) = v;
     } else {
-        for (int e = 0; e < 8 && ix0 + e < W; ++e) o[e] = (__bf16)acc[e];
+        for (int e = 0; e < 8 && ix0 + e < W; ++e) o[e] = (T)acc[e];
     }
 }
 
@@ -644,12 +669,11 @@ int fill_operands(const char *fn, Operands &o, const void *a, int a_bf16, const 
 // transposed convolution's output with its 2 x 2 sub-pixels still apart; this pass interleaves them into NCHW planes
 //   out[b][co][2 y + dy][2 x + dx] = U[b][(2 dy + dx) * C + co][y * w + x]            (inverse: the other way round)
 // One thread: 8 consecutive x of one source row pair (dx = 0, 1) <-> 16 consecutive output pixels (16-byte accesses).
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 ps_bf16x8;
-// `add` (forward only, planes-shaped bf16 or null): dst = interleave(src) + add, rounded once - the `up(c2) + c1` of
-// vit_adapter.py:107 in the precision autocast gives it (two bf16 tensors summed into bf16)
-template <bool INVERSE>
-__global__ __launch_bounds__(256) void pixel_shuffle2_kernel(const __bf16 *__restrict__ src, __bf16 *__restrict__ dst,
-                                                             const __bf16 *__restrict__ add, int B, int C, int h, int w,
+// `add` (forward only, planes-shaped, of type T, or null): dst = interleave(src) + add, rounded once - the `up(c2) + c1`
+// of vit_adapter.py:107 in the precision autocast gives it (two 16-bit tensors summed into one)
+template <typename T, bool INVERSE>
+__global__ __launch_bounds__(256) void pixel_shuffle2_kernel(const T *__restrict__ src, T *__restrict__ dst,
+                                                             const T *__restrict__ add, int B, int C, int h, int w,
                                                              int64_t items) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // (b, co, Y, x8)
     if (i >= items) return;
@@ -664,34 +688,195 @@ __global__ __launch_bounds__(256) void pixel_shuffle2_kernel(const __bf16 *__res
     const int64_t u1 = u0 + (int64_t)C * h * w;                                                                  // dx = 1 row
     const int64_t o = (((int64_t)b * C + co) * (2 * h) + Y) * (2 * (int64_t)w) + 16 * x8;
     if (!INVERSE) {
-        const ps_bf16x8 a = *reinterpret_cast<const ps_bf16x8 *>(src + u0), c = *reinterpret_cast<const ps_bf16x8 *>(src + u1);
-        ps_bf16x8 lo, hi;
+        const vec8<T> a = *reinterpret_cast<const vec8<T> *>(src + u0), c = *reinterpret_cast<const vec8<T> *>(src + u1);
+        vec8<T> lo, hi;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             lo[2 * j] = a[j], lo[2 * j + 1] = c[j];
             hi[2 * j] = a[4 + j], hi[2 * j + 1] = c[4 + j];
         }
         if (add) {
-            const ps_bf16x8 p = *reinterpret_cast<const ps_bf16x8 *>(add + o), q = *reinterpret_cast<const ps_bf16x8 *>(add + o + 8);
+            const vec8<T> p = *reinterpret_cast<const vec8<T> *>(add + o), q = *reinterpret_cast<const vec8<T> *>(add + o + 8);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                lo[j] = (__bf16)((float)lo[j] + (float)p[j]);
-                hi[j] = (__bf16)((float)hi[j] + (float)q[j]);
+                lo[j] = (T)((float)lo[j] + (float)p[j]);
+                hi[j] = (T)((float)hi[j] + (float)q[j]);
             }
         }
-        *reinterpret_cast<ps_bf16x8 *>(dst + o) = lo;
-        *reinterpret_cast<ps_bf16x8 *>(dst + o + 8) = hi;
+        *reinterpret_cast<vec8<T> *>(dst + o) = lo;
+        *reinterpret_cast<vec8<T> *>(dst + o + 8) = hi;
     } else {
-        const ps_bf16x8 lo = *reinterpret_cast<const ps_bf16x8 *>(src + o), hi = *reinterpret_cast<const ps_bf16x8 *>(src + o + 8);
-        ps_bf16x8 a, c;
+        const vec8<T> lo = *reinterpret_cast<const vec8<T> *>(src + o), hi = *reinterpret_cast<const vec8<T> *>(src + o + 8);
+        vec8<T> a, c;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             a[j] = lo[2 * j], c[j] = lo[2 * j + 1];
             a[4 + j] = hi[2 * j], c[4 + j] = hi[2 * j + 1];
         }
-        *reinterpret_cast<ps_bf16x8 *>(dst + u0) = a;
-        *reinterpret_cast<ps_bf16x8 *>(dst + u1) = c;
+        *reinterpret_cast<vec8<T> *>(dst + u0) = a;
+        *reinterpret_cast<vec8<T> *>(dst + u1) = c;
     }
+}
+
+// One entry / launch template per pair of entry points (bf16 | `_f16`): checks, messages (function name apart), launch
+// geometry, LDS and workspaces are the same code; T picks the kernel instantiation and the profiler row.
+template <typename T>
+int tail_stats_launch(const char *fn, const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale, int64_t N,
+                      int64_t C, int64_t H, int64_t W, const float *shift, float *sums, float *ws, void *stream) {
+    clear_error();
+    Operands o;
+    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
+    if (!sums || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    o.shift = shift;
+    hipStream_t st = (hipStream_t)stream;
+    const int nparts = (int)N * o.chunks;
+    LaunchScope scope(tname<T>("bn_tail_stats", "bn_tail_stats_f16"),
+                      N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0)), st);
+    hipLaunchKernelGGL(tail_stats_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, ws);
+    hipLaunchKernelGGL(tail_finalize, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, ws, nparts, (int)(2 * C), sums);
+    return check_launch(fn);
+}
+
+template <typename T>
+int tail_apply_launch(const char *fn, const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale, int64_t N,
+                      int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd, const float *gamma,
+                      const float *beta, int relu, const float *shift, void *y, int y_bf16, void *stream) {
+    clear_error();
+    Operands o;
+    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
+    if (!mean || !rstd || !y) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if ((uintptr_t)y % (y_bf16 ? 8 : 16)) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    o.relu = relu != 0;
+    o.y_bf16 = y_bf16 != 0;
+    o.shift = shift;
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("bn_tail_apply", "bn_tail_apply_f16"),
+                      N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0) + 4), st);
+    hipLaunchKernelGGL(tail_apply_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, mean, rstd, gamma, beta, y);
+    return check_launch(fn);
+}
+
+template <typename T>
+int tail_bwd_stats_launch(const char *fn, const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale,
+                          int64_t N, int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd,
+                          const float *gamma, const float *beta, int relu, const float *shift, const void *dy, int dy_bf16,
+                          float *sums, float *ws, void *stream) {
+    clear_error();
+    Operands o;
+    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
+    if (!mean || !rstd || !dy || !sums || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if ((uintptr_t)dy % (dy_bf16 ? 8 : 16)) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    o.relu = relu != 0;
+    o.dy_bf16 = dy_bf16 != 0;
+    o.shift = shift;
+    hipStream_t st = (hipStream_t)stream;
+    const int nparts = (int)N * o.chunks;
+    LaunchScope scope(tname<T>("bn_tail_bwd_stats", "bn_tail_bwd_stats_f16"),
+                      N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0) + 4), st);
+    hipLaunchKernelGGL(tail_bwd_stats_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, mean, rstd, gamma, beta,
+                       dy, ws);
+    hipLaunchKernelGGL(tail_finalize, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, ws, nparts, (int)(2 * C), sums);
+    return check_launch(fn);
+}
+
+template <typename T>
+int tail_bwd_apply_launch(const char *fn, const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale,
+                          int64_t N, int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd,
+                          const float *gamma, const float *beta, int relu, const float *shift, const void *dy, int dy_bf16,
+                          const float *mdy, const float *mdyx, void *da, void *db, float *dxlo, void *stream) {
+    clear_error();
+    Operands o;
+    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
+    if (!mean || !rstd || !dy || !mdy || !mdyx) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if ((uintptr_t)dy % (dy_bf16 ? 8 : 16) || (uintptr_t)dxlo % 16 || ((uintptr_t)da | (uintptr_t)db) % 8)
+        return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    o.relu = relu != 0;
+    o.dy_bf16 = dy_bf16 != 0;
+    o.shift = shift;
+    hipStream_t st = (hipStream_t)stream;
+    size_t smem = 0;
+    if (dxlo && x && scale > 1) smem = (size_t)o.rows_per_block * (o.W + o.Wl) * sizeof(float);
+    LaunchScope scope(tname<T>("bn_tail_bwd_apply", "bn_tail_bwd_apply_f16"),
+                      N * C * H * W * (2 * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0)) + 4), st);
+    if (smem > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)tail_bwd_apply_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(tail_bwd_apply_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), smem, st, o, mean, rstd, gamma,
+                       beta, dy, mdy, mdyx, da, db, dxlo);
+    return check_launch(fn);
+}
+
+template <typename T>
+int transpose_tokens_launch(const char *fn, const void *src, int64_t B, int64_t T_total, int64_t t0, int64_t Tn, int64_t C,
+                            void *dst, int to_planes, int planes_bf16, const float *vec, void *stream) {
+    clear_error();
+    if (B < 0 || T_total < 0 || t0 < 0 || Tn < 0 || t0 + Tn > T_total || C < 1 || B > 65535 || C > 65535 * 32 || Tn >= ((int64_t)1 << 31))
+        return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (B == 0 || Tn == 0) return VAH_OK;
+    if (!src || !dst) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (to_planes && vec) return fail(VAH_E_UNSUPPORTED, "%s: vec only applies to planes -> tokens", fn);
+    const dim3 grid((unsigned)((Tn + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("transpose_tokens", "transpose_tokens_f16"), B * Tn * C * (4 + (planes_bf16 ? 2 : 4)), st);
+    if (to_planes)
+        hipLaunchKernelGGL((transpose_tokens_kernel<T, true>), grid, dim3(256), 0, st, src, dst, T_total, t0, (int)Tn, (int)C,
+                           planes_bf16, vec);
+    else
+        hipLaunchKernelGGL((transpose_tokens_kernel<T, false>), grid, dim3(256), 0, st, src, dst, T_total, t0, (int)Tn, (int)C,
+                           planes_bf16, vec);
+    return check_launch(fn);
+}
+
+template <typename T>
+int maxpool_fwd_launch(const char *fn, const void *x, int64_t planes, int64_t H, int64_t W, void *y, void *idx, void *stream) {
+    clear_error();
+    if (planes < 0 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, total = planes * Ho * Wo;
+    if (total == 0) return VAH_OK;
+    if (!x || !y || !idx) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("maxpool_fwd", "maxpool_fwd_f16"), planes * (H * W * 2 + Ho * Wo * 3), st);
+    if (planes > 65535 || (Ho + 3) / 4 > 65535) return fail(VAH_E_SHAPE, "%s: too many planes / rows", fn);
+    hipLaunchKernelGGL(maxpool3s2_fwd_kernel<T>, dim3((unsigned)((Wo + 63) / 64), (unsigned)((Ho + 3) / 4), (unsigned)planes),
+                       dim3(256), 0, st, (const T *)x, (int)H, (int)W, (int)Ho, (int)Wo, (T *)y, (unsigned char *)idx);
+    return check_launch(fn);
+}
+
+template <typename T>
+int maxpool_bwd_launch(const char *fn, const void *gy, const void *idx, int64_t planes, int64_t H, int64_t W, void *gx,
+                       void *stream) {
+    clear_error();
+    if (planes < 0 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, total = planes * H * W;
+    if (total == 0) return VAH_OK;
+    if (!gy || !idx || !gx) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("maxpool_bwd", "maxpool_bwd_f16"), planes * (H * W * 2 + Ho * Wo * 3), st);
+    if (planes > 65535 || (H + 3) / 4 > 65535) return fail(VAH_E_SHAPE, "%s: too many planes / rows", fn);
+    if ((uintptr_t)gx % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    hipLaunchKernelGGL(maxpool3s2_bwd_kernel<T>, dim3((unsigned)((W + 511) / 512), (unsigned)((H + 3) / 4), (unsigned)planes),
+                       dim3(256), 0, st, (const T *)gy, (const unsigned char *)idx, (int)H, (int)W, (int)Ho, (int)Wo, (T *)gx);
+    return check_launch(fn);
+}
+
+template <typename T>
+int pixel_shuffle2_launch(const char *fn, const void *src, int64_t B, int64_t C, int64_t h, int64_t w, void *dst, int inverse,
+                          const void *add, void *stream) {
+    clear_error();
+    if (B < 0 || C < 1 || h < 1 || w < 8 || w % 8) return fail(VAH_E_SHAPE, "%s: w must be a multiple of 8", fn);
+    if (B == 0) return VAH_OK;
+    if (!src || !dst) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)src | (uintptr_t)dst) % 16) return fail(VAH_E_ALIGN, "%s: 16-byte alignment", fn);
+    const int64_t items = B * C * 2 * h * (w / 8);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("pixel_shuffle2", "pixel_shuffle2_f16"), B * C * 4 * h * w * 4, st);
+    if (add && (inverse || (uintptr_t)add % 16)) return fail(VAH_E_SHAPE, "%s: add is a forward-only, 16-byte aligned operand", fn);
+    if (inverse)
+        hipLaunchKernelGGL((pixel_shuffle2_kernel<T, true>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, (const T *)src,
+                           (T *)dst, (const T *)nullptr, (int)B, (int)C, (int)h, (int)w, items);
+    else
+        hipLaunchKernelGGL((pixel_shuffle2_kernel<T, false>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, (const T *)src,
+                           (T *)dst, (const T *)add, (int)B, (int)C, (int)h, (int)w, items);
+    return check_launch(fn);
 }
 
 }  // namespace
@@ -710,87 +895,54 @@ int vah_bn_tail_supported(int64_t N, int64_t C, int64_t H, int64_t W, int scale,
 
 int vah_bn_tail_stats(const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale, int64_t N,
                       int64_t C, int64_t H, int64_t W, const float *shift, float *sums, float *ws, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_bn_tail_stats";
-    Operands o;
-    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
-    if (!sums || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    o.shift = shift;
-    hipStream_t st = (hipStream_t)stream;
-    const int nparts = (int)N * o.chunks;
-    LaunchScope scope("bn_tail_stats", N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0)), st);
-    hipLaunchKernelGGL(tail_stats_kernel, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, ws);
-    hipLaunchKernelGGL(tail_finalize, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, ws, nparts, (int)(2 * C), sums);
-    return check_launch(fn);
+    return vah::tail_stats_launch<__bf16>("vah_bn_tail_stats", a, a_bf16, b, b_bf16, x, scale, N, C, H, W, shift, sums, ws, stream);
+}
+int vah_bn_tail_stats_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale, int64_t N,
+                          int64_t C, int64_t H, int64_t W, const float *shift, float *sums, float *ws, void *stream) {
+    return vah::tail_stats_launch<_Float16>("vah_bn_tail_stats_f16", a, a_f16, b, b_f16, x, scale, N, C, H, W, shift, sums, ws, stream);
 }
 
 int vah_bn_tail_apply(const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale, int64_t N,
                       int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd, const float *gamma,
                       const float *beta, int relu, const float *shift, void *y, int y_bf16, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_bn_tail_apply";
-    Operands o;
-    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
-    if (!mean || !rstd || !y) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if ((uintptr_t)y % (y_bf16 ? 8 : 16)) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    o.relu = relu != 0;
-    o.y_bf16 = y_bf16 != 0;
-    o.shift = shift;
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("bn_tail_apply", N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0) + 4), st);
-    hipLaunchKernelGGL(tail_apply_kernel, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, mean, rstd, gamma, beta, y);
-    return check_launch(fn);
+    return vah::tail_apply_launch<__bf16>("vah_bn_tail_apply", a, a_bf16, b, b_bf16, x, scale, N, C, H, W, mean, rstd, gamma, beta,
+                                          relu, shift, y, y_bf16, stream);
+}
+int vah_bn_tail_apply_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale, int64_t N,
+                          int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd, const float *gamma,
+                          const float *beta, int relu, const float *shift, void *y, int y_f16, void *stream) {
+    return vah::tail_apply_launch<_Float16>("vah_bn_tail_apply_f16", a, a_f16, b, b_f16, x, scale, N, C, H, W, mean, rstd, gamma,
+                                            beta, relu, shift, y, y_f16, stream);
 }
 
 int vah_bn_tail_bwd_stats(const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale, int64_t N,
                           int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd, const float *gamma,
                           const float *beta, int relu, const float *shift, const void *dy, int dy_bf16, float *sums,
                           float *ws, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_bn_tail_bwd_stats";
-    Operands o;
-    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
-    if (!mean || !rstd || !dy || !sums || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if ((uintptr_t)dy % (dy_bf16 ? 8 : 16)) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    o.relu = relu != 0;
-    o.dy_bf16 = dy_bf16 != 0;
-    o.shift = shift;
-    hipStream_t st = (hipStream_t)stream;
-    const int nparts = (int)N * o.chunks;
-    LaunchScope scope("bn_tail_bwd_stats", N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0) + 4), st);
-    hipLaunchKernelGGL(tail_bwd_stats_kernel, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, mean, rstd, gamma, beta,
-                       dy, ws);
-    hipLaunchKernelGGL(tail_finalize, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, ws, nparts, (int)(2 * C), sums);
-    return check_launch(fn);
+    return vah::tail_bwd_stats_launch<__bf16>("vah_bn_tail_bwd_stats", a, a_bf16, b, b_bf16, x, scale, N, C, H, W, mean, rstd, gamma,
+                                              beta, relu, shift, dy, dy_bf16, sums, ws, stream);
+}
+int vah_bn_tail_bwd_stats_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale, int64_t N,
+                              int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd, const float *gamma,
+                              const float *beta, int relu, const float *shift, const void *dy, int dy_f16, float *sums,
+                              float *ws, void *stream) {
+    return vah::tail_bwd_stats_launch<_Float16>("vah_bn_tail_bwd_stats_f16", a, a_f16, b, b_f16, x, scale, N, C, H, W, mean, rstd,
+                                                gamma, beta, relu, shift, dy, dy_f16, sums, ws, stream);
 }
 
 int vah_bn_tail_bwd_apply(const void *a, int a_bf16, const void *b, int b_bf16, const float *x, int scale, int64_t N,
                           int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd, const float *gamma,
                           const float *beta, int relu, const float *shift, const void *dy, int dy_bf16, const float *mdy,
                           const float *mdyx, void *da, void *db, float *dxlo, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_bn_tail_bwd_apply";
-    Operands o;
-    if (int rc = fill_operands(fn, o, a, a_bf16, b, b_bf16, x, scale, N, C, H, W)) return rc;
-    if (!mean || !rstd || !dy || !mdy || !mdyx) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if ((uintptr_t)dy % (dy_bf16 ? 8 : 16) || (uintptr_t)dxlo % 16 || ((uintptr_t)da | (uintptr_t)db) % 8)
-        return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    o.relu = relu != 0;
-    o.dy_bf16 = dy_bf16 != 0;
-    o.shift = shift;
-    hipStream_t st = (hipStream_t)stream;
-    size_t smem = 0;
-    if (dxlo && x && scale > 1) smem = (size_t)o.rows_per_block * (o.W + o.Wl) * sizeof(float);
-    LaunchScope scope("bn_tail_bwd_apply", N * C * H * W * (2 * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0)) + 4), st);
-    if (smem > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)tail_bwd_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(tail_bwd_apply_kernel, dim3((unsigned)(N * C * o.chunks)), dim3(256), smem, st, o, mean, rstd, gamma,
-                       beta, dy, mdy, mdyx, da, db, dxlo);
-    return check_launch(fn);
+    return vah::tail_bwd_apply_launch<__bf16>("vah_bn_tail_bwd_apply", a, a_bf16, b, b_bf16, x, scale, N, C, H, W, mean, rstd, gamma,
+                                              beta, relu, shift, dy, dy_bf16, mdy, mdyx, da, db, dxlo, stream);
+}
+int vah_bn_tail_bwd_apply_f16(const void *a, int a_f16, const void *b, int b_f16, const float *x, int scale, int64_t N,
+                              int64_t C, int64_t H, int64_t W, const float *mean, const float *rstd, const float *gamma,
+                              const float *beta, int relu, const float *shift, const void *dy, int dy_f16, const float *mdy,
+                              const float *mdyx, void *da, void *db, float *dxlo, void *stream) {
+    return vah::tail_bwd_apply_launch<_Float16>("vah_bn_tail_bwd_apply_f16", a, a_f16, b, b_f16, x, scale, N, C, H, W, mean, rstd,
+                                                gamma, beta, relu, shift, dy, dy_f16, mdy, mdyx, da, db, dxlo, stream);
 }
 
 // sums = [sum (C) | sum of squares (C) | element count (1)] (as written by vah_bn_tail_stats plus the
@@ -810,92 +962,46 @@ int vah_bn_finalize_stats(const float *sums, int64_t C, float eps, float momentu
 
 // tokens -> planes (to_planes != 0): dst (B, C, T) <- src (B, T_total, C)[:, t0 : t0 + T, :];
 // planes -> tokens: dst (B, T_total, C)[:, t0 : t0 + T, :] <- src (B, C, T) (+ vec[C] if given).
-// Tokens are fp32; the planes fp32 or bf16 (planes_bf16).
+// Tokens are fp32; the planes fp32 or 16-bit (planes_bf16: bf16, or fp16 for the `_f16` entry).
 // Replaces  c[:, a:b].transpose(1, 2).view(B, C, H, W).contiguous()  of the pyramid assembly
 // (vit_adapter.py:113-119) and  cat([fc_l(c_l).flatten(2).transpose(1, 2) + level_embed[l]])  of
 // vit_adapter.py:94-97 / adapter_modules.py:262-268, and their backward passes.
 int vah_transpose_tokens(const void *src, int64_t B, int64_t T_total, int64_t t0, int64_t T, int64_t C, void *dst,
                          int to_planes, int planes_bf16, const float *vec, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_transpose_tokens";
-    if (B < 0 || T_total < 0 || t0 < 0 || T < 0 || t0 + T > T_total || C < 1 || B > 65535 || C > 65535 * 32 || T >= ((int64_t)1 << 31))
-        return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (B == 0 || T == 0) return VAH_OK;
-    if (!src || !dst) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (to_planes && vec) return fail(VAH_E_UNSUPPORTED, "%s: vec only applies to planes -> tokens", fn);
-    const dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("transpose_tokens", B * T * C * (4 + (planes_bf16 ? 2 : 4)), st);
-    if (to_planes)
-        hipLaunchKernelGGL(transpose_tokens_kernel<true>, grid, dim3(256), 0, st, src, dst, T_total, t0, (int)T, (int)C,
-                           planes_bf16, vec);
-    else
-        hipLaunchKernelGGL(transpose_tokens_kernel<false>, grid, dim3(256), 0, st, src, dst, T_total, t0, (int)T, (int)C,
-                           planes_bf16, vec);
-    return check_launch(fn);
+    return vah::transpose_tokens_launch<__bf16>("vah_transpose_tokens", src, B, T_total, t0, T, C, dst, to_planes, planes_bf16, vec,
+                                                stream);
+}
+int vah_transpose_tokens_f16(const void *src, int64_t B, int64_t T_total, int64_t t0, int64_t T, int64_t C, void *dst,
+                             int to_planes, int planes_f16, const float *vec, void *stream) {
+    return vah::transpose_tokens_launch<_Float16>("vah_transpose_tokens_f16", src, B, T_total, t0, T, C, dst, to_planes, planes_f16,
+                                                  vec, stream);
 }
 
-// MaxPool2d(3, stride 2, padding 1) on bf16 NCHW (planes = N * C): y, idx (1 byte per output: window position
+// MaxPool2d(3, stride 2, padding 1) on 16-bit NCHW (planes = N * C): y, idx (1 byte per output: window position
 // of the first maximum) <- x;  backward: gx <- gy, idx (gather, no atomics).
 int vah_maxpool3s2_fwd_bf16(const void *x, int64_t planes, int64_t H, int64_t W, void *y, void *idx, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_maxpool3s2_fwd_bf16";
-    if (planes < 0 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, total = planes * Ho * Wo;
-    if (total == 0) return VAH_OK;
-    if (!x || !y || !idx) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("maxpool_fwd", planes * (H * W * 2 + Ho * Wo * 3), st);
-    if (planes > 65535 || (Ho + 3) / 4 > 65535) return fail(VAH_E_SHAPE, "%s: too many planes / rows", fn);
-    hipLaunchKernelGGL(maxpool3s2_fwd_kernel, dim3((unsigned)((Wo + 63) / 64), (unsigned)((Ho + 3) / 4), (unsigned)planes),
-                       dim3(256), 0, st, (const __bf16 *)x, (int)H, (int)W, (int)Ho, (int)Wo, (__bf16 *)y,
-                       (unsigned char *)idx);
-    return check_launch(fn);
+    return vah::maxpool_fwd_launch<__bf16>("vah_maxpool3s2_fwd_bf16", x, planes, H, W, y, idx, stream);
+}
+int vah_maxpool3s2_fwd_f16(const void *x, int64_t planes, int64_t H, int64_t W, void *y, void *idx, void *stream) {
+    return vah::maxpool_fwd_launch<_Float16>("vah_maxpool3s2_fwd_f16", x, planes, H, W, y, idx, stream);
 }
 
 int vah_maxpool3s2_bwd_bf16(const void *gy, const void *idx, int64_t planes, int64_t H, int64_t W, void *gx, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_maxpool3s2_bwd_bf16";
-    if (planes < 0 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, total = planes * H * W;
-    if (total == 0) return VAH_OK;
-    if (!gy || !idx || !gx) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("maxpool_bwd", planes * (H * W * 2 + Ho * Wo * 3), st);
-    if (planes > 65535 || (H + 3) / 4 > 65535) return fail(VAH_E_SHAPE, "%s: too many planes / rows", fn);
-    if ((uintptr_t)gx % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    hipLaunchKernelGGL(maxpool3s2_bwd_kernel, dim3((unsigned)((W + 511) / 512), (unsigned)((H + 3) / 4), (unsigned)planes),
-                       dim3(256), 0, st, (const __bf16 *)gy, (const unsigned char *)idx, (int)H, (int)W, (int)Ho, (int)Wo,
-                       (__bf16 *)gx);
-    return check_launch(fn);
+    return vah::maxpool_bwd_launch<__bf16>("vah_maxpool3s2_bwd_bf16", gy, idx, planes, H, W, gx, stream);
+}
+int vah_maxpool3s2_bwd_f16(const void *gy, const void *idx, int64_t planes, int64_t H, int64_t W, void *gx, void *stream) {
+    return vah::maxpool_bwd_launch<_Float16>("vah_maxpool3s2_bwd_f16", gy, idx, planes, H, W, gx, stream);
 }
 
-
 /* inverse == 0: planes (B, C, 2h, 2w) <- U (B, 4*C, h*w), rows (dy, dx, co) [+ add, planes-shaped, optional];
- * inverse != 0: U <- planes.  bf16, w % 8 == 0. */
+ * inverse != 0: U <- planes.  bf16 (fp16: the `_f16` entry), w % 8 == 0. */
 int vah_pixel_shuffle2_bf16(const void *src, int64_t B, int64_t C, int64_t h, int64_t w, void *dst, int inverse, const void *add,
                             void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_pixel_shuffle2_bf16";
-    if (B < 0 || C < 1 || h < 1 || w < 8 || w % 8) return fail(VAH_E_SHAPE, "%s: w must be a multiple of 8", fn);
-    if (B == 0) return VAH_OK;
-    if (!src || !dst) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)src | (uintptr_t)dst) % 16) return fail(VAH_E_ALIGN, "%s: 16-byte alignment", fn);
-    const int64_t items = B * C * 2 * h * (w / 8);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("pixel_shuffle2", B * C * 4 * h * w * 4, st);
-    if (add && (inverse || (uintptr_t)add % 16)) return fail(VAH_E_SHAPE, "%s: add is a forward-only, 16-byte aligned operand", fn);
-    if (inverse)
-        hipLaunchKernelGGL(pixel_shuffle2_kernel<true>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, (const __bf16 *)src,
-                           (__bf16 *)dst, (const __bf16 *)nullptr, (int)B, (int)C, (int)h, (int)w, items);
-    else
-        hipLaunchKernelGGL(pixel_shuffle2_kernel<false>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, (const __bf16 *)src,
-                           (__bf16 *)dst, (const __bf16 *)add, (int)B, (int)C, (int)h, (int)w, items);
-    return check_launch(fn);
+    return vah::pixel_shuffle2_launch<__bf16>("vah_pixel_shuffle2_bf16", src, B, C, h, w, dst, inverse, add, stream);
+}
+int vah_pixel_shuffle2_f16(const void *src, int64_t B, int64_t C, int64_t h, int64_t w, void *dst, int inverse, const void *add,
+                           void *stream) {
+    return vah::pixel_shuffle2_launch<_Float16>("vah_pixel_shuffle2_f16", src, B, C, h, w, dst, inverse, add, stream);
 }
 
 }  // extern "C"

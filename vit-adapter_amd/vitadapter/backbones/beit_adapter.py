@@ -101,9 +101,10 @@ class BEiTAdapter(BEiT):
         if self.add_vit_feature:
             x1, x2, x3, x4 = outs
             c4 = c4 + fused.halve(x4)
-            # GEMM form on the token rows, c1 summed in by its interleave pass (one bf16 operand for the tail instead of two)
-            up = fused.up_from_tokens(self.up, c[:, :4 * H * W], 2 * H, 2 * W, c1 if c1.dtype == torch.bfloat16 else None) if fold else None
-            if up is not None and c1.dtype == torch.bfloat16:
+            # GEMM form on the token rows, c1 summed in by its interleave pass (one 16-bit operand for the tail instead of two)
+            add = c1 if c1.dtype == fused.tail_dtype() else None
+            up = fused.up_from_tokens(self.up, c[:, :4 * H * W], 2 * H, 2 * W, add) if fold else None
+            if up is not None and add is not None:
                 c1 = None
             if up is None:
                 up = F.conv_transpose2d(c2, self.up.weight, None, stride=2) if fold else self.up(c2)

@@ -257,8 +257,9 @@ class BEiTAdapter(BEiT):
             else:
                 x1 = x2 = x3 = x4 = fused.tokens_to_maps(x, [(H, W)])[0]
             c4 = c4 + fused.halve(x4)
-            up = fused.up_from_tokens(self.up, c[:, :4 * H * W], 2 * H, 2 * W, c1 if c1.dtype == torch.bfloat16 else None) if fold else None
-            if up is not None and c1.dtype == torch.bfloat16:
+            add = c1 if c1.dtype == fused.tail_dtype() else None     # the 16-bit c1 is summed in by the interleave pass
+            up = fused.up_from_tokens(self.up, c[:, :4 * H * W], 2 * H, 2 * W, add) if fold else None
+            if up is not None and add is not None:
                 c1 = None
             if up is None:
                 up = F.conv_transpose2d(c2, self.up.weight, None, stride=2) if fold else self.up(c2)

@@ -126,8 +126,8 @@ class ViTAdapter(TIMMVisionTransformer):
         # fused tail: the biases of spm.fc1 and self.up reach norm1 as a per-channel shift
         fold = self.add_vit_feature and fused.tail_takes_conv_bias(self.norm1, x)
         if spm_nhwc.takes(self.spm, x, fold):
-            # the whole module on NHWC bf16 (fp16 under fp16 autocast, where the tail is torch's and c1 carries fc1's bias)
-            # with its own convolution kernels; its stride-8/16/32 maps are the token rows
+            # the whole module on NHWC bf16 (fp16 under fp16 autocast) with its own convolution kernels; its stride-8/16/32
+            # maps are the token rows.  c1 carries fc1's bias only where the tail does not take it (fp16 with fp16_tail off)
             c1, c = spm_nhwc.forward(self.spm, x, self.level_embed, c1_bias=not fold)
         elif fused.ENABLED['maps'] and fused.ENABLED['maps_in'] and x.is_cuda:
             # c2..c4 leave the SPM as bias-free maps; bias + level embedding are added while the token
@@ -158,12 +158,13 @@ class ViTAdapter(TIMMVisionTransformer):
             else:
                 x1 = x2 = x3 = x4 = fused.tokens_to_maps(x, [(H, W)])[0]
             # f1 = norm1(up(c2) + c1 + interp(x1, 4)), f2 = norm2(c2 + interp(x2, 2)), f3 = norm3(c3 + x3):
-            # sum, upsampling and batch norm in one pair of passes (csrc/tail_ops.hip); off the bf16
+            # sum, upsampling and batch norm in one pair of passes (csrc/tail_ops.hip); off the bf16 / fp16
             # GPU path fused.bn_tail evaluates exactly the reference expression
             c4 = c4 + fused.halve(x4)
-            # GEMM form on the token rows, c1 summed in by its interleave pass (one bf16 operand for the tail instead of two)
-            up = fused.up_from_tokens(self.up, c[:, :4 * H * W], 2 * H, 2 * W, c1 if c1.dtype == torch.bfloat16 else None) if fold else None
-            if up is not None and c1.dtype == torch.bfloat16:
+            # GEMM form on the token rows, c1 summed in by its interleave pass (one 16-bit operand for the tail instead of two)
+            add = c1 if c1.dtype == fused.tail_dtype() else None
+            up = fused.up_from_tokens(self.up, c[:, :4 * H * W], 2 * H, 2 * W, add) if fold else None
+            if up is not None and add is not None:
                 c1 = None
             if up is None:
                 up = F.conv_transpose2d(c2, self.up.weight, None, stride=2) if fold else self.up(c2)

@@ -8,8 +8,9 @@ residual stream, bf16 branch outputs) and otherwise evaluates the same expressio
 The row-streaming operators - LayerNorm (plain, keep, dual), residual, residual + LayerNorm, the token
 DWConv - also take fp16 autocast (the reference's AMP mode): the same kernels instantiated on fp16
 (`*_f16` entry points), fp32 math, fp32 -> fp16 rounded to nearest even with overflow to inf and
-subnormals kept.  Linear, conv1x1, patch embedding, up_from_tokens, the BN tail and the MSDA pair core
-stay bf16-only; under fp16 autocast they are torch's.
+subnormals kept.  So does the output tail (csrc/tail_ops.hip: the BatchNorm tail, bn_relu, halve, the token <-> plane
+transposes, the NCHW max-pool and up_from_tokens, whose two products are torch's fp16 library GEMMs).  Linear, conv1x1,
+patch embedding and the MSDA pair core stay bf16-only; under fp16 autocast they are torch's.
 """
 import os
 
@@ -20,7 +21,7 @@ import _vah
 
 ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln': True, 'dwconv': True, 'linear': True, 'bn_tail': True,
            'bn_relu': True, 'bias_fold': True, 'keep_feat': True, 'maps': True, 'maps_in': True, 'linear_pair': True, 'maxpool': True, 'conv1x1': True, 'ln_dual': True, 'wgrad_fin': True, 'spm_nhwc': True, 'up_gemm': True, 'patch_gemm': True, 'wgrad_overlap': True, 'drop_pool': True,
-           'fp16_rows': True, 'fp16_spm': True, 'bias_partials': True}
+           'fp16_rows': True, 'fp16_spm': True, 'fp16_tail': True, 'bias_partials': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -57,7 +58,24 @@ def _autocast_16():
 
 def _sym(name, dtype):
     """The entry point ``name`` (its bf16 spelling) for 16-bit operands of ``dtype``: itself or its `_f16` twin."""
-    return getattr(_vah.lib, name if dtype == torch.bfloat16 else _vah.FUSED_F16_TWINS[name])
+    if dtype == torch.bfloat16:
+        return getattr(_vah.lib, name)
+    return getattr(_vah.lib, _vah.FUSED_F16_TWINS[name] if name in _vah.FUSED_F16_TWINS else _vah.TAIL_F16_TWINS[name])
+
+
+def _tail_dtype():
+    """The 16-bit type the output-tail kernels (csrc/tail_ops.hip) read and write under the active autocast:
+    torch.bfloat16, torch.float16, or None (no autocast, another autocast type, or fp16 with its switch off:
+    VAH_FUSED_DISABLE=fp16_tail, the torch expressions under fp16 autocast, for A/B runs)."""
+    if not torch.is_autocast_enabled():
+        return None
+    dtype = torch.get_autocast_dtype('cuda')
+    return dtype if dtype == torch.bfloat16 or (dtype == torch.float16 and ENABLED['fp16_tail']) else None
+
+
+def tail_dtype():
+    """Public spelling of _tail_dtype() for the backbones: the dtype of a ``c1`` that up_from_tokens can sum in."""
+    return _tail_dtype()
 
 
 class _LayerNormBF16(torch.autograd.Function):
@@ -934,67 +952,80 @@ class _Conv1x1BF16(torch.autograd.Function):
 
 class _UpFromTokens(torch.autograd.Function):
     """ConvTranspose2d(C, Co, kernel 2, stride 2) WITHOUT bias applied to a map given as its token rows:
-    rows (B, h*w, C) -> NCHW planes (B, Co, 2h, 2w) bf16.  The transposed convolution with stride = kernel is a plain
+    rows (B, h*w, C) -> NCHW planes (B, Co, 2h, 2w) in ``t16`` (bf16 | fp16).  The transposed convolution with stride = kernel is a plain
     GEMM per image, U_b (4*Co, h*w) = Wcat (4*Co, C) rows_b^T with Wcat rows (dy, dx, co), followed by the 2 x 2 sub-pixel
     interleave (csrc/tail_ops.hip::pixel_shuffle2); the backward is the inverse interleave and two GEMMs.  MIOpen's
-    NCHW transposed convolution took 494 + 846 us for this layer at base_det (2 x 768 x 128 x 128)."""
+    NCHW transposed convolution took 494 + 846 us for this layer at base_det (2 x 768 x 128 x 128).
+    bf16: the products are gemm_bf16.  fp16: they are torch's fp16 library GEMMs on the token rows, as every Linear in
+    that mode; dW is what autocast gives conv_transpose2d - fp16 products per image, summed over the images in fp32."""
 
     @staticmethod
-    def forward(ctx, rows, weight, h, w, addend):
+    def forward(ctx, rows, weight, h, w, addend, t16):
         B, T, C = rows.shape
         Co = weight.shape[1]
-        xb = rows.detach().to(torch.bfloat16).contiguous()
-        wc = BF16_COPIES.get(weight).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()       # rows (dy, dx, co)
-        U = torch.empty((B, 4 * Co, T), dtype=torch.bfloat16, device=rows.device)
-        for b in range(B):
-            gemm_bf16(wc, xb[b], trans_b=True, out=U[b])
-        out = torch.empty((B, Co, 2 * h, 2 * w), dtype=torch.bfloat16, device=rows.device)
+        xb = rows.detach().to(t16).contiguous()
+        if t16 == torch.bfloat16:
+            wc = BF16_COPIES.get(weight).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()       # rows (dy, dx, co)
+            U = torch.empty((B, 4 * Co, T), dtype=torch.bfloat16, device=rows.device)
+            for b in range(B):
+                gemm_bf16(wc, xb[b], trans_b=True, out=U[b])
+        else:
+            wc = weight.detach().to(t16).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()
+            U = torch.bmm(wc.unsqueeze(0).expand(B, 4 * Co, C), xb.transpose(1, 2))
+        out = torch.empty((B, Co, 2 * h, 2 * w), dtype=t16, device=rows.device)
         add = addend.contiguous() if addend is not None else None
         with _vah.on(rows.device):
-            _vah.check(_vah.lib.vah_pixel_shuffle2_bf16(U.data_ptr(), B, Co, h, w, out.data_ptr(), 0,
-                                                        add.data_ptr() if add is not None else None, _stream(rows)), 'pixel_shuffle2')
+            _vah.check(_sym('vah_pixel_shuffle2_bf16', t16)(U.data_ptr(), B, Co, h, w, out.data_ptr(), 0,
+                                                            add.data_ptr() if add is not None else None, _stream(rows)), 'pixel_shuffle2')
         ctx.save_for_backward(xb, wc)
-        ctx.meta = (h, w, Co, rows.dtype)
+        ctx.meta = (h, w, Co, rows.dtype, t16)
         return out
 
     @staticmethod
     def backward(ctx, g):
         xb, wc = ctx.saved_tensors
-        h, w, Co, in_dtype = ctx.meta
+        h, w, Co, in_dtype, t16 = ctx.meta
         B, T, C = xb.shape
-        g = g.contiguous().to(torch.bfloat16)
-        dU = torch.empty((B, 4 * Co, T), dtype=torch.bfloat16, device=g.device)
+        g = g.contiguous().to(t16)
+        dU = torch.empty((B, 4 * Co, T), dtype=t16, device=g.device)
         with _vah.on(g.device):
-            _vah.check(_vah.lib.vah_pixel_shuffle2_bf16(g.data_ptr(), B, Co, h, w, dU.data_ptr(), 1, None, _stream(g)), 'pixel_shuffle2')
+            _vah.check(_sym('vah_pixel_shuffle2_bf16', t16)(g.data_ptr(), B, Co, h, w, dU.data_ptr(), 1, None, _stream(g)), 'pixel_shuffle2')
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty((B, T, C), dtype=torch.bfloat16, device=g.device)
-            for b in range(B):
-                gemm_bf16(dU[b], wc, trans_a=True, out=dx[b])
+            if t16 == torch.bfloat16:
+                dx = torch.empty((B, T, C), dtype=torch.bfloat16, device=g.device)
+                for b in range(B):
+                    gemm_bf16(dU[b], wc, trans_a=True, out=dx[b])
+            else:
+                dx = torch.matmul(dU.transpose(1, 2), wc)
             if dx.dtype != in_dtype:
                 dx = dx.to(in_dtype)
         if ctx.needs_input_grad[1]:
-            for b in range(B):
-                part = gemm_bf16(dU[b], xb[b], out_dtype=torch.float32)
-                dw = part if dw is None else dw.add_(part)
+            if t16 == torch.bfloat16:
+                for b in range(B):
+                    part = gemm_bf16(dU[b], xb[b], out_dtype=torch.float32)
+                    dw = part if dw is None else dw.add_(part)
+            else:
+                dw = torch.bmm(dU, xb).float().sum(0)
             dw = dw.view(2, 2, Co, C).permute(3, 2, 0, 1).contiguous()
-        return dx, dw, None, None, (g if ctx.needs_input_grad[4] else None)      # d(out)/d(addend) = identity
+        return dx, dw, None, None, (g if ctx.needs_input_grad[4] else None), None      # d(out)/d(addend) = identity
 
 
 def up_from_tokens(up, rows, h, w, addend=None):
     """``F.conv_transpose2d(rows.transpose(1, 2).view(B, C, h, w), up.weight, None, stride=2)`` for the backbone's
     2 x 2 / stride 2 ``up`` (vit_adapter.py:46), from the token rows of the map and without the bias (the caller folds
-    it into the BatchNorm tail); ``addend`` (planes-shaped bf16, e.g. c1) is summed in by the interleave pass -
-    ``up(c2) + c1`` rounded once to bf16, as autocast rounds the sum of two half tensors - so the tail reads one operand
-    instead of two.  None when the GEMM form does not apply."""
+    it into the BatchNorm tail); ``addend`` (planes-shaped, in the autocast's 16-bit type, e.g. c1) is summed in by the
+    interleave pass - ``up(c2) + c1`` rounded once, as autocast rounds the sum of two half tensors - so the tail reads one
+    operand instead of two.  bf16 or (ENABLED['fp16_tail']) fp16 autocast.  None when the GEMM form does not apply."""
     wt = up.weight
-    if (ENABLED['up_gemm'] and ENABLED['linear'] and rows.is_cuda and _bf16_autocast() and isinstance(up, torch.nn.ConvTranspose2d)
+    t16 = _tail_dtype()
+    if (ENABLED['up_gemm'] and ENABLED['linear'] and rows.is_cuda and t16 is not None and isinstance(up, torch.nn.ConvTranspose2d)
             and up.kernel_size == (2, 2) and up.stride == (2, 2) and up.padding == (0, 0) and up.output_padding == (0, 0)
             and up.groups == 1 and up.dilation == (1, 1) and wt.dtype == torch.float32 and rows.dim() == 3
             and rows.shape[1] == h * w and rows.shape[2] == wt.shape[0] and w % 8 == 0 and wt.shape[0] % 8 == 0
-            and wt.shape[1] % 8 == 0 and rows.dtype in (torch.float32, torch.bfloat16) and rows.numel() > 0
-            and (addend is None or (addend.dtype == torch.bfloat16 and tuple(addend.shape) == (rows.shape[0], wt.shape[1], 2 * h, 2 * w)))):
-        return _UpFromTokens.apply(rows, wt, h, w, addend)
+            and wt.shape[1] % 8 == 0 and rows.dtype in (torch.float32, t16) and rows.numel() > 0
+            and (addend is None or (addend.dtype == t16 and tuple(addend.shape) == (rows.shape[0], wt.shape[1], 2 * h, 2 * w)))):
+        return _UpFromTokens.apply(rows, wt, h, w, addend, t16)
     return None
 
 
@@ -1287,10 +1318,11 @@ def _sync_group(norm):
 
 class _BNTail(torch.autograd.Function):
     """y = [relu] BatchNorm(a + b + upsample(x)): statistics pass, one bookkeeping launch (mean, rstd,
-    running statistics), normalise pass; SyncBatchNorm all-reduces the sums in between."""
+    running statistics), normalise pass; SyncBatchNorm all-reduces the sums in between.  ``t16``: the 16-bit type of
+    the call (bf16 | fp16) - it picks the entry points, and an operand is either of that type or fp32."""
 
     @staticmethod
-    def forward(ctx, a, b, x, weight, bias, shift, norm, scale, relu, out_dtype):
+    def forward(ctx, a, b, x, weight, bias, shift, norm, scale, relu, out_dtype, t16):
         N, C, H, W = a.shape
         sh = shift.detach().float().contiguous() if shift is not None else None
         shp = sh.data_ptr() if sh is not None else None
@@ -1298,8 +1330,8 @@ class _BNTail(torch.autograd.Function):
         b = b.contiguous() if b is not None else None
         x = x.contiguous().float() if x is not None else None
         dev, st = a.device, _stream(a)
-        ops = (a.data_ptr(), int(a.dtype == torch.bfloat16), b.data_ptr() if b is not None else None,
-               int(b is not None and b.dtype == torch.bfloat16), x.data_ptr() if x is not None else None,
+        ops = (a.data_ptr(), int(a.dtype == t16), b.data_ptr() if b is not None else None,
+               int(b is not None and b.dtype == t16), x.data_ptr() if x is not None else None,
                scale, N, C, H, W)
         training = norm.training or norm.running_mean is None
         group = _sync_group(norm) if training else None
@@ -1309,7 +1341,7 @@ class _BNTail(torch.autograd.Function):
             if training:
                 sums = torch.empty(2 * C + 1, dtype=torch.float32, device=dev)
                 ws = torch.empty(_vah.lib.vah_bn_tail_ws_floats(C), dtype=torch.float32, device=dev)
-                _vah.check(_vah.lib.vah_bn_tail_stats(*ops, shp, sums.data_ptr(), ws.data_ptr(), st), 'bn_tail_stats')
+                _vah.check(_sym('vah_bn_tail_stats', t16)(*ops, shp, sums.data_ptr(), ws.data_ptr(), st), 'bn_tail_stats')
                 sums[2 * C:].fill_(float(N * H * W))
                 if group is not None:
                     import torch.distributed as dist
@@ -1330,35 +1362,35 @@ class _BNTail(torch.autograd.Function):
                 mean = norm.running_mean.float().contiguous()
                 rstd = torch.rsqrt(norm.running_var.float() + norm.eps)
             y = torch.empty((N, C, H, W), dtype=out_dtype, device=dev)
-            _vah.check(_vah.lib.vah_bn_tail_apply(
+            _vah.check(_sym('vah_bn_tail_apply', t16)(
                 *ops, mean.data_ptr(), rstd.data_ptr(), w.data_ptr() if w is not None else None,
                 bb.data_ptr() if bb is not None else None, int(relu), shp, y.data_ptr(),
-                int(out_dtype == torch.bfloat16), st), 'bn_tail_apply')
+                int(out_dtype == t16), st), 'bn_tail_apply')
         ctx.save_for_backward(a, b, x, mean, rstd, w, bb, count, sh)
-        ctx.meta = (scale, training, group, weight is not None, bias is not None, relu)
+        ctx.meta = (scale, training, group, weight is not None, bias is not None, relu, t16)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         a, b, x, mean, rstd, w, bb, count, sh = ctx.saved_tensors
-        scale, training, group, has_w, has_b, relu = ctx.meta
+        scale, training, group, has_w, has_b, relu, t16 = ctx.meta
         shp = sh.data_ptr() if sh is not None else None
         N, C, H, W = a.shape
         dy = dy.contiguous()
-        if dy.dtype not in (torch.float32, torch.bfloat16):
+        if dy.dtype not in (torch.float32, t16):
             dy = dy.float()
-        dy_bf16 = int(dy.dtype == torch.bfloat16)
+        dy_bf16 = int(dy.dtype == t16)      # "16-bit (t16) or fp32", as the entry points read the flag
         dev, st = a.device, _stream(a)
-        ops = (a.data_ptr(), int(a.dtype == torch.bfloat16), b.data_ptr() if b is not None else None,
-               int(b is not None and b.dtype == torch.bfloat16), x.data_ptr() if x is not None else None,
+        ops = (a.data_ptr(), int(a.dtype == t16), b.data_ptr() if b is not None else None,
+               int(b is not None and b.dtype == t16), x.data_ptr() if x is not None else None,
                scale, N, C, H, W)
         wp = w.data_ptr() if w is not None else None
         bp = bb.data_ptr() if bb is not None else None
         with _vah.on(dev):
             sums = torch.empty(2 * C, dtype=torch.float32, device=dev)
             ws = torch.empty(_vah.lib.vah_bn_tail_ws_floats(C), dtype=torch.float32, device=dev)
-            _vah.check(_vah.lib.vah_bn_tail_bwd_stats(*ops, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu), shp,
-                                                      dy.data_ptr(), dy_bf16, sums.data_ptr(), ws.data_ptr(), st),
+            _vah.check(_sym('vah_bn_tail_bwd_stats', t16)(*ops, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu), shp,
+                                                          dy.data_ptr(), dy_bf16, sums.data_ptr(), ws.data_ptr(), st),
                        'bn_tail_bwd_stats')
             local = sums.clone() if (training and group is not None) else sums      # dweight / dbias are per-rank sums
             dweight = local[C:] if has_w else None
@@ -1377,7 +1409,7 @@ class _BNTail(torch.autograd.Function):
             if x is not None and need_x:
                 dx = torch.zeros_like(x) if scale > 1 else torch.empty_like(x)
             if da is not None or db is not None or dx is not None:
-                _vah.check(_vah.lib.vah_bn_tail_bwd_apply(
+                _vah.check(_sym('vah_bn_tail_bwd_apply', t16)(
                     *ops, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu), shp, dy.data_ptr(), dy_bf16,
                     means[:C].data_ptr(), means[C:].data_ptr(),
                     da.data_ptr() if da is not None else None, db.data_ptr() if db is not None else None,
@@ -1387,12 +1419,15 @@ class _BNTail(torch.autograd.Function):
             # d/d(shift) = sum of dt over the channel: BatchNorm in training removes channel constants
             # (exactly 0); with running statistics it is gamma * rstd * sum(dy)
             dshift = torch.zeros_like(sh) if training else (w if w is not None else 1.0) * rstd * local[:C]
-        return da, db, dx, dweight, dbias, dshift, None, None, None, None
+        return da, db, dx, dweight, dbias, dshift, None, None, None, None, None
 
 
 def _bn_fusable(norm, a):
-    return (isinstance(norm, torch.nn.modules.batchnorm._BatchNorm) and a.is_cuda and _bf16_autocast()
-            and a.dim() == 4 and a.dtype in (torch.bfloat16, torch.float32) and a.shape[3] <= 8192
+    """bf16 autocast, or fp16 autocast with ENABLED['fp16_tail']; ``a`` in the autocast's 16-bit type or fp32 (a tensor
+    of the other 16-bit type takes the reference expression, nothing fused)."""
+    t16 = _tail_dtype()
+    return (isinstance(norm, torch.nn.modules.batchnorm._BatchNorm) and a.is_cuda and t16 is not None
+            and a.dim() == 4 and a.dtype in (t16, torch.float32) and a.shape[3] <= 8192
             and a.numel() > 0 and norm.momentum is not None
             and (not norm.training or a.shape[0] * a.shape[2] * a.shape[3] > 1)
             and (norm.training or norm.running_mean is not None)
@@ -1415,9 +1450,9 @@ def tail_takes_conv_bias(norm, ref):
 def halve(x):
     """``F.interpolate(x, scale_factor=0.5, mode='bilinear', align_corners=False)`` (vit_adapter.py:121).
     With even H, W the taps are (0.5, 0.5) in both directions: the 2x2 mean.  torch's bilinear
-    kernel parallelises over output pixels only (706 us for 2x768x32x32 on MI355X); on the bf16
-    GPU path the mean is taken with avg_pool2d, elsewhere the reference call is kept."""
-    if (ENABLED['bn_tail'] and x.is_cuda and _bf16_autocast() and x.dim() == 4 and x.shape[2] % 2 == 0
+    kernel parallelises over output pixels only (706 us for 2x768x32x32 on MI355X); on the bf16 (and,
+    ENABLED['fp16_tail'], fp16) GPU path the mean is taken with avg_pool2d, elsewhere the reference call is kept."""
+    if (ENABLED['bn_tail'] and x.is_cuda and _tail_dtype() is not None and x.dim() == 4 and x.shape[2] % 2 == 0
             and x.shape[3] % 2 == 0):
         return F.avg_pool2d(x.float(), 2)
     return F.interpolate(x, scale_factor=0.5, mode='bilinear', align_corners=False)
@@ -1428,12 +1463,13 @@ def bn_tail(norm, a, b=None, x=None, scale=1, shift=None):
     for a (Sync)BatchNorm2d ``norm`` - the output tail of the backbone (ref vit_adapter.py:106-127);
     ``b`` / ``x`` optional, ``scale == 1`` adds ``x`` as it is.  ``shift`` (C,): per-channel constant
     added to the sum (biases of the convolutions that made ``a`` / ``b``, applied here for free)."""
+    t16 = _tail_dtype()
     if (ENABLED['bn_tail'] and _bn_fusable(norm, a) and x is not None
-            and (b is None or (b.shape == a.shape and b.dtype in (torch.bfloat16, torch.float32)))
+            and (b is None or (b.shape == a.shape and b.dtype in (t16, torch.float32)))
             and scale in (1, 2, 4, 8) and a.shape[3] % (4 * scale) == 0 and a.shape[2] % scale == 0
             and tuple(x.shape) == (a.shape[0], a.shape[1], a.shape[2] // scale, a.shape[3] // scale)
-            and x.dtype in (torch.bfloat16, torch.float32) and _tail_shape_ok(a, scale, True)):
-        return _BNTail.apply(a, b, x, norm.weight, norm.bias, shift, norm, scale, False, torch.float32)
+            and x.dtype in (t16, torch.float32) and _tail_shape_ok(a, scale, True)):
+        return _BNTail.apply(a, b, x, norm.weight, norm.bias, shift, norm, scale, False, torch.float32, t16)
     t = a if b is None else a + b
     if shift is not None:
         t = t + shift.view(1, -1, 1, 1).to(t.dtype)
@@ -1452,7 +1488,7 @@ def bn_relu(norm, a):
     # the two-pass form pays from a few million elements on (below that MIOpen's single kernel wins)
     if (ENABLED['bn_relu'] and _bn_fusable(norm, a) and a.shape[3] % 4 == 0 and a.numel() >= BN_RELU_MIN_NUMEL
             and _tail_shape_ok(a, 1, False)):
-        return _BNTail.apply(a, None, None, norm.weight, norm.bias, None, norm, 1, True, a.dtype)
+        return _BNTail.apply(a, None, None, norm.weight, norm.bias, None, norm, 1, True, a.dtype, _tail_dtype())
     return F.relu(norm(a))
 
 
@@ -1466,18 +1502,18 @@ class _TokensToMaps(torch.autograd.Function):
     an add)."""
 
     @staticmethod
-    def forward(ctx, tokens, hw):
+    def forward(ctx, tokens, hw, t16):
         B, T, C = tokens.shape
         tokens = tokens.contiguous()
         outs, t0 = [], 0
         with _vah.on(tokens.device):
             for h, w in hw:
                 o = torch.empty((B, C, h, w), dtype=torch.float32, device=tokens.device)
-                _vah.check(_vah.lib.vah_transpose_tokens(tokens.data_ptr(), B, T, t0, h * w, C, o.data_ptr(), 1, 0, None,
-                                                         _stream(tokens)), 'transpose_tokens')
+                _vah.check(_sym('vah_transpose_tokens', t16)(tokens.data_ptr(), B, T, t0, h * w, C, o.data_ptr(), 1, 0, None,
+                                                             _stream(tokens)), 'transpose_tokens')
                 outs.append(o)
                 t0 += h * w
-        ctx.hw, ctx.shape = hw, (B, T, C)
+        ctx.hw, ctx.shape, ctx.t16 = hw, (B, T, C), t16
         ctx.set_materialize_grads(False)
         return tuple(outs)
 
@@ -1493,10 +1529,16 @@ class _TokensToMaps(torch.autograd.Function):
                     gt[:, t0:t0 + h * w].zero_()
                 else:
                     g = g.contiguous().float()
-                    _vah.check(_vah.lib.vah_transpose_tokens(g.data_ptr(), B, T, t0, h * w, C, gt.data_ptr(), 0, 0, None,
-                                                             _stream(g)), 'transpose_tokens')
+                    _vah.check(_sym('vah_transpose_tokens', ctx.t16)(g.data_ptr(), B, T, t0, h * w, C, gt.data_ptr(), 0, 0, None,
+                                                                     _stream(g)), 'transpose_tokens')
                 t0 += h * w
-        return gt, None
+        return gt, None, None
+
+
+def _maps_dtype():
+    """The 16-bit type whose instantiation of the token <-> plane transposes serves the call: fp16 under fp16 autocast
+    with ENABLED['fp16_tail'] (fp32 planes included, so that the step's profiler rows are all `_f16`), else bf16."""
+    return torch.float16 if _tail_dtype() == torch.float16 else torch.bfloat16
 
 
 def tokens_to_maps(tokens, hw):
@@ -1506,7 +1548,7 @@ def tokens_to_maps(tokens, hw):
     assert sum(h * w for h, w in hw) == tokens.shape[1]
     if (ENABLED['maps'] and tokens.is_cuda and tokens.dtype == torch.float32 and tokens.dim() == 3
             and tokens.numel() > 0 and tokens.shape[0] <= 65535):
-        return list(_TokensToMaps.apply(tokens, hw))
+        return list(_TokensToMaps.apply(tokens, hw, _maps_dtype()))
     outs, t0 = [], 0
     B, _, C = tokens.shape
     for h, w in hw:
@@ -1521,7 +1563,7 @@ class _MapsToTokens(torch.autograd.Function):
     column sums of their token ranges."""
 
     @staticmethod
-    def forward(ctx, *args):
+    def forward(ctx, t16, *args):
         n = len(args) // 2
         maps, vecs = args[:n], args[n:]
         B, C = maps[0].shape[:2]
@@ -1534,23 +1576,23 @@ class _MapsToTokens(torch.autograd.Function):
             for m, v, (h, w) in zip(maps, vecs, hw):
                 m = m.contiguous()
                 vv = v.detach().float().contiguous() if v is not None else None
-                _vah.check(_vah.lib.vah_transpose_tokens(
-                    m.data_ptr(), B, T, t0, h * w, C, out.data_ptr(), 0, int(m.dtype == torch.bfloat16),
+                _vah.check(_sym('vah_transpose_tokens', t16)(
+                    m.data_ptr(), B, T, t0, h * w, C, out.data_ptr(), 0, int(m.dtype == t16),
                     vv.data_ptr() if vv is not None else None, _stream(m)), 'transpose_tokens')
                 t0 += h * w
-        ctx.meta = (hw, [m.dtype for m in maps], [v is not None for v in vecs], (B, T, C))
+        ctx.meta = (hw, [m.dtype for m in maps], [v is not None for v in vecs], (B, T, C), t16)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        hw, dts, has_vec, (B, T, C) = ctx.meta
+        hw, dts, has_vec, (B, T, C), t16 = ctx.meta
         g = g.contiguous().float()
         gmaps, gvecs, t0 = [], [], 0
         with _vah.on(g.device):
             for (h, w), dt, hv in zip(hw, dts, has_vec):
                 gm = torch.empty((B, C, h, w), dtype=dt, device=g.device)
-                _vah.check(_vah.lib.vah_transpose_tokens(g.data_ptr(), B, T, t0, h * w, C, gm.data_ptr(), 1,
-                                                         int(dt == torch.bfloat16), None, _stream(g)), 'transpose_tokens')
+                _vah.check(_sym('vah_transpose_tokens', t16)(g.data_ptr(), B, T, t0, h * w, C, gm.data_ptr(), 1,
+                                                             int(dt == t16), None, _stream(g)), 'transpose_tokens')
                 gmaps.append(gm)
                 gv = None
                 if hv and C % 4 == 0:
@@ -1562,16 +1604,17 @@ class _MapsToTokens(torch.autograd.Function):
                     gv = g[:, t0:t0 + h * w].sum((0, 1))
                 gvecs.append(gv)
                 t0 += h * w
-        return (*gmaps, *gvecs)
+        return (None, *gmaps, *gvecs)
 
 
 def maps_to_tokens(maps, vecs):
     """``torch.cat([m.flatten(2).transpose(1, 2) + v for m, v in zip(maps, vecs)], dim=1)`` in fp32
     (the SPM's c2..c4 maps with their conv bias + level embedding, vit_adapter.py:94-97)."""
-    if (ENABLED['maps'] and maps[0].is_cuda and all(m.dim() == 4 and m.dtype in (torch.bfloat16, torch.float32)
+    t16 = _maps_dtype()       # fp16 maps under fp16 autocast (ENABLED['fp16_tail']); maps of the other 16-bit type: reference
+    if (ENABLED['maps'] and maps[0].is_cuda and all(m.dim() == 4 and m.dtype in (t16, torch.float32)
                                                     and m.shape[:2] == maps[0].shape[:2] for m in maps)
             and maps[0].numel() > 0 and maps[0].shape[0] <= 65535):
-        return _MapsToTokens.apply(*maps, *vecs)
+        return _MapsToTokens.apply(t16, *maps, *vecs)
     return torch.cat([m.flatten(2).transpose(1, 2).float() + (v if v is not None else 0.) for m, v in zip(maps, vecs)], dim=1)
 
 
@@ -1581,32 +1624,34 @@ class _MaxPool3s2(torch.autograd.Function):
         N, C, H, W = x.shape
         x = x.contiguous()
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        y = torch.empty((N, C, Ho, Wo), dtype=torch.bfloat16, device=x.device)
+        y = torch.empty((N, C, Ho, Wo), dtype=x.dtype, device=x.device)
         idx = torch.empty((N, C, Ho, Wo), dtype=torch.uint8, device=x.device)
         with _vah.on(x.device):
-            _vah.check(_vah.lib.vah_maxpool3s2_fwd_bf16(x.data_ptr(), N * C, H, W, y.data_ptr(), idx.data_ptr(),
-                                                        _stream(x)), 'maxpool_fwd')
+            _vah.check(_sym('vah_maxpool3s2_fwd_bf16', x.dtype)(x.data_ptr(), N * C, H, W, y.data_ptr(), idx.data_ptr(),
+                                                                _stream(x)), 'maxpool_fwd')
         ctx.save_for_backward(idx)
-        ctx.shape = (N, C, H, W)
+        ctx.shape, ctx.t16 = (N, C, H, W), x.dtype
         return y
 
     @staticmethod
     def backward(ctx, gy):
         (idx,) = ctx.saved_tensors
         N, C, H, W = ctx.shape
-        gy = gy.contiguous().to(torch.bfloat16)
-        gx = torch.empty((N, C, H, W), dtype=torch.bfloat16, device=gy.device)
+        gy = gy.contiguous().to(ctx.t16)
+        gx = torch.empty((N, C, H, W), dtype=ctx.t16, device=gy.device)
         with _vah.on(gy.device):
-            _vah.check(_vah.lib.vah_maxpool3s2_bwd_bf16(gy.data_ptr(), idx.data_ptr(), N * C, H, W, gx.data_ptr(),
-                                                        _stream(gy)), 'maxpool_bwd')
+            _vah.check(_sym('vah_maxpool3s2_bwd_bf16', ctx.t16)(gy.data_ptr(), idx.data_ptr(), N * C, H, W, gx.data_ptr(),
+                                                                _stream(gy)), 'maxpool_bwd')
         return gx
 
 
 def max_pool(pool, x):
-    """``pool(x)`` for the SPM stem's nn.MaxPool2d(kernel_size=3, stride=2, padding=1)."""
+    """``pool(x)`` for the SPM stem's nn.MaxPool2d(kernel_size=3, stride=2, padding=1) on bf16 or (ENABLED['fp16_tail'])
+    fp16 NCHW input."""
     def _is(v, k):
         return v == k or v == (k, k)
-    if (ENABLED['maxpool'] and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.numel() > 0
+    if (ENABLED['maxpool'] and x.is_cuda and (x.dtype == torch.bfloat16 or (x.dtype == torch.float16 and ENABLED['fp16_tail']))
+            and x.dim() == 4 and x.numel() > 0
             and isinstance(pool, torch.nn.MaxPool2d) and _is(pool.kernel_size, 3) and _is(pool.stride, 2)
             and _is(pool.padding, 1) and _is(pool.dilation, 1) and not pool.ceil_mode and not pool.return_indices):
         return _MaxPool3s2.apply(x)

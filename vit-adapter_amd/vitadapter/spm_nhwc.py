@@ -222,8 +222,9 @@ def autocast_dtype():
 
 
 def takes(spm, x, fold):
-    """Does the backbone hand the module to forward()?  Under bf16 autocast when the BatchNorm tail takes fc1's bias
-    (``fold``); under fp16 autocast whenever usable() holds (the tail is bf16-only: forward() then adds the bias)."""
+    """Does the backbone hand the module to forward()?  When the BatchNorm tail takes fc1's bias (``fold``: bf16
+    autocast, and fp16 autocast with ENABLED['fp16_tail']); under fp16 autocast also without it, whenever usable() holds
+    (the tail is then torch's and forward() adds the bias)."""
     if not (fold or autocast_dtype() == torch.float16):
         return False
     return usable(spm, x) and not (spm.with_cp and x.requires_grad)
@@ -269,8 +270,9 @@ def _fc1_planes_f16(fc1, c1, with_bias):
 
 
 def forward(spm, x, level_embed, c1_bias=False):
-    """-> (c1, c): c1 = fc1's output as NCHW 16-bit planes, WITHOUT its bias unless ``c1_bias`` (bf16: the caller folds
-    the bias into the BatchNorm tail; fp16: the tail is torch's and the caller asks for the bias),
+    """-> (c1, c): c1 = fc1's output as NCHW 16-bit planes, WITHOUT its bias unless ``c1_bias`` (the caller folds the
+    bias into the BatchNorm tail; only under fp16 with ENABLED['fp16_tail'] off, where the tail is torch's, does it ask
+    for the bias),
     c = cat([fc_l(c_l) + level_embed[l-2] for l = 2, 3, 4]) as (B, T, E) fp32 token rows."""
     dtype = autocast_dtype() or torch.bfloat16
     t = image_to_nhwc16(x, dtype)
