@@ -99,7 +99,8 @@ int vah_msda_backward_f64(const double *value, const int64_t *shapes, const int6
  *   offsets   (N,Lq,M,L,P,2)    raw sampling_offsets Linear output, param_dtype 0 = fp32 / 1 = bf16
  *   logits    (N,Lq,M,L*P)      raw attention_weights Linear output (softmax is done in-kernel)
  *   ref       (Lq, ref_levels, 2) fp32 reference points (x, y) in [0,1], ref_levels = 1 or L,
- *             shared by the batch (the adapter's reference grids)
+ *             shared by the batch (the adapter's reference grids); the *_nref entry points take
+ *             (ref_batch, Lq, ref_levels, 2) with ref_batch = 1 or N: one grid per image
  *   location  = ref + offsets / (W_l, H_l)
  * Supported: D == 32 and (L, P) in {(1,4), (3,4), (4,4)}  (vah_msda_fused_supported).
  * Backward (vah_msda_fused_backward): grad_value fp32 (N,S,M,32) zero on entry (float atomics, one per
@@ -122,6 +123,28 @@ int vah_msda_fused_backward(const void *value, int value_dtype, const int64_t *s
                             const float *ref, int64_t ref_levels, const void *grad_out,
                             int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
                             float *grad_value, void *d_offsets, void *d_logits, void *stream);
+/* Reference points per image.  The reference's MSDeformAttnPixelDecoder multiplies its grid by the valid ratios of
+ * every image - reference_points[None, :, None].repeat(batch, 1, L, 1) * valid_ratios, an (N, Lq, L, 2) tensor
+ * (segmentation/mmseg_custom/models/plugins/msdeformattn_pixel_decoder.py:224-240) - and half of its Mask2Former
+ * configs train with 2 or 4 images per GPU (e.g. mask2former_beit_adapter_large_640_160k_ade20k_ss.py:146).
+ * The *_nref entry points are the functions above (and vah_msda_fused_backward_tiled below) with one more argument,
+ * ref_batch, directly after ref_levels: ref is (ref_batch, Lq, ref_levels, 2) fp32 and image n reads
+ *   ref[((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2],   rq = (ref_batch == N && N > 1) ? Lq : 0.
+ * ref_batch must be 1 or N: anything else is VAH_E_SHAPE, decided on the host before any HIP call; ref_batch == 1
+ * (also N == 1) is the shared form, and the entry points without ref_batch are these with ref_batch = 1.  Same
+ * kernels (rq is a run-time argument), alignment rules, profile rows (msda_fused_fwd / msda_fused_bwd) and byte
+ * accounting.  vah_msda_fused_forward_win has no such form: its schedule is built from one grid for the batch. */
+int vah_msda_fused_forward_nref(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                                const void *offsets, const void *logits, int param_dtype,
+                                int64_t offsets_stride, int64_t logits_stride,
+                                const float *ref, int64_t ref_levels, int64_t ref_batch,
+                                int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
+                                void *out, void *stream);
+int vah_msda_fused_backward_nref(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                                 const void *offsets, const void *logits, int param_dtype,
+                                 const float *ref, int64_t ref_levels, int64_t ref_batch, const void *grad_out,
+                                 int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
+                                 float *grad_value, void *d_offsets, void *d_logits, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused forward over LDS value windows (csrc/msda_fwd_win.hip), single-level calls (L == 1, D == 32, P == 4,
@@ -191,6 +214,17 @@ int vah_msda_fused_backward_tiled(const void *value, int value_dtype, const int6
                                   int grad_value_dtype, void *d_offsets, void *d_logits,
                                   int grad_param_dtype, int64_t d_offsets_stride, int64_t d_logits_stride,
                                   void *ws, int64_t ws_bytes, void *stream);
+/* The same with reference points per image: ref (ref_batch, Lq, ref_levels, 2), ref_batch = 1 or N (see
+ * vah_msda_fused_forward_nref; msdeformattn_pixel_decoder.py:224-240). */
+int vah_msda_fused_backward_tiled_nref(const void *value, int value_dtype, const int64_t *shapes,
+                                       const int64_t *lsi, const void *offsets, const void *logits,
+                                       int param_dtype, int64_t offsets_stride, int64_t logits_stride,
+                                       const float *ref, int64_t ref_levels, int64_t ref_batch,
+                                       const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D,
+                                       int64_t L, int64_t Lq, int64_t P, void *grad_value,
+                                       int grad_value_dtype, void *d_offsets, void *d_logits,
+                                       int grad_param_dtype, int64_t d_offsets_stride, int64_t d_logits_stride,
+                                       void *ws, int64_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Softmax attention of the ViT blocks, bf16 (fp16 twins: *_f16, below), head_dim 64  

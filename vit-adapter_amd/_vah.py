@@ -89,6 +89,14 @@ lib.vah_msda_backward_tiled_f32.restype = ctypes.c_int
 lib.vah_msda_fused_backward_tiled.argtypes = ([_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p, _i64, _p] + [_i64] * 7
                                               + [_p, _ci, _p, _p, _ci, _i64, _i64, _p, _i64, _p])
 lib.vah_msda_fused_backward_tiled.restype = ctypes.c_int
+# reference points per image: one more int64 (ref_batch) directly after ref_levels
+lib.vah_msda_fused_forward_nref.argtypes = [_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p, _i64, _i64] + [_i64] * 7 + [_p, _p]
+lib.vah_msda_fused_forward_nref.restype = ctypes.c_int
+lib.vah_msda_fused_backward_nref.argtypes = [_p, _ci, _p, _p, _p, _p, _ci, _p, _i64, _i64, _p] + [_i64] * 7 + [_p] * 4
+lib.vah_msda_fused_backward_nref.restype = ctypes.c_int
+lib.vah_msda_fused_backward_tiled_nref.argtypes = ([_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p, _i64, _i64, _p] + [_i64] * 7
+                                                   + [_p, _ci, _p, _p, _ci, _i64, _i64, _p, _i64, _p])
+lib.vah_msda_fused_backward_tiled_nref.restype = ctypes.c_int
 _f = ctypes.c_float
 lib.vah_layernorm_fwd_f32_bf16.argtypes = [_p, _p, _p, _i64, _i64, _f, _p, _p, _p, _p]
 lib.vah_layernorm_bwd_f32_bf16.argtypes = [_p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]
@@ -209,6 +217,7 @@ EXPORTS = (
     'vah_msda_backward_f32', 'vah_msda_backward_f64',
     'vah_msda_fused_supported', 'vah_msda_fused_forward', 'vah_msda_fused_backward',
     'vah_msda_fused_forward_win', 'vah_msda_win_ws_bytes', 'vah_msda_tile_ws_bytes', 'vah_msda_backward_tiled_f32', 'vah_msda_fused_backward_tiled',
+    'vah_msda_fused_forward_nref', 'vah_msda_fused_backward_nref', 'vah_msda_fused_backward_tiled_nref',
     'vah_pixel_shuffle2_bf16', 'vah_patchify_bf16', 'vah_attn_bias_fwd_bf16', 'vah_attn_bias_bwd_bf16', 'vah_relpos_bias_build', 'vah_relpos_bias_grad_ws_floats',
     'vah_relpos_bias_grad', 'vah_attn_padded_len', 'vah_attn_fwd_bf16', 'vah_attn_bwd_workspace_bytes', 'vah_attn_bwd_bf16',
     'vah_attn_win_fwd_bf16', 'vah_attn_win_bwd_bf16',

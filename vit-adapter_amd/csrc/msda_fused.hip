@@ -13,8 +13,11 @@
 // read directly; out is written in the value's dtype.  Gather / scatter arithmetic is that of
 // msda.hip (spec: ms_deform_im2col_cuda.cuh:33-159,237-403).
 //
-// Restrictions of this path: D == 32, (L, P) in {(1,4), (3,4), (4,4)}, reference points shared by
-// the batch with last dim 2 (the adapter's).  Everything else uses the unfused Function.
+// Restrictions of this path: D == 32, (L, P) in {(1,4), (3,4), (4,4)}, reference points with last dim 2,
+// shared by the batch (the adapter's) or one grid per image (the Mask2Former pixel decoder's grid times
+// valid ratios, segmentation/mmseg_custom/models/plugins/msdeformattn_pixel_decoder.py:224-240): `rq`, the
+// rows of ref between consecutive images, is a run-time kernel argument, 0 for a shared grid.
+// Everything else uses the unfused Function.
 #include <cstdlib>
 #include <type_traits>
 
@@ -91,7 +94,7 @@ template <typename VT, typename PT, int L, int P>
 __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const PT *__restrict__ off, const PT *__restrict__ logit, int64_t os, int64_t ls, const float *__restrict__ ref,
-    int ref_levels, int64_t S, int M, int64_t Lq, int64_t total_rows, int64_t nblocks,
+    int ref_levels, int64_t rq, int64_t S, int M, int64_t Lq, int64_t total_rows, int64_t nblocks,
     VT *__restrict__ out) {
     constexpr int LP = L * P;
     constexpr int ROWS = kBlock / 8;
@@ -110,10 +113,10 @@ __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
         }
         const Level lv = read_level(shapes, lsi, l, S);
         if (w < total_rows && lv.valid) {
-            const int64_t q = w % Lq;
-            const int64_t rw = (w / Lq / M * Lq + q) * M + (w / Lq) % M;
+            const int64_t q = w % Lq, n = w / Lq / M;
+            const int64_t rw = (n * Lq + q) * M + (w / Lq) % M;
             const float2 o = load2(off + rw * os + sidx * 2);
-            const float2 rp = *reinterpret_cast<const float2 *>(ref + (q * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+            const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
             const Tap<float> t = make_tap<float>(rp.x + o.x / (float)lv.W, rp.y + o.y / (float)lv.H, lv.H, lv.W);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -181,7 +184,7 @@ template <typename VT, typename PT, int L, int P>
 __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const PT *__restrict__ off, const PT *__restrict__ logit, const float *__restrict__ ref,
-    int ref_levels, const VT *__restrict__ grad_out, int64_t S, int M, int64_t Lq, int64_t total_rows,
+    int ref_levels, int64_t rq, const VT *__restrict__ grad_out, int64_t S, int M, int64_t Lq, int64_t total_rows,
     int64_t nblocks, float near_radius, float *__restrict__ grad_value, PT *__restrict__ d_off,
     PT *__restrict__ d_logit) {
     // near_radius == kNoScatter: grad_value is left to the tile pass (msda_tile.hip) altogether
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
 #pragma unroll
     for (int l = 0; l < L; ++l) {
         const Level lv = read_level(shapes, lsi, l, S);
-        const float2 rp = *reinterpret_cast<const float2 *>(ref + (q * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+        const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
         const int64_t lstart = lv.valid ? lv.start : 0;      // the gathers below are unconditional: stay in bounds
         const VT *vl = value + head_off + lstart * stride;
         float *gvl = grad_value + head_off + lstart * stride;
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(V
 void msda_fused_bwd_vec4(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const PT *__restrict__ off, const PT *__restrict__ logit, const float *__restrict__ ref,
-    int ref_levels, const VT *__restrict__ grad_out, int64_t S, int M, int64_t Lq, int64_t total_rows,
+    int ref_levels, int64_t rq, const VT *__restrict__ grad_out, int64_t S, int M, int64_t Lq, int64_t total_rows,
     int64_t nblocks, float near_radius, float *__restrict__ grad_value, PT *__restrict__ d_off,
     PT *__restrict__ d_logit) {
     constexpr int LP = L * P;
@@ -305,11 +308,11 @@ void msda_fused_bwd_vec4(
         tl.lh = tl.lw = 0.f;
         tl.pad[0] = tl.pad[1] = 0;
         if (w < total_rows) {
-            const int64_t q = w % Lq;
-            const int64_t rw = (w / Lq / M * Lq + q) * M + (w / Lq) % M;
+            const int64_t q = w % Lq, n = w / Lq / M;
+            const int64_t rw = (n * Lq + q) * M + (w / Lq) % M;
             const Level lv = read_level(shapes, lsi, l, S);
             const float2 o = load2(off + (rw * LP + sidx) * 2);
-            const float2 rp = *reinterpret_cast<const float2 *>(ref + (q * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+            const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
             const Tap<float> t = make_tap<float>(lv.valid ? rp.x + o.x / (float)lv.W : -8.f,
                                                  lv.valid ? rp.y + o.y / (float)lv.H : -8.f, max(lv.H, 1), max(lv.W, 1));
 #pragma unroll
@@ -402,6 +405,7 @@ struct FusedArgs {
     const int64_t *shapes, *lsi;
     const float *ref;
     int ref_levels;
+    int64_t rq = 0;                  // rows of ref between consecutive images: Lq for a per-image grid, 0 for a shared one
     int64_t N, S, M, L, Lq, P;
     void *out;
     float *grad_value;
@@ -419,7 +423,7 @@ int launch_fwd(const FusedArgs &a) {
     if (grid >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "msda fused forward: grid too large");
     hipLaunchKernelGGL((msda_fused_fwd<VT, PT, L, P>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
                        (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.os ? a.os : L * P * 2,
-                       a.ls ? a.ls : L * P, a.ref, a.ref_levels, a.S, (int)a.M, a.Lq, rows, nblocks, (VT *)a.out);
+                       a.ls ? a.ls : L * P, a.ref, a.ref_levels, a.rq, a.S, (int)a.M, a.Lq, rows, nblocks, (VT *)a.out);
     return check_launch("msda fused forward launch");
 }
 
@@ -434,7 +438,7 @@ int launch_bwd(const FusedArgs &a) {
         // one lane per channel; scatters grad_value with atomics unless the tile pass owns it (taps_only)
         hipLaunchKernelGGL((msda_fused_bwd<VT, PT, L, P>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
                            (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.ref,
-                           a.ref_levels, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nblocks,
+                           a.ref_levels, a.rq, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nblocks,
                            a.taps_only ? kNoScatter : -1.f, a.grad_value, (PT *)a.d_off, (PT *)a.d_logit);
         return check_launch("msda fused backward launch");
     }
@@ -442,7 +446,7 @@ int launch_bwd(const FusedArgs &a) {
     const int64_t grid8 = (nb8 + 7) / 8 * 8;
     hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P>), dim3((unsigned)grid8), dim3(kBlock), 0, a.st,
                        (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.ref,
-                       a.ref_levels, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nb8, kNoScatter,
+                       a.ref_levels, a.rq, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nb8, kNoScatter,
                        a.grad_value, (PT *)a.d_off, (PT *)a.d_logit);
     return check_launch("msda fused backward (gather) launch");
 }
@@ -468,23 +472,29 @@ int dispatch(const FusedArgs &a, int value_dtype, int param_dtype) {
 }
 
 int check_common(const char *fn, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
-                 int64_t ref_levels) {
+                 int64_t ref_levels, int64_t ref_batch) {
     if (N < 0 || S < 1 || M < 1 || L < 1 || Lq < 0 || P < 1 || M * D >= (1LL << 31))
         return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (D != kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32", fn);
     if (ref_levels != 1 && ref_levels != L) return fail(VAH_E_SHAPE, "%s: ref_levels must be 1 or L", fn);
+    if (ref_batch != 1 && ref_batch != N)
+        return fail(VAH_E_SHAPE, "%s: ref_batch must be 1 or N (%lld), got %lld", fn, (long long)N, (long long)ref_batch);
     return VAH_OK;
 }
 
 }  // namespace
 
+// rows of ref between consecutive images as the kernels take it: Lq for a per-image grid, 0 for one the batch shares
+// (ref_batch == N == 1 is the shared form).  ((N - 1) * Lq + q) * ref_levels * 2 is formed in int64_t in this file.
+int64_t msda_ref_rows_per_image(int64_t ref_batch, int64_t N, int64_t Lq) { return ref_batch == N && N > 1 ? Lq : 0; }
+
 int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi, const void *offsets,
-                         const void *logits, int param_dtype, const float *ref, int64_t ref_levels, const void *grad_out,
-                         int64_t N, int64_t S, int64_t M, int64_t L, int64_t Lq, int64_t P, void *d_offsets, void *d_logits,
-                         hipStream_t st) {
+                         const void *logits, int param_dtype, const float *ref, int64_t ref_levels, int64_t rq,
+                         const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t L, int64_t Lq, int64_t P, void *d_offsets,
+                         void *d_logits, hipStream_t st) {
     FusedArgs a{};
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
-    a.ref_levels = (int)ref_levels, a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P;
+    a.ref_levels = (int)ref_levels, a.rq = rq, a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P;
     a.grad_out = grad_out, a.d_off = d_offsets, a.d_logit = d_logits;
     a.grad_value = nullptr;          // never dereferenced: nothing scatters in this mode
     a.taps_only = true;
@@ -492,29 +502,22 @@ int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shap
     return dispatch<true>(a, value_dtype, param_dtype);
 }
 
-}  // namespace vah
+namespace {
 
-extern "C" {
-
-int vah_msda_fused_supported(int64_t D, int64_t L, int64_t P) {
-    return D == 32 && P == 4 && (L == 1 || L == 3 || L == 4);
-}
-
-int vah_msda_fused_forward(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
-                           const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
-                           int64_t logits_stride, const float *ref,
-                           int64_t ref_levels, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L,
-                           int64_t Lq, int64_t P, void *out, void *stream) {
-    using namespace vah;
+// The C entry points below with and without ref_batch are calls of these two.
+int fused_forward_impl(const char *fn, const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                       const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
+                       int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch, int64_t N, int64_t S,
+                       int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, void *out, void *stream) {
     clear_error();
-    const char *fn = "vah_msda_fused_forward";
-    if (int rc = check_common(fn, N, S, M, D, L, Lq, P, ref_levels)) return rc;
+    if (int rc = check_common(fn, N, S, M, D, L, Lq, P, ref_levels, ref_batch)) return rc;
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !out) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (((uintptr_t)value | (uintptr_t)out | (uintptr_t)offsets | (uintptr_t)ref) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
     FusedArgs a{};
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
-    a.ref_levels = (int)ref_levels, a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P, a.out = out;
+    a.ref_levels = (int)ref_levels, a.rq = msda_ref_rows_per_image(ref_batch, N, Lq);
+    a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P, a.out = out;
     a.os = offsets_stride, a.ls = logits_stride;
     if (offsets_stride < 0 || logits_stride < 0 || ((offsets_stride * (param_dtype == 1 ? 2 : 4)) % 8) ||
         ((logits_stride * (param_dtype == 1 ? 2 : 4)) % (param_dtype == 1 ? 2 : 4)))
@@ -532,21 +535,19 @@ int vah_msda_fused_forward(const void *value, int value_dtype, const int64_t *sh
 // grad_value: fp32 (N,S,M,D), zero on entry (float atomics).  grad_out has the value dtype; d_offsets / d_logits the
 // parameter dtype.  This is the fallback of vah_msda_fused_backward_tiled (csrc/msda_tile.hip) for the shapes the tile
 // pass does not take.
-int vah_msda_fused_backward(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
-                            const void *offsets, const void *logits, int param_dtype, const float *ref,
-                            int64_t ref_levels, const void *grad_out, int64_t N, int64_t S, int64_t M,
-                            int64_t D, int64_t L, int64_t Lq, int64_t P, float *grad_value,
-                            void *d_offsets, void *d_logits, void *stream) {
-    using namespace vah;
+int fused_backward_impl(const char *fn, const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                        const void *offsets, const void *logits, int param_dtype, const float *ref, int64_t ref_levels,
+                        int64_t ref_batch, const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L,
+                        int64_t Lq, int64_t P, float *grad_value, void *d_offsets, void *d_logits, void *stream) {
     clear_error();
-    const char *fn = "vah_msda_fused_backward";
-    if (int rc = check_common(fn, N, S, M, D, L, Lq, P, ref_levels)) return rc;
+    if (int rc = check_common(fn, N, S, M, D, L, Lq, P, ref_levels, ref_batch)) return rc;
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !grad_out || !grad_value || !d_offsets || !d_logits)
         return fail(VAH_E_NULL, "%s: null pointer", fn);
     FusedArgs a{};
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
-    a.ref_levels = (int)ref_levels, a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P;
+    a.ref_levels = (int)ref_levels, a.rq = msda_ref_rows_per_image(ref_batch, N, Lq);
+    a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P;
     a.grad_out = grad_out, a.grad_value = grad_value, a.d_off = d_offsets, a.d_logit = d_logits;
     a.st = (hipStream_t)stream;
     // moved bytes: value + grad_out read in the value dtype, offsets / logits read and their gradients
@@ -555,6 +556,52 @@ int vah_msda_fused_backward(const void *value, int value_dtype, const int64_t *s
     LaunchScope scope("msda_fused_bwd", vs * (N * S * M * D + N * Lq * M * D) + 4 * N * S * M * D + ps * 6 * N * Lq * M * L * P,
                       a.st, 4 * (2 * N * S * M * D + 6 * N * Lq * M * L * P + N * Lq * M * D));
     return dispatch<true>(a, value_dtype, param_dtype);
+}
+
+}  // namespace
+}  // namespace vah
+
+extern "C" {
+
+int vah_msda_fused_supported(int64_t D, int64_t L, int64_t P) {
+    return D == 32 && P == 4 && (L == 1 || L == 3 || L == 4);
+}
+
+int vah_msda_fused_forward(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                           const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
+                           int64_t logits_stride, const float *ref,
+                           int64_t ref_levels, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L,
+                           int64_t Lq, int64_t P, void *out, void *stream) {
+    return vah::fused_forward_impl("vah_msda_fused_forward", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
+                                   offsets_stride, logits_stride, ref, ref_levels, 1, N, S, M, D, L, Lq, P, out, stream);
+}
+
+int vah_msda_fused_forward_nref(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                                const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
+                                int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch,
+                                int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, void *out,
+                                void *stream) {
+    return vah::fused_forward_impl("vah_msda_fused_forward_nref", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
+                                   offsets_stride, logits_stride, ref, ref_levels, ref_batch, N, S, M, D, L, Lq, P, out, stream);
+}
+
+int vah_msda_fused_backward(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                            const void *offsets, const void *logits, int param_dtype, const float *ref,
+                            int64_t ref_levels, const void *grad_out, int64_t N, int64_t S, int64_t M,
+                            int64_t D, int64_t L, int64_t Lq, int64_t P, float *grad_value,
+                            void *d_offsets, void *d_logits, void *stream) {
+    return vah::fused_backward_impl("vah_msda_fused_backward", value, value_dtype, shapes, lsi, offsets, logits, param_dtype, ref,
+                                    ref_levels, 1, grad_out, N, S, M, D, L, Lq, P, grad_value, d_offsets, d_logits, stream);
+}
+
+int vah_msda_fused_backward_nref(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                                 const void *offsets, const void *logits, int param_dtype, const float *ref,
+                                 int64_t ref_levels, int64_t ref_batch, const void *grad_out, int64_t N, int64_t S,
+                                 int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, float *grad_value,
+                                 void *d_offsets, void *d_logits, void *stream) {
+    return vah::fused_backward_impl("vah_msda_fused_backward_nref", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
+                                    ref, ref_levels, ref_batch, grad_out, N, S, M, D, L, Lq, P, grad_value, d_offsets, d_logits,
+                                    stream);
 }
 
 }  // extern "C"

@@ -10,10 +10,15 @@ int msda_grad_taps_f32(const float *value, const int64_t *shapes, const int64_t 
                        const float *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
                        float *grad_loc, float *grad_attn, hipStream_t st);
 
+// Rows of the fused core's reference points between consecutive images: Lq for a per-image grid (ref_batch == N > 1),
+// 0 for one the batch shares.
+int64_t msda_ref_rows_per_image(int64_t ref_batch, int64_t N, int64_t Lq);
+
 // d(offsets), d(logits) of the fused core, nothing scattered (msda_fused.hip: msda_fused_bwd_vec4 / msda_fused_bwd).
+// rq: msda_ref_rows_per_image.
 int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi, const void *offsets,
-                         const void *logits, int param_dtype, const float *ref, int64_t ref_levels, const void *grad_out,
-                         int64_t N, int64_t S, int64_t M, int64_t L, int64_t Lq, int64_t P, void *d_offsets, void *d_logits,
-                         hipStream_t st);
+                         const void *logits, int param_dtype, const float *ref, int64_t ref_levels, int64_t rq,
+                         const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t L, int64_t Lq, int64_t P, void *d_offsets,
+                         void *d_logits, hipStream_t st);
 
 }  // namespace vah

@@ -321,7 +321,7 @@ __device__ __forceinline__ void write_item(const PlanDev &g, const Bounds &bd, I
 }
 
 // ---- sample sources ---------------------------------------------------------------------------
-// A source hands out one (n, q, m) row's samples of one level in two steps: load() only issues the
+// A source hands out one (n, q, m) row's samples of one level in two steps: load(row, ref_row(n, q), level) only issues the
 // global loads - whole 16 / 8-byte vectors, kept as raw words so that a caller can hold the NEXT chunk's
 // operands in few registers while it works on the current one - and xy() / weights() decode them.
 // Plain: sampling_locations (N,Lq,M,L,P,2) and attention_weights (N,Lq,M,L,P), fp32 (the reference API).
@@ -352,8 +352,9 @@ struct PlainSrc {
         float4 xy[2];       // P = 4 locations
         float4 a;
     };
+    __device__ __forceinline__ int ref_row(int n, int q) const { return q; }
     template <bool WEIGHTS>
-    __device__ __forceinline__ Raw load(int row, int q, int l) const {
+    __device__ __forceinline__ Raw load(int row, int rr, int l) const {
         Raw r;
         const float4 *lp = reinterpret_cast<const float4 *>(loc + (row * LP + l * kP) * 2);       // 32-byte aligned
         r.xy[0] = lp[0];
@@ -387,6 +388,7 @@ struct FusedSrc {
     const PT *off, *logit;
     const float *ref;
     int ref_levels;
+    int rq;                                // rows of ref between consecutive images: Lq (one grid per image) or 0 (shared)
     int os, ls;                            // elements between the offsets / logits of consecutive (n, q, m) rows
     static constexpr int kLevels = L;
     static constexpr int LP = L * kP;
@@ -437,8 +439,10 @@ struct FusedSrc {
         uint32_t lg[LW];
         float2 rp;
     };
+    // row of ref that query q of image n reads (n is uniform over a workgroup of either pass)
+    __device__ __forceinline__ int ref_row(int n, int q) const { return n * rq + q; }
     template <bool WEIGHTS>
-    __device__ __forceinline__ Raw load(int row, int q, int l) const {
+    __device__ __forceinline__ Raw load(int row, int rr, int l) const {
         Raw r;
         const uint4 *op = reinterpret_cast<const uint4 *>(off + row * os + l * kP * 2);           // 16-byte aligned
 #pragma unroll
@@ -446,7 +450,7 @@ struct FusedSrc {
             const uint4 v = op[i];
             r.o[4 * i] = v.x, r.o[4 * i + 1] = v.y, r.o[4 * i + 2] = v.z, r.o[4 * i + 3] = v.w;
         }
-        r.rp = *reinterpret_cast<const float2 *>(ref + (q * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+        r.rp = *reinterpret_cast<const float2 *>(ref + (rr * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
         const uint2 *lp = reinterpret_cast<const uint2 *>(logit + row * ls);                       // 8-byte aligned
 #pragma unroll
         for (int i = 0; i < LW / 2; ++i) {
@@ -575,7 +579,7 @@ __global__ __launch_bounds__(256) void msda_bin(Src src, const unsigned char *__
 #pragma unroll
     for (int p = 0; p < kP; ++p) ya[p] = yb[p] = xa[p] = xb[p] = 0, in[p] = false;
     if (live) {
-        const typename Src::Raw raw = src.template load<false>(row, q, l);
+        const typename Src::Raw raw = src.template load<false>(row, src.ref_row(n, q), l);
         const typename Src::LevelConst lc = src.level_const(H, W);
         unsigned orphan = 0;
         ay = 1 << 30, ax = 1 << 30;
@@ -820,7 +824,7 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
     constexpr int RPI = 64 / NV;                                // rows per load instruction
     auto request = [&](int n_, int m_, int l_, int e) __attribute__((always_inline)) {
         row = (n_ * Lq + e) * M + m_;
-        raw = src.template load<true>(row, e, l_);
+        raw = src.template load<true>(row, src.ref_row(n_, e), l_);
 #if VAH_GR_COOP
         const unsigned char *gbytes = reinterpret_cast<const unsigned char *>(grad_out) + (size_t)(lane % NV) * 16;
 #pragma unroll
@@ -1255,12 +1259,12 @@ constexpr bool kTapsInTile = std::is_same<VT, __bf16>::value;
 
 template <typename VT, typename PT, typename GPT, int L>
 int fused_tiled(const char *fn, const Bounds &bd, const void *value, const int64_t *shapes, const int64_t *lsi, const void *off,
-                const void *logit, int64_t os, int64_t ls, const float *ref, int ref_levels, int64_t N, int64_t M, int64_t Lq, int64_t S,
+                const void *logit, int64_t os, int64_t ls, const float *ref, int ref_levels, int rq, int64_t N, int64_t M, int64_t Lq, int64_t S,
                 const void *grad_out, void *grad_value, int gv_bf16, void *d_off, void *d_logit, int64_t dos, int64_t dls, void *ws,
                 hipStream_t st) {
     constexpr bool TAPS = kTapsInTile<VT>;
     uint32_t *rec = (uint32_t *)((char *)ws + bd.off_ga);
-    FusedSrc<PT, GPT, L> src{(const PT *)off, (const PT *)logit, ref, ref_levels, (int)os, (int)ls, rec};
+    FusedSrc<PT, GPT, L> src{(const PT *)off, (const PT *)logit, ref, ref_levels, rq, (int)os, (int)ls, rec};
     int rc;
     if (gv_bf16) {
         if constexpr (std::is_same<VT, __bf16>::value)
@@ -1277,6 +1281,70 @@ int fused_tiled(const char *fn, const Bounds &bd, const void *value, const int64
     hipLaunchKernelGGL((msda_grad_finish<PT, GPT, L>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, (const PT *)logit, ls,
                        (const uint32_t *)rec, rows, (GPT *)d_off, (GPT *)d_logit, dos, dls);
     return check_launch(fn);
+}
+
+int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                              const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
+                              int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch, const void *grad_out,
+                              int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, void *grad_value,
+                              int grad_value_dtype, void *d_offsets, void *d_logits, int grad_param_dtype,
+                              int64_t d_offsets_stride, int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
+    clear_error();
+    if (N < 0 || S < 1 || M < 1 || Lq < 0 || M * D >= (1LL << 31)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (D != kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32", fn);
+    if (ref_levels != 1 && ref_levels != L) return fail(VAH_E_SHAPE, "%s: ref_levels must be 1 or L", fn);
+    if (ref_batch != 1 && ref_batch != N)
+        return fail(VAH_E_SHAPE, "%s: ref_batch must be 1 or N (%lld), got %lld", fn, (long long)N, (long long)ref_batch);
+    if (N * Lq * M == 0) return VAH_OK;
+    if (!value || !shapes || !lsi || !offsets || !logits || !ref || !grad_out || !grad_value || !d_offsets || !d_logits || !ws)
+        return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)grad_out | (uintptr_t)grad_value | (uintptr_t)ws | (uintptr_t)offsets) % 16 || ((uintptr_t)d_offsets | (uintptr_t)ref) % 8)
+        return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    if ((value_dtype | param_dtype | grad_value_dtype | grad_param_dtype) & ~1)
+        return fail(VAH_E_UNSUPPORTED, "%s: dtype codes must be 0 (f32) or 1 (bf16)", fn);
+    if (grad_param_dtype != param_dtype && !(param_dtype == 0 && grad_param_dtype == 1))
+        return fail(VAH_E_UNSUPPORTED, "%s: gradients of fp32 offsets / logits may be bf16, not the reverse", fn);
+    const int64_t vs = value_dtype ? 2 : 4, ps = param_dtype ? 2 : 4, gps = grad_param_dtype ? 2 : 4, gs = grad_value_dtype ? 2 : 4;
+    const int64_t os = offsets_stride ? offsets_stride : L * P * 2, ls = logits_stride ? logits_stride : L * P;
+    const int64_t dos = d_offsets_stride ? d_offsets_stride : L * P * 2, dls = d_logits_stride ? d_logits_stride : L * P;
+    const bool strided = os != L * P * 2 || ls != L * P || dos != L * P * 2 || dls != L * P;
+    if (os < L * P * 2 || ls < L * P || dos < L * P * 2 || dls < L * P || (os * ps) % 16 || (ls * ps) % 8 || (dos * gps) % (gps == 4 ? 16 : 8) ||
+        ((uintptr_t)logits) % 8 || (dls * gps) % gps || N * Lq * M * (os > ls ? os : ls) >= ((int64_t)1 << 31))
+        return fail(VAH_E_ALIGN, "%s: bad strides", fn);
+    // the passes index ref in int: N * Lq * ref_levels * 2 <= N * Lq * 2 * L < N * Lq * M * os < 2^31 by the check above
+    // (os >= 2 * L * P)
+    const int64_t rq = msda_ref_rows_per_image(ref_batch, N, Lq);
+    Bounds bd;
+    if (int rc = make_bounds(fn, N, S, M, L, Lq, P, &bd)) return rc;
+    if (ws_bytes < bd.total) return fail(VAH_E_SHAPE, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes, (long long)bd.total);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope("msda_fused_bwd", vs * (N * S * M * D + N * Lq * M * D) + gs * N * S * M * D + (ps + gps) * 3 * N * Lq * M * L * P, st,
+                      4 * (2 * N * S * M * D + 6 * N * Lq * M * L * P + N * Lq * M * D));
+    // d(offsets), d(logits) from the gather kernel of msda_fused.hip (nothing scattered) where the tile pass does not
+    // compute them itself (fp32 values)
+    if (value_dtype != 1) {
+        if (grad_param_dtype != param_dtype || strided)
+            return fail(VAH_E_UNSUPPORTED, "%s: fp32 values write gradients in the parameter dtype, contiguous tensors only", fn);
+        if (int rc = msda_fused_grad_taps(value, value_dtype, shapes, lsi, offsets, logits, param_dtype, ref, ref_levels, rq, grad_out,
+                                          N, S, M, L, Lq, P, d_offsets, d_logits, st))
+            return rc;
+    }
+#define VAH_CASE(VT, VC, PT, PC, GPT, GC, LL)                                                                              \
+    if (value_dtype == VC && param_dtype == PC && grad_param_dtype == GC && L == LL)                                      \
+        return fused_tiled<VT, PT, GPT, LL>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, (int)rq, N, M, Lq, S, \
+                                            grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)
+#define VAH_CASES(LL)                                  \
+    VAH_CASE(float, 0, float, 0, float, 0, LL);        \
+    VAH_CASE(__bf16, 1, __bf16, 1, __bf16, 1, LL);     \
+    VAH_CASE(__bf16, 1, float, 0, float, 0, LL);       \
+    VAH_CASE(__bf16, 1, float, 0, __bf16, 1, LL);      \
+    VAH_CASE(float, 0, __bf16, 1, __bf16, 1, LL)
+    VAH_CASES(1);
+    VAH_CASES(3);
+    VAH_CASES(4);
+#undef VAH_CASES
+#undef VAH_CASE
+    return fail(VAH_E_UNSUPPORTED, "%s: L = %lld not instantiated", fn, (long long)L);
 }
 
 }  // namespace
@@ -1325,59 +1393,23 @@ int vah_msda_fused_backward_tiled(const void *value, int value_dtype, const int6
                                   int64_t L, int64_t Lq, int64_t P, void *grad_value, int grad_value_dtype,
                                   void *d_offsets, void *d_logits, int grad_param_dtype, int64_t d_offsets_stride,
                                   int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_msda_fused_backward_tiled";
-    if (N < 0 || S < 1 || M < 1 || Lq < 0 || M * D >= (1LL << 31)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (D != kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32", fn);
-    if (ref_levels != 1 && ref_levels != L) return fail(VAH_E_SHAPE, "%s: ref_levels must be 1 or L", fn);
-    if (N * Lq * M == 0) return VAH_OK;
-    if (!value || !shapes || !lsi || !offsets || !logits || !ref || !grad_out || !grad_value || !d_offsets || !d_logits || !ws)
-        return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)grad_out | (uintptr_t)grad_value | (uintptr_t)ws | (uintptr_t)offsets) % 16 || ((uintptr_t)d_offsets | (uintptr_t)ref) % 8)
-        return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    if ((value_dtype | param_dtype | grad_value_dtype | grad_param_dtype) & ~1)
-        return fail(VAH_E_UNSUPPORTED, "%s: dtype codes must be 0 (f32) or 1 (bf16)", fn);
-    if (grad_param_dtype != param_dtype && !(param_dtype == 0 && grad_param_dtype == 1))
-        return fail(VAH_E_UNSUPPORTED, "%s: gradients of fp32 offsets / logits may be bf16, not the reverse", fn);
-    const int64_t vs = value_dtype ? 2 : 4, ps = param_dtype ? 2 : 4, gps = grad_param_dtype ? 2 : 4, gs = grad_value_dtype ? 2 : 4;
-    const int64_t os = offsets_stride ? offsets_stride : L * P * 2, ls = logits_stride ? logits_stride : L * P;
-    const int64_t dos = d_offsets_stride ? d_offsets_stride : L * P * 2, dls = d_logits_stride ? d_logits_stride : L * P;
-    const bool strided = os != L * P * 2 || ls != L * P || dos != L * P * 2 || dls != L * P;
-    if (os < L * P * 2 || ls < L * P || dos < L * P * 2 || dls < L * P || (os * ps) % 16 || (ls * ps) % 8 || (dos * gps) % (gps == 4 ? 16 : 8) ||
-        ((uintptr_t)logits) % 8 || (dls * gps) % gps || N * Lq * M * (os > ls ? os : ls) >= ((int64_t)1 << 31))
-        return fail(VAH_E_ALIGN, "%s: bad strides", fn);
-    Bounds bd;
-    if (int rc = make_bounds(fn, N, S, M, L, Lq, P, &bd)) return rc;
-    if (ws_bytes < bd.total) return fail(VAH_E_SHAPE, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes, (long long)bd.total);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("msda_fused_bwd", vs * (N * S * M * D + N * Lq * M * D) + gs * N * S * M * D + (ps + gps) * 3 * N * Lq * M * L * P, st,
-                      4 * (2 * N * S * M * D + 6 * N * Lq * M * L * P + N * Lq * M * D));
-    // d(offsets), d(logits) from the gather kernel of msda_fused.hip (nothing scattered) where the tile pass does not
-    // compute them itself (fp32 values)
-    if (value_dtype != 1) {
-        if (grad_param_dtype != param_dtype || strided)
-            return fail(VAH_E_UNSUPPORTED, "%s: fp32 values write gradients in the parameter dtype, contiguous tensors only", fn);
-        if (int rc = msda_fused_grad_taps(value, value_dtype, shapes, lsi, offsets, logits, param_dtype, ref, ref_levels, grad_out,
-                                          N, S, M, L, Lq, P, d_offsets, d_logits, st))
-            return rc;
-    }
-#define VAH_CASE(VT, VC, PT, PC, GPT, GC, LL)                                                                              \
-    if (value_dtype == VC && param_dtype == PC && grad_param_dtype == GC && L == LL)                                      \
-        return fused_tiled<VT, PT, GPT, LL>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, N, M, Lq, S, \
-                                            grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)
-#define VAH_CASES(LL)                                  \
-    VAH_CASE(float, 0, float, 0, float, 0, LL);        \
-    VAH_CASE(__bf16, 1, __bf16, 1, __bf16, 1, LL);     \
-    VAH_CASE(__bf16, 1, float, 0, float, 0, LL);       \
-    VAH_CASE(__bf16, 1, float, 0, __bf16, 1, LL);      \
-    VAH_CASE(float, 0, __bf16, 1, __bf16, 1, LL)
-    VAH_CASES(1);
-    VAH_CASES(3);
-    VAH_CASES(4);
-#undef VAH_CASES
-#undef VAH_CASE
-    return fail(VAH_E_UNSUPPORTED, "%s: L = %lld not instantiated", fn, (long long)L);
+    return vah::fused_backward_tiled_impl("vah_msda_fused_backward_tiled", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
+                                          offsets_stride, logits_stride, ref, ref_levels, 1, grad_out, N, S, M, D, L, Lq, P,
+                                          grad_value, grad_value_dtype, d_offsets, d_logits, grad_param_dtype, d_offsets_stride,
+                                          d_logits_stride, ws, ws_bytes, stream);
+}
+
+int vah_msda_fused_backward_tiled_nref(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                                       const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
+                                       int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch,
+                                       const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L,
+                                       int64_t Lq, int64_t P, void *grad_value, int grad_value_dtype, void *d_offsets,
+                                       void *d_logits, int grad_param_dtype, int64_t d_offsets_stride,
+                                       int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
+    return vah::fused_backward_tiled_impl("vah_msda_fused_backward_tiled_nref", value, value_dtype, shapes, lsi, offsets, logits,
+                                          param_dtype, offsets_stride, logits_stride, ref, ref_levels, ref_batch, grad_out, N, S, M,
+                                          D, L, Lq, P, grad_value, grad_value_dtype, d_offsets, d_logits, grad_param_dtype,
+                                          d_offsets_stride, d_logits_stride, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -15,13 +15,24 @@ import _vah
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 
 
+def ref_points_ok(reference_points, N, n_levels):
+    """Reference points the fused kernels take: (1 | N, Lq, 1 | L, 2).  The fused Functions detach them and return no
+    gradient for them; a grid shared by the batch never had one here (the adapter's is a constant), but one grid per
+    image can be learned (sigmoid reference points of a Deformable-DETR decoder): with shape[0] == N > 1 a tensor that
+    requires grad, in grad mode, keeps the unfused expression and with it its gradient."""
+    if reference_points.dim() != 4 or reference_points.shape[-1] != 2 or reference_points.shape[2] not in (1, n_levels):
+        return False
+    if reference_points.shape[0] == 1:
+        return True
+    return reference_points.shape[0] == N and not (reference_points.requires_grad and torch.is_grad_enabled())
+
+
 def fused_supported(value, offsets, logits, reference_points, n_levels, n_points):
     """True when the fused kernels cover this call (else use the unfused Function)."""
     if os.environ.get('VAH_MSDA_FUSED', '1') == '0':
         return False
     return (value.is_cuda and value.dim() == 4 and value.dtype in _DT and offsets.dtype in _DT
-            and logits.dtype == offsets.dtype and reference_points.shape[0] == 1
-            and reference_points.shape[-1] == 2 and reference_points.shape[2] in (1, n_levels)
+            and logits.dtype == offsets.dtype and ref_points_ok(reference_points, value.shape[0], n_levels)
             and bool(_vah.lib.vah_msda_fused_supported(value.shape[-1], n_levels, n_points))
             and value.numel() > 0 and offsets.numel() > 0)
 
@@ -29,11 +40,12 @@ def fused_supported(value, offsets, logits, reference_points, n_levels, n_points
 WIN_HALO = int(os.environ.get('VAH_MSDA_WIN_HALO', 5))
 
 
-def window_forward(n_levels, n_points, ref_levels, Lq):
+def window_forward(n_levels, n_points, ref_levels, Lq, ref_batch=1):
     """The LDS-window forward serves single-level calls with batch-shared reference points (VAH_MSDA_FWD_WIN=0: the
-    8-lane gather kernel).  Its schedule is built on the device from the reference points and the device copies of the
-    level geometry: nothing is read back (see _window_workspace for how one forward's six calls share it)."""
-    return (n_levels == 1 and n_points == 4 and ref_levels == 1 and Lq <= (1 << 18)
+    8-lane gather kernel, which also takes every call with one grid per image: ref_batch > 1).  Its schedule is built on
+    the device from the reference points and the device copies of the level geometry: nothing is read back (see
+    _window_workspace for how one forward's six calls share it)."""
+    return (n_levels == 1 and n_points == 4 and ref_levels == 1 and ref_batch == 1 and Lq <= (1 << 18)
             and os.environ.get('VAH_MSDA_FWD_WIN', '1') != '0')
 
 
@@ -102,12 +114,16 @@ def _window_workspace(carrier, token, spatial_shapes, level_start_index, S, Lq, 
 
 
 def fused_forward(value, spatial_shapes, level_start_index, offsets, logits, o_s, l_s, ref, carrier=None, token=None):
-    """The fused forward kernels on raw row-strided offsets / logits (see _row_strides); ref (Lq, 1 | L, 2) fp32.
+    """The fused forward kernels on raw row-strided offsets / logits (see _row_strides); ref (1 | N, Lq, 1 | L, 2) fp32,
+    or (Lq, 1 | L, 2) for a grid the batch shares.
     carrier / token: see _window_workspace (None: the window schedule is built in this call)."""
     N, S, M, D = value.shape
     _, Lq, _, L, P, _ = offsets.shape
+    if ref.dim() == 3:
+        ref = ref[None]
+    RB, RL = ref.shape[0], ref.shape[2]
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-    if window_forward(L, P, ref.shape[1], Lq):
+    if window_forward(L, P, RL, Lq, RB):
         ws, ws_bytes, ready = _window_workspace(carrier, token, spatial_shapes, level_start_index, S, Lq, value.device)
         if ws is not None:
             with _vah.on(value.device):
@@ -118,18 +134,21 @@ def fused_forward(value, spatial_shapes, level_start_index, offsets, logits, o_s
             _vah.check(rc, 'vah_msda_fused_forward_win')
             return out
     with _vah.on(value.device):
-        rc = _vah.lib.vah_msda_fused_forward(
+        rc = _vah.lib.vah_msda_fused_forward_nref(
             value.data_ptr(), _DT[value.dtype], spatial_shapes.data_ptr(),
             level_start_index.data_ptr(), offsets.data_ptr(), logits.data_ptr(),
-            _DT[offsets.dtype], o_s, l_s, ref.data_ptr(), ref.shape[1], N, S, M, D, L, Lq, P,
+            _DT[offsets.dtype], o_s, l_s, ref.data_ptr(), RL, RB, N, S, M, D, L, Lq, P,
             out.data_ptr(), _vah.raw_stream(value.device))
-    _vah.check(rc, 'vah_msda_fused_forward')
+    _vah.check(rc, 'vah_msda_fused_forward_nref')
     return out
 
 
 class MSDeformAttnFusedFunction(Function):
     """apply(value (N,S,M,32), spatial_shapes, level_start_index, offsets (N,Lq,M,L,P,2),
-    logits (N,Lq,M,L*P), reference_points (1,Lq,1|L,2)) -> (N, Lq, M*32) in value's dtype."""
+    logits (N,Lq,M,L*P), reference_points (1|N,Lq,1|L,2)) -> (N, Lq, M*32) in value's dtype.
+    reference_points with shape[0] == N are one grid per image (the Mask2Former pixel decoder's grid times valid ratios,
+    padded batches through the drop-in MSDeformAttn): the same kernels with a batch term in the reference read.  They
+    are detached and get no gradient (see ref_points_ok: the module routes learned per-image points elsewhere)."""
 
     @staticmethod
     def forward(ctx, value, spatial_shapes, level_start_index, offsets, logits, reference_points):
@@ -137,7 +156,7 @@ class MSDeformAttnFusedFunction(Function):
         _, Lq, _, L, P, _ = offsets.shape
         value = value.contiguous()
         offsets, logits, o_s, l_s = _row_strides(offsets, logits)
-        ref = reference_points.detach().float().contiguous().view(Lq, -1, 2)
+        ref = reference_points.detach().float().contiguous().view(reference_points.shape[0], Lq, -1, 2)
         out = fused_forward(value, spatial_shapes, level_start_index, offsets, logits, o_s, l_s, ref)
         ctx.save_for_backward(value, spatial_shapes, level_start_index, offsets, logits, ref)
         ctx.tiled = tiled_backward(L, P)
@@ -162,13 +181,13 @@ class MSDeformAttnFusedFunction(Function):
                 grad_value = torch.empty_like(value)
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device)
                 with _vah.on(value.device):
-                    rc = _vah.lib.vah_msda_fused_backward_tiled(
+                    rc = _vah.lib.vah_msda_fused_backward_tiled_nref(
                         value.data_ptr(), _DT[value.dtype], shapes.data_ptr(), lsi.data_ptr(),
                         offsets.data_ptr(), logits.data_ptr(), _DT[offsets.dtype], o_s, l_s, ref.data_ptr(),
-                        ref.shape[1], grad_output.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
+                        ref.shape[2], ref.shape[0], grad_output.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
                         _DT[value.dtype], d_off.data_ptr(), d_logit.data_ptr(), _DT[gdt], 0, 0,
                         ws.data_ptr(), ws_bytes, _vah.raw_stream(value.device))
-                _vah.check(rc, 'vah_msda_fused_backward_tiled')
+                _vah.check(rc, 'vah_msda_fused_backward_tiled_nref')
                 return grad_value, None, None, d_off, d_logit, None
         offsets, logits = offsets.contiguous(), logits.contiguous()
         d_off = torch.empty_like(offsets)
@@ -176,10 +195,10 @@ class MSDeformAttnFusedFunction(Function):
         # fallback: one float atomic per sample, corner and channel into a zeroed fp32 grad_value
         grad_value = torch.zeros(value.shape, dtype=torch.float32, device=value.device)
         with _vah.on(value.device):
-            rc = _vah.lib.vah_msda_fused_backward(
+            rc = _vah.lib.vah_msda_fused_backward_nref(
                 value.data_ptr(), _DT[value.dtype], shapes.data_ptr(), lsi.data_ptr(),
                 offsets.data_ptr(), logits.data_ptr(), _DT[offsets.dtype], ref.data_ptr(),
-                ref.shape[1], grad_output.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
+                ref.shape[2], ref.shape[0], grad_output.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
                 d_off.data_ptr(), d_logit.data_ptr(), _vah.raw_stream(value.device))
-        _vah.check(rc, 'vah_msda_fused_backward')
+        _vah.check(rc, 'vah_msda_fused_backward_nref')
         return grad_value.to(value.dtype), None, None, d_off, d_logit, None

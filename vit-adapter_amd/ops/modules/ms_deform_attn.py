@@ -130,7 +130,7 @@ class MSDeformAttn(nn.Module):
         offsets, logits = _linear_pair(self.sampling_offsets, self.attention_weights, query)
         offsets, logits = offsets.view(N, Lq, M, L, P, 2), logits.view(N, Lq, M, L * P)
         if fused_supported(value, offsets, logits, reference_points, L, P):
-            # softmax + location arithmetic + gather in one kernel (csrc/msda_fused.hip)
+            # softmax + location arithmetic + gather in one kernel (csrc/msda_fused.hip); reference points (1 | N, Lq, 1 | L, 2)
             out = MSDeformAttnFusedFunction.apply(value, input_spatial_shapes, input_level_start_index,
                                                   offsets, logits, reference_points)
             return _linear(self.output_proj, out)

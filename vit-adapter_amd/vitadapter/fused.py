@@ -851,8 +851,10 @@ class _MSDAPairCore(torch.autograd.Function):
         offsets = yv[..., :2 * L * P].unflatten(-1, (L, P, 2))
         logits = yv[..., 2 * L * P:]
         value = value.contiguous()
-        refc = ref.detach().float().contiguous().view(Lq, -1, 2)
-        out = mf.fused_forward(value, shapes, lsi, offsets, logits, PS, PS, refc, carrier=ref, token=BF16_COPIES.epoch)
+        refc = ref.detach().float().contiguous().view(ref.shape[0], Lq, -1, 2)
+        # the window-forward schedule rides on a grid the batch shares; one grid per image has no such schedule
+        out = mf.fused_forward(value, shapes, lsi, offsets, logits, PS, PS, refc, carrier=ref if refc.shape[0] == 1 else None,
+                               token=BF16_COPIES.epoch)
         ctx.save_for_backward(x2, w, y, value, shapes, lsi, refc, perm[1])
         ctx.dims = (N, Lq, M, L, P, wa.shape[0])
         ctx.in_shape, ctx.in_dtype = query.shape, query.dtype
@@ -872,11 +874,11 @@ class _MSDAPairCore(torch.autograd.Function):
         ws_bytes = _vah.lib.vah_msda_tile_ws_bytes(N, S, M, L, Lq, P)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device)
         with _vah.on(value.device):
-            rc = _vah.lib.vah_msda_fused_backward_tiled(
+            rc = _vah.lib.vah_msda_fused_backward_tiled_nref(
                 value.data_ptr(), 1, shapes.data_ptr(), lsi.data_ptr(), y.data_ptr(), y.data_ptr() + 2 * L * P * 4, 0, PS, PS,
-                refc.data_ptr(), refc.shape[1], gout.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(), 1,
+                refc.data_ptr(), refc.shape[2], refc.shape[0], gout.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(), 1,
                 g.data_ptr(), g.data_ptr() + 2 * L * P * 2, 1, PS, PS, ws.data_ptr(), ws_bytes, _stream(value))
-        _vah.check(rc, 'vah_msda_fused_backward_tiled')
+        _vah.check(rc, 'vah_msda_fused_backward_tiled_nref')
         gx = gw = gbias = None
         if ctx.needs_input_grad[0]:
             gx = gemm_bf16(g, w).view(ctx.in_shape)
@@ -893,8 +895,9 @@ class _MSDAPairCore(torch.autograd.Function):
 def msda_pair_core_ok(mod, query, value, reference_points):
     """The one-node form of MSDeformAttn's offsets / weights pair + core: bf16 autocast on the GPU with bf16 values, the
     tile-pass backward and shapes the fused kernels cover (D == 32, P == 4, L in {1, 3, 4}), reference points shared by
-    the batch."""
+    the batch or one grid per image (not learned ones: ops.functions.ms_deform_attn_fused.ref_points_ok)."""
     import os
+    from ops.functions.ms_deform_attn_fused import ref_points_ok
     a, b = mod.sampling_offsets, mod.attention_weights
     M, L, P = mod.n_heads, mod.n_levels, mod.n_points
     return (ENABLED['linear'] and ENABLED['linear_pair'] and ENABLED['pair_core'] and query.is_cuda and _bf16_autocast()
@@ -902,7 +905,7 @@ def msda_pair_core_ok(mod, query, value, reference_points):
             and (M * 3 * L * P) % 8 == 0            # rows of the pair GEMM / its column sums: 16-byte multiples
             and type(a) is torch.nn.Linear and type(b) is torch.nn.Linear and a.bias is not None and b.bias is not None
             and a.weight.dtype == torch.float32 and b.weight.dtype == torch.float32 and a.weight.shape[1] % 8 == 0
-            and reference_points.shape[0] == 1 and reference_points.shape[-1] == 2 and reference_points.shape[2] in (1, L)
+            and ref_points_ok(reference_points, value.shape[0], L)
             and query.numel() > 0 and value.numel() > 0 and query.dtype in (torch.bfloat16, torch.float32)
             and os.environ.get('VAH_MSDA_FUSED', '1') != '0' and os.environ.get('VAH_MSDA_TILED', '1') != '0'
             and _vah.lib.vah_msda_tile_ws_bytes(value.shape[0], value.shape[1], M, L, query.shape[1], P) >= 0)

@@ -7,7 +7,10 @@ norm_cfg=None, init_cfg=None)`` (ref: segmentation/mmseg_custom/models/plugins/
 msdeformattn_pixel_decoder.py:52-62, configs/_base_/models/mask2former_beit.py:41-51) and calls them
 through mmcv's BaseTransformerLayer with ``query`` (Lq, N, E), ``query_pos``, ``key_padding_mask``,
 ``reference_points`` (N, Lq, L, 2), ``spatial_shapes``, ``level_start_index``
-(msdeformattn_pixel_decoder.py:230-242); ``init_weights()`` is called explicitly (:154-158).
+(msdeformattn_pixel_decoder.py:230-242); ``init_weights()`` is called explicitly (:154-158).  Those reference points are
+one grid per image (the pixel centres times each image's valid ratios, :224-240): with 32-channel heads the fused kernels
+take them as they are, at any batch size; 4-component points, and per-image points that require grad, keep the unfused
+sequence (ops/functions/ms_deform_attn_fused.py::ref_points_ok).
 
 The class itself lives in mmcv (``mmcv.ops.multi_scale_deform_attn``), which is not part of the
 reference tree: its behaviour is restated here from the call sites above and mmcv 1.4's published

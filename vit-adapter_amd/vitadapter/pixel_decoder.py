@@ -8,7 +8,10 @@ The reference builds it from mmcv / mmdet registry entries (``DetrTransformerEnc
 ``MSDeformAttnPixelDecoder.forward`` (/root/reference/segmentation/mmseg_custom/models/plugins/
 msdeformattn_pixel_decoder.py:160-242): the three coarsest backbone maps, projected to 256 channels and flattened from
 low to high resolution, are the queries AND the values (Lq = S); ``query_pos`` = sine position + level embedding;
-reference points = pixel centres of every level, repeated over the levels.
+reference points = pixel centres of every level, repeated over the levels and multiplied by the valid ratios of every
+image: an (N, Lq, L, 2) tensor (:224-240).  At every batch size the attention of all six layers runs on the fused MSDA
+kernels, which read one grid per image (csrc/msda_fused.hip); under bf16 autocast that is the one-node
+pair core of vitadapter/fused.py.
 
 mmcv and mmdet are not part of the reference tree: the layer is restated from those call sites and mmcv 1.4's published
 ``BaseTransformerLayer`` / ``FFN`` (post-norm: ``x = norm(attn(x) + x)``, ``x = norm(x + ffn(x))``; the attention adds its
