@@ -95,14 +95,25 @@ int vah_msda_backward_f64(const double *value, const int64_t *shapes, const int6
  * sampling-location arithmetic + the gather in one kernel, and their gradients in one more.
  * Replaces lines 108-128 of /root/reference/detection/ops/modules/ms_deform_attn.py.
  *
- *   value     (N,S,M,32)        value_dtype: 0 = fp32, 1 = bf16   (out and grad_out use this dtype)
- *   offsets   (N,Lq,M,L,P,2)    raw sampling_offsets Linear output, param_dtype 0 = fp32 / 1 = bf16
+ *   value     (N,S,M,32)        value_dtype: 0 = fp32, 1 = bf16, 2 = fp16   (out and grad_out use this dtype)
+ *   offsets   (N,Lq,M,L,P,2)    raw sampling_offsets Linear output, param_dtype 0 = fp32 / 1 = bf16 / 2 = fp16
  *   logits    (N,Lq,M,L*P)      raw attention_weights Linear output (softmax is done in-kernel)
  *   ref       (Lq, ref_levels, 2) fp32 reference points (x, y) in [0,1], ref_levels = 1 or L,
  *             shared by the batch (the adapter's reference grids); the *_nref entry points take
  *             (ref_batch, Lq, ref_levels, 2) with ref_batch = 1 or N: one grid per image
  *   location  = ref + offsets / (W_l, H_l)
  * Supported: D == 32 and (L, P) in {(1,4), (3,4), (4,4)}  (vah_msda_fused_supported).
+ * Dtype codes: 0 and 1 mix freely between value_dtype and param_dtype.  Code 2 (fp16, what fp16 autocast hands the
+ * module) is accepted in ONE form: value / out / grad_out / grad_value fp16 AND offsets / logits / d_offsets / d_logits
+ * fp16, contiguous or row-strided, by vah_msda_fused_forward[_nref], vah_msda_fused_forward_win and
+ * vah_msda_fused_backward_tiled[_nref] (value_dtype = param_dtype = grad_value_dtype = grad_param_dtype = 2).  Any
+ * other use of code 2 - with a bf16 or fp32 partner, or in the atomic vah_msda_fused_backward[_nref], whose grad_value
+ * is fp32 - and any other code is VAH_E_UNSUPPORTED, decided on the host before any HIP call.  fp16 rows are widened
+ * exactly, the arithmetic is the fp32 arithmetic of the other forms, and every fp16 result is rounded once, at its
+ * store: to nearest even, overflow to +-inf, subnormals kept (torch's .to(float16); GradScaler needs the infs).
+ * Row strides of fp16 offsets need 8-byte alignment (16 for the other types in the window forward and the tiled
+ * backward).  Profile rows of fp16 calls: msda_fused_fwd_f16 / msda_fused_bwd_f16; other calls: msda_fused_fwd /
+ * msda_fused_bwd.
  * Backward (vah_msda_fused_backward): grad_value fp32 (N,S,M,32) zero on entry (float atomics, one per
  * sample, corner and channel as the reference); d_offsets / d_logits in param_dtype, fully written.  It is
  * the fallback of vah_msda_fused_backward_tiled below, which is what the modules call.
@@ -193,6 +204,8 @@ int vah_msda_fused_forward_win(const void *value, int value_dtype, const int64_t
  *   ws / ws_bytes          : device workspace of at least vah_msda_tile_ws_bytes(...) bytes, 16-byte
  *                            aligned, contents arbitrary (plan, list counters, entries, partial tiles, d(out)/d(p))
  *   needs D == 32, P == 4, 1 <= L <= 4 (VAH_E_UNSUPPORTED otherwise: use the functions above)
+ * fp16 values (code 2, one form, see the fused core above): as bf16 with v_mfma_f32_32x32x16_f16 and the weights as
+ * fp16 hi + lo; grad_value_dtype = grad_param_dtype = 2.
  * vah_msda_fused_backward_tiled: grad_value_dtype 0 = fp32, 1 = bf16 (bf16 values only); grad_param_dtype: type of
  * d_offsets / d_logits, = param_dtype or bf16 for fp32 offsets / logits (bf16 values only: the module keeps the
  * sampling offsets in fp32 under autocast and hands bf16 gradients to its Linear layers).  The strides are those of

@@ -13,6 +13,11 @@
 // read directly; out is written in the value's dtype.  Gather / scatter arithmetic is that of
 // msda.hip (spec: ms_deform_im2col_cuda.cuh:33-159,237-403).
 //
+// fp16 (dtype code 2, fp16 autocast) exists in ONE form - value, out, offsets and logits all fp16 - and in the forward
+// only: its gradients are the tile pass's (msda_tile.hip).  fp16 rows are widened by v_cvt_f32_f16 (exact), the math is
+// the fp32 math of the other forms, and out is rounded once by the plain cast (nearest even, overflow to +-inf,
+// subnormals kept: what torch's .to(float16) does, see fused_ops.hip).
+//
 // Restrictions of this path: D == 32, (L, P) in {(1,4), (3,4), (4,4)}, reference points with last dim 2,
 // shared by the batch (the adapter's) or one grid per image (the Mask2Former pixel decoder's grid times
 // valid ratios, segmentation/mmseg_custom/models/plugins/msdeformattn_pixel_decoder.py:224-240): `rq`, the
@@ -31,10 +36,16 @@ using namespace vah::msda;
 
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
 typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2;
+typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
+typedef __attribute__((__vector_size__(2 * sizeof(_Float16)))) _Float16 f16x2;
 
 __device__ __forceinline__ float4 load4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ float4 load4(const __bf16 *p) {
     const bf16x4 v = *reinterpret_cast<const bf16x4 *>(p);
+    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+__device__ __forceinline__ float4 load4(const _Float16 *p) {
+    const f16x4 v = *reinterpret_cast<const f16x4 *>(p);
     return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 __device__ __forceinline__ void store4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
@@ -46,9 +57,21 @@ __device__ __forceinline__ void store4(__bf16 *p, float4 v) {
     o[3] = (__bf16)v.w;
     *reinterpret_cast<bf16x4 *>(p) = o;
 }
+__device__ __forceinline__ void store4(_Float16 *p, float4 v) {
+    f16x4 o;
+    o[0] = (_Float16)v.x;
+    o[1] = (_Float16)v.y;
+    o[2] = (_Float16)v.z;
+    o[3] = (_Float16)v.w;
+    *reinterpret_cast<f16x4 *>(p) = o;
+}
 __device__ __forceinline__ float2 load2(const float *p) { return *reinterpret_cast<const float2 *>(p); }
 __device__ __forceinline__ float2 load2(const __bf16 *p) {
     const bf16x2 v = *reinterpret_cast<const bf16x2 *>(p);
+    return make_float2((float)v[0], (float)v[1]);
+}
+__device__ __forceinline__ float2 load2(const _Float16 *p) {
+    const f16x2 v = *reinterpret_cast<const f16x2 *>(p);
     return make_float2((float)v[0], (float)v[1]);
 }
 __device__ __forceinline__ void store2(float *p, float a, float b) { *reinterpret_cast<float2 *>(p) = make_float2(a, b); }
@@ -454,7 +477,10 @@ int launch_bwd(const FusedArgs &a) {
 template <bool BWD, typename VT, typename PT>
 int dispatch_lp(const FusedArgs &a) {
 #define VAH_CASE(LL, PP)                                                        \
-    if (a.L == LL && a.P == PP) return BWD ? launch_bwd<VT, PT, LL, PP>(a) : launch_fwd<VT, PT, LL, PP>(a)
+    if (a.L == LL && a.P == PP) {                                               \
+        if constexpr (BWD) return launch_bwd<VT, PT, LL, PP>(a);                \
+        else return launch_fwd<VT, PT, LL, PP>(a);       /* (fp16 has no backward instantiation here) */ \
+    }
     VAH_CASE(1, 4);
     VAH_CASE(3, 4);
     VAH_CASE(4, 4);
@@ -468,7 +494,10 @@ int dispatch(const FusedArgs &a, int value_dtype, int param_dtype) {
     if (value_dtype == 1 && param_dtype == 1) return dispatch_lp<BWD, __bf16, __bf16>(a);
     if (value_dtype == 1 && param_dtype == 0) return dispatch_lp<BWD, __bf16, float>(a);
     if (value_dtype == 0 && param_dtype == 1) return dispatch_lp<BWD, float, __bf16>(a);
-    return fail(VAH_E_UNSUPPORTED, "msda fused: dtype codes must be 0 (f32) or 1 (bf16)");
+    // fp16: the forward only (its gradients are the tile pass's: no atomic fp16 backward, no fp16 gather kernels)
+    if constexpr (!BWD)
+        if (value_dtype == 2 && param_dtype == 2) return dispatch_lp<false, _Float16, _Float16>(a);
+    return fail(VAH_E_UNSUPPORTED, "msda fused: dtype codes not instantiated (%d, %d)", value_dtype, param_dtype);
 }
 
 int check_common(const char *fn, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
@@ -487,6 +516,15 @@ int check_common(const char *fn, int64_t N, int64_t S, int64_t M, int64_t D, int
 // rows of ref between consecutive images as the kernels take it: Lq for a per-image grid, 0 for one the batch shares
 // (ref_batch == N == 1 is the shared form).  ((N - 1) * Lq + q) * ref_levels * 2 is formed in int64_t in this file.
 int64_t msda_ref_rows_per_image(int64_t ref_batch, int64_t N, int64_t Lq) { return ref_batch == N && N > 1 ? Lq : 0; }
+
+int msda_check_dtypes(const char *fn, int value_dtype, int param_dtype, bool f16_ok) {
+    const bool wide = (value_dtype | param_dtype) & ~1;          // a code other than 0 / 1 somewhere
+    if (!wide || (f16_ok && value_dtype == 2 && param_dtype == 2)) return VAH_OK;
+    if (value_dtype == 2 || param_dtype == 2)
+        return fail(VAH_E_UNSUPPORTED, f16_ok ? "%s: fp16 (code 2) comes in one form: values, offsets and logits all fp16"
+                                              : "%s: no fp16 (code 2) form of this entry point (the tiled backward has one)", fn);
+    return fail(VAH_E_UNSUPPORTED, "%s: dtype codes must be 0 (f32), 1 (bf16) or 2 (fp16)", fn);
+}
 
 int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi, const void *offsets,
                          const void *logits, int param_dtype, const float *ref, int64_t ref_levels, int64_t rq,
@@ -513,21 +551,21 @@ int fused_forward_impl(const char *fn, const void *value, int value_dtype, const
     if (int rc = check_common(fn, N, S, M, D, L, Lq, P, ref_levels, ref_batch)) return rc;
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !out) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (int rc = msda_check_dtypes(fn, value_dtype, param_dtype, true)) return rc;
     if (((uintptr_t)value | (uintptr_t)out | (uintptr_t)offsets | (uintptr_t)ref) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
     FusedArgs a{};
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
     a.ref_levels = (int)ref_levels, a.rq = msda_ref_rows_per_image(ref_batch, N, Lq);
     a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P, a.out = out;
     a.os = offsets_stride, a.ls = logits_stride;
-    if (offsets_stride < 0 || logits_stride < 0 || ((offsets_stride * (param_dtype == 1 ? 2 : 4)) % 8) ||
-        ((logits_stride * (param_dtype == 1 ? 2 : 4)) % (param_dtype == 1 ? 2 : 4)))
+    if (offsets_stride < 0 || logits_stride < 0 || ((offsets_stride * msda_dtype_bytes(param_dtype)) % 8))
         return fail(VAH_E_ALIGN, "%s: bad strides", fn);
     a.st = (hipStream_t)stream;
     // algorithmic bytes the launch really moves: value / out in the value dtype, offsets (2) + logits (1)
     // per sample in the parameter dtype; the op's fp32 definition is reported
     // beside it as def_bytes
-    const int64_t vs = value_dtype == 1 ? 2 : 4, ps = param_dtype == 1 ? 2 : 4;
-    LaunchScope scope("msda_fused_fwd", vs * (N * S * M * D + N * Lq * M * D) + ps * 3 * N * Lq * M * L * P, a.st,
+    const int64_t vs = msda_dtype_bytes(value_dtype), ps = msda_dtype_bytes(param_dtype);
+    LaunchScope scope(value_dtype == 2 ? "msda_fused_fwd_f16" : "msda_fused_fwd", vs * (N * S * M * D + N * Lq * M * D) + ps * 3 * N * Lq * M * L * P, a.st,
                       4 * (N * S * M * D + 3 * N * Lq * M * L * P + N * Lq * M * D));
     return dispatch<false>(a, value_dtype, param_dtype);
 }
@@ -544,6 +582,7 @@ int fused_backward_impl(const char *fn, const void *value, int value_dtype, cons
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !grad_out || !grad_value || !d_offsets || !d_logits)
         return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (int rc = msda_check_dtypes(fn, value_dtype, param_dtype, false)) return rc;
     FusedArgs a{};
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
     a.ref_levels = (int)ref_levels, a.rq = msda_ref_rows_per_image(ref_batch, N, Lq);

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "msda_common.h"
+#include "msda_internal.h"
 
 namespace vah {
 namespace {
@@ -29,10 +30,13 @@ constexpr int kWinThreads = 128;
 
 typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2;
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
+typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8;
 
 template <typename T>
 __device__ __forceinline__ float word_elem(const uint32_t *w, int i) {       // element i of a packed T array
     if constexpr (sizeof(T) == 4) return __builtin_bit_cast(float, w[i]);
+    else if constexpr (std::is_same<T, _Float16>::value)                      // v_cvt_f32_f16: exact, subnormals kept
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)((i & 1) ? w[i >> 1] >> 16 : w[i >> 1] & 0xFFFFu));
     else return __builtin_bit_cast(float, (i & 1) ? (w[i >> 1] & 0xFFFF0000u) : (w[i >> 1] << 16));
 }
 
@@ -271,11 +275,18 @@ __global__ __launch_bounds__(kWinThreads) void msda_fused_fwd_win(
             // ---- the row's operands: 4 offsets (x, y), 4 logits, the reference point
             uint32_t ow[kP * 2 * sizeof(PT) / 4], lw[kP * sizeof(PT) / 4];
             {
-                const uint4 *op = reinterpret_cast<const uint4 *>(off + row * os);
+                if constexpr (std::is_same<PT, _Float16>::value) {
+                    // fp16 rows are 8-byte aligned only (one fp16 [offsets | logits | gap] matrix: rows of 3 P + 8 halves)
+                    const uint2 *op = reinterpret_cast<const uint2 *>(off + row * os);
+                    const uint2 v0 = op[0], v1 = op[1];
+                    ow[0] = v0.x, ow[1] = v0.y, ow[2] = v1.x, ow[3] = v1.y;
+                } else {
+                    const uint4 *op = reinterpret_cast<const uint4 *>(off + row * os);
 #pragma unroll
-                for (int i = 0; i < (int)(kP * 2 * sizeof(PT) / 16); ++i) {
-                    const uint4 v = op[i];
-                    ow[4 * i] = v.x, ow[4 * i + 1] = v.y, ow[4 * i + 2] = v.z, ow[4 * i + 3] = v.w;
+                    for (int i = 0; i < (int)(kP * 2 * sizeof(PT) / 16); ++i) {
+                        const uint4 v = op[i];
+                        ow[4 * i] = v.x, ow[4 * i + 1] = v.y, ow[4 * i + 2] = v.z, ow[4 * i + 3] = v.w;
+                    }
                 }
                 const uint2 *lp = reinterpret_cast<const uint2 *>(logit + row * ls);
 #pragma unroll
@@ -332,6 +343,14 @@ __global__ __launch_bounds__(kWinThreads) void msda_fused_fwd_win(
             if constexpr (std::is_same<VT, float>::value) {
 #pragma unroll
                 for (int c = 0; c < kD; c += 4) *reinterpret_cast<float4 *>(dst + c) = make_float4(acc[c], acc[c + 1], acc[c + 2], acc[c + 3]);
+            } else if constexpr (std::is_same<VT, _Float16>::value) {
+#pragma unroll
+                for (int c = 0; c < kD; c += 8) {
+                    f16x8 o;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[e] = (_Float16)acc[c + e];     // nearest even, overflow to inf, subnormals kept
+                    *reinterpret_cast<f16x8 *>(dst + c) = o;
+                }
             } else {
 #pragma unroll
                 for (int c = 0; c < kD; c += 8) {
@@ -399,17 +418,18 @@ int vah_msda_fused_forward_win(const void *value, int value_dtype, const int64_t
     if (D != kD || P != kP) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32, P == 4 (one level)", fn);
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !ws || !out) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (int rc = msda_check_dtypes(fn, value_dtype, param_dtype, true)) return rc;
     const int64_t need = vah_msda_win_ws_bytes(S, Lq);
     if (need < 0) return VAH_E_UNSUPPORTED;
     if (ws_bytes < need) return fail(VAH_E_SHAPE, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes, (long long)need);
-    const int64_t ps = param_dtype == 1 ? 2 : 4;
+    const int64_t ps = msda_dtype_bytes(param_dtype);
     const int64_t os = offsets_stride ? offsets_stride : kP * 2, ls = logits_stride ? logits_stride : kP;
     if (((uintptr_t)value | (uintptr_t)out | (uintptr_t)offsets | (uintptr_t)ws) % 16 || ((uintptr_t)logits | (uintptr_t)ref) % 8 ||
-        (os * ps) % 16 || (ls * ps) % 8)
+        (os * ps) % (param_dtype == 2 ? 8 : 16) || (ls * ps) % 8)
         return fail(VAH_E_ALIGN, "%s: misaligned", fn);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t vs = value_dtype == 1 ? 2 : 4;
-    LaunchScope scope("msda_fused_fwd", vs * (N * S * M * D + N * Lq * M * D) + ps * 3 * N * Lq * M * P, st,
+    const int64_t vs = msda_dtype_bytes(value_dtype);
+    LaunchScope scope(value_dtype == 2 ? "msda_fused_fwd_f16" : "msda_fused_fwd", vs * (N * S * M * D + N * Lq * M * D) + ps * 3 * N * Lq * M * P, st,
                       4 * (N * S * M * D + 3 * N * Lq * M * P + N * Lq * M * D));
 #define VAH_CASE(VT, VC, PT, PC)                                                                                     \
     if (value_dtype == VC && param_dtype == PC)                                                                      \
@@ -418,8 +438,9 @@ int vah_msda_fused_forward_win(const void *value, int value_dtype, const int64_t
     VAH_CASE(__bf16, 1, __bf16, 1);
     VAH_CASE(__bf16, 1, float, 0);
     VAH_CASE(float, 0, __bf16, 1);
+    VAH_CASE(_Float16, 2, _Float16, 2);
 #undef VAH_CASE
-    return fail(VAH_E_UNSUPPORTED, "%s: dtype codes must be 0 (f32) or 1 (bf16)", fn);
+    return fail(VAH_E_UNSUPPORTED, "%s: dtype codes not instantiated (%d, %d)", fn, value_dtype, param_dtype);
 }
 
 }  // extern "C"

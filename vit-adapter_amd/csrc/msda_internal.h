@@ -21,4 +21,10 @@ int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shap
                          const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t L, int64_t Lq, int64_t P, void *d_offsets,
                          void *d_logits, hipStream_t st);
 
+// Dtype codes of the fused core: 0 = fp32, 1 = bf16, 2 = fp16.  fp32 and bf16 mix freely between values and
+// parameters; fp16 comes in one form (values, offsets, logits - and every gradient - fp16) and only where f16_ok:
+// the forward entry points and the tiled backward.  VAH_OK, or VAH_E_UNSUPPORTED with the message set.
+int msda_check_dtypes(const char *fn, int value_dtype, int param_dtype, bool f16_ok);
+inline int64_t msda_dtype_bytes(int code) { return code == 0 ? 4 : 2; }
+
 }  // namespace vah

@@ -30,9 +30,10 @@
 //                    * dV^T[32 ch, 32 px] += G^T[32 ch, 64 entries] x Wt^T[64 entries, 32 px] on the matrix cores
 //                      (lane k builds column k of Wt - attention x bilinear weight of its entry's corners inside the
 //                      tile - with plain LDS read-add-writes on its OWN column; bf16 rows: v_mfma_f32_32x32x16_bf16
-//                      with Wt as bf16 hi + lo; fp32 rows: v_mfma_f32_32x32x2_f32).  The accumulator has the pixel
+//                      with Wt as bf16 hi + lo; fp16 rows: v_mfma_f32_32x32x16_f16, the same fragments, Wt as fp16
+//                      hi + lo; fp32 rows: v_mfma_f32_32x32x2_f32).  The accumulator has the pixel
 //                      on the lane: the tile is stored straight from registers (8 / 16 bytes per lane and row);
-//                    * bf16 rows: the corner dot products <grad_out row, value row> of every entry against the
+//                    * bf16 / fp16 rows: the corner dot products <grad_out row, value row> of every entry against the
 //                      tile's 10 x 6-pixel value window as ONE more product Dd^T[60 px, 64 entries] = V x G^T (value
 //                      fragments stay in registers for the whole list), handed to the entry's lane through LDS;
 //                      a sample is OWNED by the tile of its first in-map corner and the owner writes d(offset) and
@@ -79,7 +80,30 @@ constexpr int kWinW = kTW + 2, kWinH = kTH + 2, kWinPx = kWinW * kWinH;   // val
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
 typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2;
+typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8;
+typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
+typedef __attribute__((__vector_size__(2 * sizeof(_Float16)))) _Float16 f16x2;
 typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
+
+// The 16-bit row type of an instantiation and its vectors.  fp32 rows never touch them: they get the bf16 spelling so
+// that the declarations shared by all three compile.
+template <typename T>
+struct Half {
+    typedef __bf16 elem;
+    typedef bf16x8 x8;
+    typedef bf16x4 x4;
+    typedef bf16x2 x2;
+};
+template <>
+struct Half<_Float16> {
+    typedef _Float16 elem;
+    typedef f16x8 x8;
+    typedef f16x4 x4;
+    typedef f16x2 x2;
+};
+// same fragment layout for both 16-bit types (8 consecutive k per lane, lanes 32.. the second 8)
+__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8;
 
@@ -376,13 +400,16 @@ struct PlainSrc {
 template <typename PT>
 __device__ __forceinline__ float word_elem(const uint32_t *w, int i) {       // element i of a packed PT array
     if constexpr (sizeof(PT) == 4) return __builtin_bit_cast(float, w[i]);
+    else if constexpr (std::is_same<PT, _Float16>::value)                                                // v_cvt_f32_f16: exact
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)((i & 1) ? w[i >> 1] >> 16 : w[i >> 1] & 0xFFFFu));
     else return __builtin_bit_cast(float, (i & 1) ? (w[i >> 1] & 0xFFFF0000u) : (w[i >> 1] << 16));     // bf16 -> f32
 }
 
 // Fused: raw sampling_offsets / attention logits of the MSDeformAttn module + the reference grid
 // (arithmetic of msda_fused.hip: loc = ref + off / (W, H), softmax over the L*P logits).
 // PT: type of offsets / logits; GPT: type their gradients are written in (the module's Linear layers take bf16
-// gradients under autocast also when their outputs are kept in fp32).
+// gradients under autocast also when their outputs are kept in fp32).  fp16: PT = GPT = _Float16 only; its rows need
+// 8-byte, not 16-byte, alignment (an fp16 [offsets | logits | gap] matrix has rows of 3 L P + 8 halves).
 template <typename PT, typename GPT, int L>
 struct FusedSrc {
     const PT *off, *logit;
@@ -395,7 +422,7 @@ struct FusedSrc {
     static constexpr int OW = kP * 2 * (int)sizeof(PT) / 4;      // words of one level's offsets (4 or 8)
     static constexpr int LW = LP * (int)sizeof(PT) / 4;          // words of the row's logits (even)
     // The tile pass writes one RECORD per owned sample - {d(offset x), d(offset y), d(out)/d(attention probability)} -
-    // into a scratch (N,Lq,M,L*P) of 8-byte (bf16 gradients) / 16-byte (fp32 gradients) records: a tile owns some of a
+    // into a scratch (N,Lq,M,L*P) of 8-byte (bf16 / fp16 gradients: rounded here, once) / 16-byte (fp32 gradients) records: a tile owns some of a
     // row's samples, and every partial store instruction costs a wave 64 cache-line visits whatever its width - one
     // 8-byte store per owned sample instead of a 4-byte d(offset) and a 4-byte d(p) store.  msda_grad_finish turns
     // the records into d_offsets and (softmax backward) d_logits.
@@ -403,8 +430,8 @@ struct FusedSrc {
     uint32_t *rec;
     __device__ __forceinline__ void pack(float gx, float gy, float ga_, uint32_t (&w)[RW]) const {
         if constexpr (RW == 2) {
-            bf16x2 o;
-            o[0] = (__bf16)gx, o[1] = (__bf16)gy;
+            typename Half<GPT>::x2 o;
+            o[0] = (GPT)gx, o[1] = (GPT)gy;
             w[0] = __builtin_bit_cast(uint32_t, o), w[1] = __builtin_bit_cast(uint32_t, ga_);
         } else {
             w[0] = __builtin_bit_cast(uint32_t, gx), w[1] = __builtin_bit_cast(uint32_t, gy);
@@ -444,11 +471,17 @@ struct FusedSrc {
     template <bool WEIGHTS>
     __device__ __forceinline__ Raw load(int row, int rr, int l) const {
         Raw r;
-        const uint4 *op = reinterpret_cast<const uint4 *>(off + row * os + l * kP * 2);           // 16-byte aligned
+        if constexpr (std::is_same<PT, _Float16>::value) {
+            const uint2 *op = reinterpret_cast<const uint2 *>(off + row * os + l * kP * 2);       // 8-byte aligned
+            const uint2 v0 = op[0], v1 = op[1];
+            r.o[0] = v0.x, r.o[1] = v0.y, r.o[2] = v1.x, r.o[3] = v1.y;
+        } else {
+            const uint4 *op = reinterpret_cast<const uint4 *>(off + row * os + l * kP * 2);       // 16-byte aligned
 #pragma unroll
-        for (int i = 0; i < OW / 4; ++i) {
-            const uint4 v = op[i];
-            r.o[4 * i] = v.x, r.o[4 * i + 1] = v.y, r.o[4 * i + 2] = v.z, r.o[4 * i + 3] = v.w;
+            for (int i = 0; i < OW / 4; ++i) {
+                const uint4 v = op[i];
+                r.o[4 * i] = v.x, r.o[4 * i + 1] = v.y, r.o[4 * i + 2] = v.z, r.o[4 * i + 3] = v.w;
+            }
         }
         r.rp = *reinterpret_cast<const float2 *>(ref + (rr * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
         const uint2 *lp = reinterpret_cast<const uint2 *>(logit + row * ls);                       // 8-byte aligned
@@ -667,8 +700,8 @@ __global__ __launch_bounds__(256) void msda_bin(Src src, const unsigned char *__
 }
 
 // ---- pass 2: the tile pass -------------------------------------------------------------------------------------------
-// LDS per wave: R = Wt[32 px + 1 dummy][WS] fp32 (aliased, bf16 rows with TAPS, by Dd[32 entries][DP] fp32) + G[64 entries][32 ch].
-//   bf16: WS = 68 (272-byte rows: the 8-float fragment reads are conflict-free ds_read_b128)
+// LDS per wave: R = Wt[32 px + 1 dummy][WS] fp32 (aliased, 16-bit rows with TAPS, by Dd[32 entries][DP] fp32) + G[64 entries][32 ch].
+//   bf16 / fp16: WS = 68 (272-byte rows: the 8-float fragment reads are conflict-free ds_read_b128)
 //   fp32: WS = 65 (the one-float fragment reads of v_mfma_f32_32x32x2_f32 are conflict-free)
 template <typename GT>
 struct TileLds {
@@ -726,7 +759,7 @@ __device__ __forceinline__ Run make_run(const Item &it, int count, int Lq, bool 
     return rn;
 }
 
-// TAPS: the tile also computes d(location) / d(attention) of the samples it owns (bf16 rows only; else a gather kernel
+// TAPS: the tile also computes d(location) / d(attention) of the samples it owns (16-bit rows only; else a gather kernel
 // of msda.hip / msda_fused.hip does).  WPS: waves per SIMD the register budget is set for.
 template <typename GT, typename OT, typename Src, bool TAPS, int WPS, bool EARLY>
 __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__restrict__ plan, int *__restrict__ counter,
@@ -737,7 +770,9 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
     using LD = TileLds<GT>;
     constexpr int WS = LD::WS, DP = LD::DP;
     constexpr bool F32 = std::is_same<GT, float>::value;
-    static_assert(!(TAPS && F32), "in-tile dot products are built for bf16 rows");
+    static_assert(!(TAPS && F32), "in-tile dot products are built for 16-bit rows");
+    typedef typename Half<GT>::elem HT;         // the 16-bit row type (fp32 rows: unused)
+    typedef typename Half<GT>::x8 h8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     float *Wt = reinterpret_cast<float *>(smem);
@@ -781,7 +816,7 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
     };
     // value fragments of an item's window for the dot products: lane (px = r + 32 pb, half h) holds value[px][16 s + 8 h ..]
     struct VFrag {
-        bf16x8 v00, v01, v10, v11;      // [pixel block][channel half]
+        h8 v00, v01, v10, v11;          // [pixel block][channel half]
     };
     auto load_vfrag = [&](int n_, int m_, int start_, int ty_, int tx_, int H_, int W_) __attribute__((always_inline)) -> VFrag {
         VFrag f{};
@@ -802,8 +837,8 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                     v[pb][s] = in ? t : make_uint4(0, 0, 0, 0);
                 }
             }
-            f.v00 = __builtin_bit_cast(bf16x8, v[0][0]), f.v01 = __builtin_bit_cast(bf16x8, v[0][1]);
-            f.v10 = __builtin_bit_cast(bf16x8, v[1][0]), f.v11 = __builtin_bit_cast(bf16x8, v[1][1]);
+            f.v00 = __builtin_bit_cast(h8, v[0][0]), f.v01 = __builtin_bit_cast(h8, v[0][1]);
+            f.v10 = __builtin_bit_cast(h8, v[1][0]), f.v11 = __builtin_bit_cast(h8, v[1][1]);
         }
         return f;
     };
@@ -942,15 +977,15 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
 #pragma unroll
                     for (int eb = 0; eb < 2; ++eb) {
                         const uint4 *grow = reinterpret_cast<const uint4 *>(Gs + (32 * eb + r) * kD);
-                        const bf16x8 b0 = __builtin_bit_cast(bf16x8, grow[h]), b1 = __builtin_bit_cast(bf16x8, grow[2 + h]);
+                        const h8 b0 = __builtin_bit_cast(h8, grow[h]), b1 = __builtin_bit_cast(h8, grow[2 + h]);
                         float *drow = Dd + r * DP + 4 * h;
 #pragma unroll
                         for (int pb = 0; pb < 2; ++pb) {
                             f32x16 dd;
 #pragma unroll
                             for (int i = 0; i < 16; ++i) dd[i] = 0.f;
-                            dd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pb ? vf.v10 : vf.v00, b0, dd, 0, 0, 0);
-                            dd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pb ? vf.v11 : vf.v01, b1, dd, 0, 0, 0);
+                            dd = mfma16(pb ? vf.v10 : vf.v00, b0, dd);
+                            dd = mfma16(pb ? vf.v11 : vf.v01, b1, dd);
 #pragma unroll
                             for (int gq = 0; gq < 4; ++gq)
                                 *reinterpret_cast<float4 *>(drow + 32 * pb + 8 * gq) = make_float4(dd[4 * gq], dd[4 * gq + 1], dd[4 * gq + 2], dd[4 * gq + 3]);
@@ -1033,7 +1068,7 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                     // ds_read_b64_tr_b16: lane 4q+p of a 16-lane group names row q, columns 4p..4p+3 of a 4 x 16 block
                     // and receives column (lane & 15) of its 4 rows (checked on the GPU: tools/ubench/tr_read.hip).
                     // Group g: columns 16(g&1).., rows 8(g>>1) + 4r + q.
-                    const __bf16 *gbase = reinterpret_cast<const __bf16 *>(Gs) + (8 * (grp >> 1) + qq) * kD + 16 * (grp & 1) + 4 * pp;
+                    const HT *gbase = reinterpret_cast<const HT *>(Gs) + (8 * (grp >> 1) + qq) * kD + 16 * (grp & 1) + 4 * pp;
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
@@ -1041,19 +1076,21 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                         const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                             (s16x4 __attribute__((address_space(3))) *)(gbase + (16 * s + 4) * kD));
                         const s16x8 t01 = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
-                        const bf16x8 gfr = __builtin_bit_cast(bf16x8, t01);
+                        const h8 gfr = __builtin_bit_cast(h8, t01);
                         const float *wp = Wt + r * WS + 16 * s + 8 * h;
                         const float4 w0 = *reinterpret_cast<const float4 *>(wp);
                         const float4 w1 = *reinterpret_cast<const float4 *>(wp + 4);
                         const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-                        bf16x8 whi, wlo;
+                        // the fp32 weight as hi + lo of the row type: bf16 8 + 8 bits; fp16 11 + 11 bits (lo of a weight
+                        // below 2^-3 is an fp16 subnormal: exact to 2^-25 absolute where the matrix core keeps it)
+                        h8 whi, wlo;
 #pragma unroll
                         for (int jj = 0; jj < 8; ++jj) {
-                            whi[jj] = (__bf16)wv[jj];
-                            wlo[jj] = (__bf16)(wv[jj] - (float)whi[jj]);
+                            whi[jj] = (HT)wv[jj];
+                            wlo[jj] = (HT)(wv[jj] - (float)whi[jj]);
                         }
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gfr, whi, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gfr, wlo, acc, 0, 0, 0);
+                        acc = mfma16(gfr, whi, acc);
+                        acc = mfma16(gfr, wlo, acc);
                     }
                 }
                 VAH_PHASE();
@@ -1111,11 +1148,11 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                     for (int gq = 0; gq < 4; ++gq) {
                         if constexpr (std::is_same<OT, float>::value) {
                             *reinterpret_cast<float4 *>(dst + 8 * gq) = make_float4(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
-                        } else {
-                            bf16x4 o;
+                        } else {        // bf16; fp16: the plain cast (nearest even, overflow to +-inf, subnormals kept)
+                            typename Half<OT>::x4 o;
 #pragma unroll
-                            for (int c = 0; c < 4; ++c) o[c] = (__bf16)acc[4 * gq + c];
-                            *reinterpret_cast<bf16x4 *>(dst + 8 * gq) = o;
+                            for (int c = 0; c < 4; ++c) o[c] = (OT)acc[4 * gq + c];
+                            *reinterpret_cast<typename Half<OT>::x4 *>(dst + 8 * gq) = o;
                         }
                     }
                 } else {
@@ -1126,6 +1163,12 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                         for (int c = 0; c < 4; ++c) {
                             if constexpr (std::is_same<OT, float>::value) {
                                 atomicAdd(dst + 8 * gq + c, acc[4 * gq + c]);
+                            } else if constexpr (std::is_same<OT, _Float16>::value) {
+                                if ((c & 1) == 0) {
+                                    f16x2 pr;
+                                    pr[0] = (_Float16)acc[4 * gq + c], pr[1] = (_Float16)acc[4 * gq + c + 1];
+                                    __builtin_amdgcn_global_atomic_fadd_v2f16((f16x2 __attribute__((address_space(1))) *)(dst + 8 * gq + c), pr);
+                                }
                             } else if ((c & 1) == 0) {
                                 bf16x2 pr;
                                 pr[0] = (__bf16)acc[4 * gq + c], pr[1] = (__bf16)acc[4 * gq + c + 1];
@@ -1252,21 +1295,24 @@ int run_tiled(const char *fn, const Src &src, const Bounds &bd, const int64_t *s
     return check_launch(fn);
 }
 
-// Who computes d(offsets) / d(logits)?  bf16 rows: the tile pass (matrix-core dot products against the tile's value
+// Who computes d(offsets) / d(logits)?  bf16 and fp16 rows: the tile pass (matrix-core dot products against the tile's value
 // window); fp32 rows: the gather kernels of msda.hip / msda_fused.hip in front (exact fp32 dot products).
 template <typename VT>
-constexpr bool kTapsInTile = std::is_same<VT, __bf16>::value;
+constexpr bool kTapsInTile = std::is_same<VT, __bf16>::value || std::is_same<VT, _Float16>::value;
 
 template <typename VT, typename PT, typename GPT, int L>
 int fused_tiled(const char *fn, const Bounds &bd, const void *value, const int64_t *shapes, const int64_t *lsi, const void *off,
                 const void *logit, int64_t os, int64_t ls, const float *ref, int ref_levels, int rq, int64_t N, int64_t M, int64_t Lq, int64_t S,
-                const void *grad_out, void *grad_value, int gv_bf16, void *d_off, void *d_logit, int64_t dos, int64_t dls, void *ws,
+                const void *grad_out, void *grad_value, int gv_16, void *d_off, void *d_logit, int64_t dos, int64_t dls, void *ws,
                 hipStream_t st) {
     constexpr bool TAPS = kTapsInTile<VT>;
     uint32_t *rec = (uint32_t *)((char *)ws + bd.off_ga);
     FusedSrc<PT, GPT, L> src{(const PT *)off, (const PT *)logit, ref, ref_levels, rq, (int)os, (int)ls, rec};
     int rc;
-    if (gv_bf16) {
+    if constexpr (std::is_same<VT, _Float16>::value) {          // fp16: one form, grad_value in fp16
+        rc = run_tiled<VT, VT, FusedSrc<PT, GPT, L>, TAPS>(fn, src, bd, shapes, lsi, N, M, L, Lq, S, (const VT *)value,
+                                                           (const VT *)grad_out, (VT *)grad_value, ws, st);
+    } else if (gv_16) {
         if constexpr (std::is_same<VT, __bf16>::value)
             rc = run_tiled<VT, __bf16, FusedSrc<PT, GPT, L>, TAPS>(fn, src, bd, shapes, lsi, N, M, L, Lq, S, (const VT *)value,
                                                                  (const VT *)grad_out, (__bf16 *)grad_value, ws, st);
@@ -1300,15 +1346,18 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
         return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (((uintptr_t)grad_out | (uintptr_t)grad_value | (uintptr_t)ws | (uintptr_t)offsets) % 16 || ((uintptr_t)d_offsets | (uintptr_t)ref) % 8)
         return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    if ((value_dtype | param_dtype | grad_value_dtype | grad_param_dtype) & ~1)
-        return fail(VAH_E_UNSUPPORTED, "%s: dtype codes must be 0 (f32) or 1 (bf16)", fn);
+    if (int rc = msda_check_dtypes(fn, value_dtype, param_dtype, true)) return rc;
+    const bool f16 = value_dtype == 2;
+    if (f16 ? (grad_value_dtype != 2 || grad_param_dtype != 2) : ((grad_value_dtype | grad_param_dtype) & ~1) != 0)
+        return fail(VAH_E_UNSUPPORTED, "%s: gradient dtype codes must be 0 (f32) or 1 (bf16); with fp16 operands (code 2), and only then, all 2", fn);
     if (grad_param_dtype != param_dtype && !(param_dtype == 0 && grad_param_dtype == 1))
         return fail(VAH_E_UNSUPPORTED, "%s: gradients of fp32 offsets / logits may be bf16, not the reverse", fn);
-    const int64_t vs = value_dtype ? 2 : 4, ps = param_dtype ? 2 : 4, gps = grad_param_dtype ? 2 : 4, gs = grad_value_dtype ? 2 : 4;
+    const int64_t vs = msda_dtype_bytes(value_dtype), ps = msda_dtype_bytes(param_dtype), gps = msda_dtype_bytes(grad_param_dtype),
+                  gs = msda_dtype_bytes(grad_value_dtype);
     const int64_t os = offsets_stride ? offsets_stride : L * P * 2, ls = logits_stride ? logits_stride : L * P;
     const int64_t dos = d_offsets_stride ? d_offsets_stride : L * P * 2, dls = d_logits_stride ? d_logits_stride : L * P;
     const bool strided = os != L * P * 2 || ls != L * P || dos != L * P * 2 || dls != L * P;
-    if (os < L * P * 2 || ls < L * P || dos < L * P * 2 || dls < L * P || (os * ps) % 16 || (ls * ps) % 8 || (dos * gps) % (gps == 4 ? 16 : 8) ||
+    if (os < L * P * 2 || ls < L * P || dos < L * P * 2 || dls < L * P || (os * ps) % (f16 ? 8 : 16) || (ls * ps) % 8 || (dos * gps) % (gps == 4 ? 16 : 8) ||
         ((uintptr_t)logits) % 8 || (dls * gps) % gps || N * Lq * M * (os > ls ? os : ls) >= ((int64_t)1 << 31))
         return fail(VAH_E_ALIGN, "%s: bad strides", fn);
     // the passes index ref in int: N * Lq * ref_levels * 2 <= N * Lq * 2 * L < N * Lq * M * os < 2^31 by the check above
@@ -1318,11 +1367,11 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
     if (int rc = make_bounds(fn, N, S, M, L, Lq, P, &bd)) return rc;
     if (ws_bytes < bd.total) return fail(VAH_E_SHAPE, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes, (long long)bd.total);
     hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("msda_fused_bwd", vs * (N * S * M * D + N * Lq * M * D) + gs * N * S * M * D + (ps + gps) * 3 * N * Lq * M * L * P, st,
+    LaunchScope scope(f16 ? "msda_fused_bwd_f16" : "msda_fused_bwd", vs * (N * S * M * D + N * Lq * M * D) + gs * N * S * M * D + (ps + gps) * 3 * N * Lq * M * L * P, st,
                       4 * (2 * N * S * M * D + 6 * N * Lq * M * L * P + N * Lq * M * D));
     // d(offsets), d(logits) from the gather kernel of msda_fused.hip (nothing scattered) where the tile pass does not
     // compute them itself (fp32 values)
-    if (value_dtype != 1) {
+    if (value_dtype == 0) {
         if (grad_param_dtype != param_dtype || strided)
             return fail(VAH_E_UNSUPPORTED, "%s: fp32 values write gradients in the parameter dtype, contiguous tensors only", fn);
         if (int rc = msda_fused_grad_taps(value, value_dtype, shapes, lsi, offsets, logits, param_dtype, ref, ref_levels, rq, grad_out,
@@ -1338,7 +1387,8 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
     VAH_CASE(__bf16, 1, __bf16, 1, __bf16, 1, LL);     \
     VAH_CASE(__bf16, 1, float, 0, float, 0, LL);       \
     VAH_CASE(__bf16, 1, float, 0, __bf16, 1, LL);      \
-    VAH_CASE(float, 0, __bf16, 1, __bf16, 1, LL)
+    VAH_CASE(float, 0, __bf16, 1, __bf16, 1, LL);      \
+    VAH_CASE(_Float16, 2, _Float16, 2, _Float16, 2, LL)
     VAH_CASES(1);
     VAH_CASES(3);
     VAH_CASES(4);

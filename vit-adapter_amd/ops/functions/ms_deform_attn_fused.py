@@ -1,5 +1,6 @@
 """Fused core of MSDeformAttn.forward: softmax(logits) + sampling locations + gather in one HIP
-kernel (csrc/msda_fused.hip); gradients by the tile pass of csrc/msda_tile.hip.  Not part of the reference's surface (its
+kernel (csrc/msda_fused.hip); gradients by the tile pass of csrc/msda_tile.hip.  fp32, bf16 and - in one form, every
+operand and gradient fp16: what fp16 autocast hands the module - fp16.  Not part of the reference's surface (its
 module does these steps with ~8 PyTorch ops around MSDeformAttnFunction,
 /root/reference/detection/ops/modules/ms_deform_attn.py:108-128); ops.modules.MSDeformAttn uses it
 when the shapes allow and otherwise keeps the reference sequence.
@@ -12,7 +13,30 @@ from torch.autograd.function import once_differentiable
 
 import _vah
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}          # the dtype codes of include/vitadapter_hip.h
+
+
+def _fp16_enabled():
+    """ENABLED['fp16_msda'] of vitadapter.fused (VAH_FUSED_DISABLE=fp16_msda: the reference's op sequence under fp16
+    autocast, for A/B runs).  Resolved per call: `vitadapter` imports this package.  With ops/ on its own the
+    environment variable is read here."""
+    try:
+        from vitadapter import fused
+    except ImportError:
+        return 'fp16_msda' not in [k.strip() for k in os.environ.get('VAH_FUSED_DISABLE', '').split(',')]
+    return fused.ENABLED['fp16_msda']
+
+
+def _dtypes_ok(value, offsets, logits, n_levels, n_points):
+    """fp32 and bf16 mix between the values and the parameters; fp16 comes in one form - value, offsets and logits all
+    fp16 - and has no atomic backward, so only where the tile pass serves (L, P) and the problem's size."""
+    if logits.dtype != offsets.dtype or value.dtype not in _DT or offsets.dtype not in _DT:
+        return False
+    if torch.float16 in (value.dtype, offsets.dtype):
+        return (value.dtype == offsets.dtype and tiled_backward(n_levels, n_points) and _fp16_enabled()
+                and _vah.lib.vah_msda_tile_ws_bytes(value.shape[0], value.shape[1], value.shape[2], n_levels,
+                                                    offsets.shape[1], n_points) >= 0)
+    return True
 
 
 def ref_points_ok(reference_points, N, n_levels):
@@ -31,8 +55,8 @@ def fused_supported(value, offsets, logits, reference_points, n_levels, n_points
     """True when the fused kernels cover this call (else use the unfused Function)."""
     if os.environ.get('VAH_MSDA_FUSED', '1') == '0':
         return False
-    return (value.is_cuda and value.dim() == 4 and value.dtype in _DT and offsets.dtype in _DT
-            and logits.dtype == offsets.dtype and ref_points_ok(reference_points, value.shape[0], n_levels)
+    return (value.is_cuda and value.dim() == 4 and _dtypes_ok(value, offsets, logits, n_levels, n_points)
+            and ref_points_ok(reference_points, value.shape[0], n_levels)
             and bool(_vah.lib.vah_msda_fused_supported(value.shape[-1], n_levels, n_points))
             and value.numel() > 0 and offsets.numel() > 0)
 
@@ -146,6 +170,7 @@ def fused_forward(value, spatial_shapes, level_start_index, offsets, logits, o_s
 class MSDeformAttnFusedFunction(Function):
     """apply(value (N,S,M,32), spatial_shapes, level_start_index, offsets (N,Lq,M,L,P,2),
     logits (N,Lq,M,L*P), reference_points (1|N,Lq,1|L,2)) -> (N, Lq, M*32) in value's dtype.
+    Gradients: grad_value in value's dtype, d_offsets / d_logits in the offsets' (fp16 for fp16 operands).
     reference_points with shape[0] == N are one grid per image (the Mask2Former pixel decoder's grid times valid ratios,
     padded batches through the drop-in MSDeformAttn): the same kernels with a batch term in the reference read.  They
     are detached and get no gradient (see ref_points_ok: the module routes learned per-image points elsewhere)."""
@@ -174,6 +199,8 @@ class MSDeformAttnFusedFunction(Function):
             # atomic-free tile pass (csrc/msda_tile.hip): grad_value is STORED, in the value's dtype.  Nothing about the
             # level geometry is read back to the host: grid and workspace follow from the tensor shapes.
             ws_bytes = _vah.lib.vah_msda_tile_ws_bytes(N, S, M, L, Lq, P)
+            if ws_bytes < 0 and value.dtype == torch.float16:
+                raise RuntimeError('fused MSDeformAttn: no fp16 backward for this problem size (%s)' % _vah.lib.vah_last_error().decode())
             if ws_bytes >= 0:
                 gdt = offsets.dtype
                 d_off = torch.empty(offsets.shape, dtype=gdt, device=offsets.device)

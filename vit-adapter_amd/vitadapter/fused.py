@@ -10,7 +10,9 @@ DWConv - also take fp16 autocast (the reference's AMP mode): the same kernels in
 (`*_f16` entry points), fp32 math, fp32 -> fp16 rounded to nearest even with overflow to inf and
 subnormals kept.  So does the output tail (csrc/tail_ops.hip: the BatchNorm tail, bn_relu, halve, the token <-> plane
 transposes, the NCHW max-pool and up_from_tokens, whose two products are torch's fp16 library GEMMs).  Linear, conv1x1,
-patch embedding and the MSDA pair core stay bf16-only; under fp16 autocast they are torch's.
+patch embedding and the MSDA pair core stay bf16-only; under fp16 autocast they are torch's - the deformable attention
+itself is not: MSDeformAttn's fp16 value / offsets / logits go to the fp16 instantiation of the fused MSDA kernels
+(ops/functions/ms_deform_attn_fused.py; ENABLED['fp16_msda']).
 """
 import os
 
@@ -21,7 +23,8 @@ import _vah
 
 ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln': True, 'dwconv': True, 'linear': True, 'bn_tail': True,
            'bn_relu': True, 'bias_fold': True, 'keep_feat': True, 'maps': True, 'maps_in': True, 'linear_pair': True, 'maxpool': True, 'conv1x1': True, 'ln_dual': True, 'wgrad_fin': True, 'spm_nhwc': True, 'up_gemm': True, 'patch_gemm': True, 'wgrad_overlap': True, 'drop_pool': True,
-           'fp16_rows': True, 'fp16_spm': True, 'fp16_tail': True, 'bias_partials': True}
+           'fp16_rows': True, 'fp16_spm': True, 'fp16_tail': True, 'bias_partials': True,
+           'fp16_msda': True}        # fp16_msda: read by ops.functions.ms_deform_attn_fused.fused_supported
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
