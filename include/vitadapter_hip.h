@@ -421,6 +421,22 @@ int vah_scale_residual_bwd_bsum(const float *g, const void *z_bf16, const float 
                                 float *ws, float *bpart, int64_t *nparts, void *stream);
 int vah_gelu_bwd_bsum_bf16(const void *da_bf16, const void *h_bf16, int64_t rows, int64_t C, void *dh_bf16,
                            float *bpart, int64_t *nparts, void *stream);
+/* fp16 twins of the five entry points above (fp16 autocast: the Linear layers on vah_gemm_f16): the same signatures,
+ * checks, codes and messages, _Float16 where those read or write bf16; fp32 math, one rounding at each 16-bit store
+ * (nearest even, overflow to +-inf, subnormals kept).  The two `_bsum` forms of the residual kernels are the `_bsum`
+ * forms of vah_residual_layernorm_bwd_f16 / vah_scale_residual_bwd_f16 and are named after them. */
+int vah_colsum_f16(const void *g_f16, int64_t rows, int64_t C, float *out, float *ws, void *stream);
+int vah_colsum_f16_partials(const void *g_f16, int64_t rows, int64_t C, float *ws, int64_t *nparts, void *stream);
+int vah_residual_layernorm_bwd_f16_bsum(const float *t, const void *gh_f16, const float *w, const float *mean,
+                                        const float *rstd, const float *gt, const void *z_f16, const float *gamma,
+                                        const float *sc, int64_t batch, int64_t rows_per_batch, int64_t C, float *dt,
+                                        void *dz_f16, float *dgamma, float *dw, float *db, float *ws, float *bpart,
+                                        int64_t *nparts, void *stream);
+int vah_scale_residual_bwd_f16_bsum(const float *g, const void *z_f16, const float *gamma, const float *s,
+                                    int64_t batch, int64_t rows_per_batch, int64_t C, void *dz_f16, float *dgamma,
+                                    float *ws, float *bpart, int64_t *nparts, void *stream);
+int vah_gelu_bwd_bsum_f16(const void *da_f16, const void *h_f16, int64_t rows, int64_t C, void *dh_f16,
+                          float *bpart, int64_t *nparts, void *stream);
 /* fp32, over `batch` row blocks of a strided tensor: out[c] = sum_{b, r < rows} g[b * batch_stride + r * C + c]
  * (the gradient of a per-channel vector added to a token range of a (B, T, C) tensor); C % 4 == 0. */
 int vah_colsum_f32(const float *g, int64_t batch, int64_t batch_stride, int64_t rows, int64_t C, float *out,
@@ -610,7 +626,7 @@ int vah_maxpool3s2_nhwc_fwd_f16(const void *x, int64_t N, int64_t H, int64_t W, 
 int vah_maxpool3s2_nhwc_bwd_f16(const void *gy, const void *idx, int64_t N, int64_t H, int64_t W, int64_t C, void *gx,
                                 void *stream);
 
-/* ---- bf16 GEMMs of the Linear layers (csrc/gemm.hip) ----------------------------------------
+/* ---- bf16 / fp16 GEMMs of the Linear layers (csrc/gemm.hip) ----------------------------------------
  * D (M x N, row-major, leading dimension ldd; bf16, or fp32 when d_is_f32) = op(A) op(B), bf16
  * operands, fp32 accumulation.  trans_a: A is stored (K x M) row-major and used transposed;
  * trans_b likewise (B stored (N x K)).  Replaces F.linear and its backward products
@@ -637,6 +653,18 @@ int vah_gemm_bf16_fin(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
                       const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, void *workspace,
                       int64_t workspace_bytes, const float *fin_part, int64_t fin_nparts, int64_t fin_C,
                       float *fin_out, void *stream);   /* + fin_out[c] = sum_p fin_part[p * fin_C + c] */
+/* fp16 operands (fp16 autocast): A, B, a 16-bit D and a 16-bit bias are _Float16, the rest as above.  An fp16 D is the
+ * plain cast of the fp32 accumulator (nearest even, overflow to +-inf, subnormals kept).  An fp16 bias goes with an fp16 D
+ * only (with an fp32 D: VAH_E_UNSUPPORTED - hipBLASLt misreads it; pass the bias in fp32).  The operand type is part of a
+ * problem's identity: the same shape in bf16 and fp16 is tuned and cached twice, and an fp16 problem's line of the table
+ * text is the bf16 line behind a leading "f16 " token. */
+int vah_gemm_f16(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+                 const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue,
+                 const void *bias, int bias_is_f32, void *workspace, int64_t workspace_bytes, void *stream);
+int vah_gemm_f16_fin(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+                     const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, void *workspace,
+                     int64_t workspace_bytes, const float *fin_part, int64_t fin_nparts, int64_t fin_C,
+                     float *fin_out, void *stream);
 int64_t vah_gemm_library_version(void);                /* hipBLASLt build the algorithm indices belong to */
 /* Tuning candidates dropped so far because the 64 x 64 corner of their result differed from the corner the heuristic's
  * first answer computes for the same operands (an algorithm that runs without an error status may still be wrong). */

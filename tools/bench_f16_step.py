@@ -1,17 +1,18 @@
 #!/usr/bin/env python
 """fp16-autocast training step of a ViT-Adapter preset (the reference's AMP mode: GradScaler(init_scale=512)), eager:
 forward + backward + unscale per step, HIP-event timed.  bench.py has no fp16 mode; this is the A/B tool for the fp16
-row kernels, the fp16 SpatialPriorModule kernels, the fp16 output tail and the fp16 deformable attention:
+row kernels, the fp16 SpatialPriorModule kernels, the fp16 output tail, the fp16 deformable attention and the fp16 Linears:
 
     python tools/bench_f16_step.py                                   # fused fp16 rows (default)
     VAH_FUSED_DISABLE=fp16_rows python tools/bench_f16_step.py       # torch's expressions: the behaviour before them
     VAH_FUSED_DISABLE=fp16_spm python tools/bench_f16_step.py        # the SpatialPriorModule as torch's NCHW module
     VAH_FUSED_DISABLE=fp16_tail python tools/bench_f16_step.py       # the output tail as torch's separate ops
     VAH_FUSED_DISABLE=fp16_msda python tools/bench_f16_step.py       # MSDA as the reference's op sequence on the fp32 kernels
+    VAH_FUSED_DISABLE=fp16_linear python tools/bench_f16_step.py     # the Linear layers as torch's fp16 library GEMMs
     python tools/bench_f16_step.py --autocast bfloat16               # the same step under bf16, for the rows side by side
 
 Prints ms per step (median and mean of the timed steps) and, from one more profiled step, the GPU time of every
-profiler row of the row-kernel, conv_, spm_, output-tail and msda_ families (none with the switches off: torch's kernels are not timed by this library).
+profiler row of the row-kernel, conv_, spm_, output-tail, msda_ and Linear (gemm_, gelu_bwd, colsum) families (none with the switches off: torch's kernels are not timed by this library).
 """
 import argparse
 import json
@@ -23,7 +24,7 @@ for p in (ROOT, os.path.join(ROOT, 'vit-adapter_amd')):
     sys.path.insert(0, p)
 import torch  # noqa: E402
 
-FAMILIES = 'layernorm,residual_layernorm,scale_residual,dwconv_tokens,conv_,spm_,bn_tail,transpose_tokens,pixel_shuffle2,maxpool,msda_'
+FAMILIES = 'layernorm,residual_layernorm,scale_residual,dwconv_tokens,conv_,spm_,bn_tail,transpose_tokens,pixel_shuffle2,maxpool,msda_,gemm_,gelu_bwd,colsum'
 
 
 def main():
@@ -71,7 +72,7 @@ def main():
     finite = all(bool(torch.isfinite(p.grad).all()) for p in model.parameters() if p.grad is not None)
     print(json.dumps({'preset': args.preset, 'size': args.size, 'batch': args.batch, 'autocast': args.autocast,
                       'fp16_rows': fused.ENABLED['fp16_rows'], 'fp16_spm': fused.ENABLED['fp16_spm'], 'fp16_tail': fused.ENABLED['fp16_tail'],
-                      'fp16_msda': fused.ENABLED['fp16_msda'],
+                      'fp16_msda': fused.ENABLED['fp16_msda'], 'fp16_linear': fused.ENABLED['fp16_linear'],
                       'ms_per_step_median': round(ms[len(ms) // 2], 3), 'ms_per_step_mean': round(sum(ms) / len(ms), 3),
                       'ms_min': round(ms[0], 3), 'ms_max': round(ms[-1], 3), 'steps': args.steps, 'grads_finite': finite,
                       'row_ms_one_step': rows, 'row_ms_total': round(sum(rows.values()), 3)}))

@@ -113,7 +113,7 @@ lib.vah_gemm_bf16.argtypes = [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, 
 lib.vah_gemm_bf16_fin.argtypes = [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _int, _p, _i64, _p, _i64, _i64,
                                   _p, _p]
 lib.vah_colsum_bf16_partials.argtypes = [_p, _i64, _i64, _p, ctypes.POINTER(_i64), _p]
-# the producers of a Linear's dY that carry its bias-gradient partials (bf16 only: no _f16 twins)
+# the producers of a Linear's dY that carry its bias-gradient partials (fp16 twins: LINEAR_F16_TWINS)
 lib.vah_residual_layernorm_bwd_bsum.argtypes = [_p] * 9 + [_i64] * 3 + [_p] * 6 + [_p, ctypes.POINTER(_i64), _p]
 lib.vah_scale_residual_bwd_bsum.argtypes = [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, ctypes.POINTER(_i64), _p]
 lib.vah_gelu_bwd_bsum_bf16.argtypes = [_p, _p, _i64, _i64, _p, _p, ctypes.POINTER(_i64), _p]
@@ -183,6 +183,18 @@ FUSED_F16_TWINS = {
 for _b16, _f16 in FUSED_F16_TWINS.items():
     getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
 
+# fp16 twins of the Linear path: the GEMM dispatcher (csrc/gemm.hip) and its satellites in csrc/fused_ops.hip - column
+# sums, GELU backward, and the `_bsum` forms of the two residual backward kernels (named after their `_f16` parents)
+LINEAR_F16_TWINS = {
+    'vah_gemm_bf16': 'vah_gemm_f16', 'vah_gemm_bf16_fin': 'vah_gemm_f16_fin',
+    'vah_colsum_bf16': 'vah_colsum_f16', 'vah_colsum_bf16_partials': 'vah_colsum_f16_partials',
+    'vah_gelu_bwd_bsum_bf16': 'vah_gelu_bwd_bsum_f16',
+    'vah_residual_layernorm_bwd_bsum': 'vah_residual_layernorm_bwd_f16_bsum',
+    'vah_scale_residual_bwd_bsum': 'vah_scale_residual_bwd_f16_bsum',
+}
+for _b16, _f16 in LINEAR_F16_TWINS.items():
+    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
+
 # fp16 twins of the SpatialPriorModule kernels (csrc/conv.hip, csrc/spm_nhwc.hip); the workspace queries and
 # vah_bn_finalize_stats are shared
 SPM_F16_TWINS = {
@@ -232,6 +244,8 @@ EXPORTS = (
     'vah_dwconv3x3_tokens_f16', 'vah_dwconv3x3_tokens_wgrad_f16',
     'vah_residual_layernorm_bwd_bsum', 'vah_scale_residual_bwd_bsum', 'vah_gelu_bwd_bsum_bf16',
     'vah_gemm_set_tuning', 'vah_gemm_bf16', 'vah_gemm_bf16_fin', 'vah_colsum_bf16_partials', 'vah_gemm_table_dump', 'vah_gemm_table_load', 'vah_gemm_library_version', 'vah_gemm_rejected_candidates',
+    'vah_gemm_f16', 'vah_gemm_f16_fin', 'vah_colsum_f16', 'vah_colsum_f16_partials', 'vah_gelu_bwd_bsum_f16',
+    'vah_residual_layernorm_bwd_f16_bsum', 'vah_scale_residual_bwd_f16_bsum',
     'vah_bn_tail_ws_floats', 'vah_bn_tail_supported', 'vah_bn_tail_stats', 'vah_bn_tail_apply', 'vah_bn_tail_bwd_stats', 'vah_bn_tail_bwd_apply',
     'vah_bn_finalize_stats', 'vah_transpose_tokens', 'vah_maxpool3s2_fwd_bf16', 'vah_maxpool3s2_bwd_bf16',
     'vah_image_to_nhwc16_bf16', 'vah_bn_nhwc_ws_floats', 'vah_bn_nhwc_stats', 'vah_bn_nhwc_apply', 'vah_bn_nhwc_bwd_stats',
@@ -312,7 +326,7 @@ GEMM_EPI_NONE, GEMM_EPI_BIAS = 0, 1
 
 def gemm_table_dump():
     """The GEMM algorithm cache as text: a '#hipblaslt <version>' line, then one problem per line
-    (see include/vitadapter_hip.h)."""
+    (see include/vitadapter_hip.h; the line of an fp16 problem starts with 'f16 ')."""
     n = lib.vah_gemm_table_dump(None, 0)
     buf = ctypes.create_string_buffer(int(n))
     lib.vah_gemm_table_dump(buf, n)

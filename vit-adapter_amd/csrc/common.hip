@@ -44,7 +44,7 @@ struct Rec {
 
 static std::mutex g_mu;
 static bool g_on = false;
-static char g_prefix[128] = "";                 // only scopes whose name starts with one of these are timed
+static char g_prefix[512] = "";                 // only scopes whose name starts with one of these are timed
 static std::vector<Rec> g_recs;                 // live records of the current collection
 static std::vector<hipEvent_t> g_pool;          // recycled events
 

@@ -22,6 +22,7 @@
 // torch's .to(float16) does): loss-scaled gradients live in fp16's subnormal range and an overflow has to
 // reach GradScaler as inf, so no cvt_pkrtz, no saturation, no flushed denormals.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -31,17 +32,31 @@ namespace {
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
 typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
+typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8;
 
 // vector of 4 elements of the kernels' 16-bit type T
 template <typename T> struct Vec16;
-template <> struct Vec16<__bf16> { typedef bf16x4 x4; };
-template <> struct Vec16<_Float16> { typedef f16x4 x4; };
+template <> struct Vec16<__bf16> { typedef bf16x4 x4; typedef bf16x8 x8; };
+template <> struct Vec16<_Float16> { typedef f16x4 x4; typedef f16x8 x8; };
 template <typename T> using vec4 = typename Vec16<T>::x4;
+template <typename T> using vec8 = typename Vec16<T>::x8;
 
 // profiler row of the instantiation: the bf16 name or its _f16 twin
 template <typename T> constexpr const char *tname(const char *bf16_name, const char *f16_name);
 template <> constexpr const char *tname<__bf16>(const char *bf16_name, const char *) { return bf16_name; }
 template <> constexpr const char *tname<_Float16>(const char *, const char *f16_name) { return f16_name; }
+
+// fp32 -> T where a kernel both stores the rounded value and sums it (the bias partials), or has to agree bit for bit
+// with another kernel's store: every dz / dh store of the residual, residual + LayerNorm and GELU backward kernels.  For _Float16 the fp32 value is made opaque first: with -ffp-contract=fast the compiler
+// otherwise folds the multiply that produced it into v_fma_mixlo_f16 (one rounding, from the exact product) for one use
+// and keeps v_mul_f32 + v_cvt_pk_f16_f32 (fp32 product, then fp16: two roundings) for another, and the two differ by an
+// fp16 ulp about once in 10^4 elements - the sum then is not the sum of what was stored.  What is kept is the second
+// form: the fp32 value rounded once to fp16, which is also what torch's kernels do.  (bf16 has no such instruction.)
+template <typename T>
+__device__ __forceinline__ T round16(float v) {
+    if constexpr (std::is_same<T, _Float16>::value) asm("" : "+v"(v));
+    return (T)v;
+}
 
 constexpr int kMaxVecAll = 8;    // float4 groups per lane: C <= 64 * 4 * 8 = 2048 (template NV <= 8)
 
@@ -294,10 +309,10 @@ __global__ __launch_bounds__(64 * kWaves) void ln_bwd_kernel(const float *__rest
                     if constexpr (kRes) {                 // t = x + sc * gamma * z in front: dz, dgamma from dt = d
                         const float4 gm = *reinterpret_cast<const float4 *>(s_gm + 4 * i);
                         vec4<T> o;
-                        o[0] = (T)(sb[u] * gm.x * d.x);
-                        o[1] = (T)(sb[u] * gm.y * d.y);
-                        o[2] = (T)(sb[u] * gm.z * d.z);
-                        o[3] = (T)(sb[u] * gm.w * d.w);
+                        o[0] = round16<T>(sb[u] * gm.x * d.x);
+                        o[1] = round16<T>(sb[u] * gm.y * d.y);
+                        o[2] = round16<T>(sb[u] * gm.z * d.z);
+                        o[3] = round16<T>(sb[u] * gm.w * d.w);
                         *reinterpret_cast<vec4<T> *>(dz + rws[u] * C + 4 * i) = o;
                         float4 *pg = reinterpret_cast<float4 *>(acc + 2 * C + 4 * i);
                         float4 ag = *pg;
@@ -490,10 +505,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kMaxVec <= 
 }
 
 // ---------------------------------------------------------------------------------------
-// Column sums of a bf16 [rows, C] matrix (bias gradient of a Linear).  Workgroup = 32 column lanes
-// (8 bf16 = 16 bytes each: 256 columns) x 8 row lanes over a strip of rows; one partial row each.
+// Column sums of a 16-bit (T: bf16 or fp16) [rows, C] matrix (bias gradient of a Linear).  Workgroup = 32 column lanes
+// (8 elements = 16 bytes each: 256 columns) x 8 row lanes over a strip of rows; one partial row each.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void colsum_bf16_kernel(const __bf16 *__restrict__ g, int64_t rows,
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_bf16_kernel(const T *__restrict__ g, int64_t rows,
                                                           int C, int rows_per_block,
                                                           float *__restrict__ part) {
     __shared__ float s_acc[8][256 + 8];
@@ -505,16 +521,16 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const __bf16 *__restri
     if (c0 < C) {
         int64_t r = r0 + rl;
         for (; r + 24 < r1; r += 32) {           // 4 independent 16-byte loads in flight
-            bf16x8 v[4];
+            vec8<T> v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const bf16x8 *>(g + (r + 8 * u) * C + c0);
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const vec8<T> *>(g + (r + 8 * u) * C + c0);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[e] += (float)v[u][e];
         }
         for (; r < r1; r += 8) {
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(g + r * C + c0);
+            const vec8<T> v = *reinterpret_cast<const vec8<T> *>(g + r * C + c0);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
         }
@@ -645,10 +661,10 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_kernel(
                 if (!ok[u]) continue;
                 const int64_t off = (r + 4 * u) * C + 4 * cv;
                 vec4<T> o;
-                o[0] = (T)(sb[u] * gm.x * gv[u].x);
-                o[1] = (T)(sb[u] * gm.y * gv[u].y);
-                o[2] = (T)(sb[u] * gm.z * gv[u].z);
-                o[3] = (T)(sb[u] * gm.w * gv[u].w);
+                o[0] = round16<T>(sb[u] * gm.x * gv[u].x);
+                o[1] = round16<T>(sb[u] * gm.y * gv[u].y);
+                o[2] = round16<T>(sb[u] * gm.z * gv[u].z);
+                o[3] = round16<T>(sb[u] * gm.w * gv[u].w);
                 *reinterpret_cast<vec4<T> *>(dz + off) = o;
                 if constexpr (kDg) {
                     acc.x += sb[u] * gv[u].x * (float)zv[u][0];
@@ -705,10 +721,10 @@ __global__ __launch_bounds__(256) void scale_only_bwd_kernel(const float *__rest
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < vec_per_batch; i += (int64_t)gridDim.x * 256) {
         const float4 v = *reinterpret_cast<const float4 *>(g + 4 * (base + i));
         vec4<T> o;
-        o[0] = (T)(sb * v.x);
-        o[1] = (T)(sb * v.y);
-        o[2] = (T)(sb * v.z);
-        o[3] = (T)(sb * v.w);
+        o[0] = round16<T>(sb * v.x);
+        o[1] = round16<T>(sb * v.y);
+        o[2] = round16<T>(sb * v.z);
+        o[3] = round16<T>(sb * v.w);
         *reinterpret_cast<vec4<T> *>(dz + 4 * (base + i)) = o;
     }
 }
@@ -1101,9 +1117,10 @@ int scale_residual_bwd(const char *fn, const float *g, const void *z, const floa
 // tiling of colsum_bf16_kernel instead: 32 column lanes x 8 columns x 8 row lanes over a strip of rows, 4 rows
 // (8 x 16 bytes of g per thread) requested before the first is used, one partial row per workgroup.
 // rows_per_block % 32 == 0, so only the last strip has dead slots (clamped loads, results unused).
+template <typename T>
 __global__ __launch_bounds__(256) void scale_bsum_bwd_kernel(const float *__restrict__ g, const float *__restrict__ s,
                                                              unsigned rows, unsigned rows_per_batch, int C,
-                                                             int rows_per_block, __bf16 *__restrict__ dz,
+                                                             int rows_per_block, T *__restrict__ dz,
                                                              float *__restrict__ bpart) {
     __shared__ float s_acc[8][256 + 8];
     const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
@@ -1126,16 +1143,16 @@ __global__ __launch_bounds__(256) void scale_bsum_bwd_kernel(const float *__rest
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (r + 8 * u >= r1) break;
-                bf16x8 o;
-                o[0] = (__bf16)(sb[u] * lo[u].x);
-                o[1] = (__bf16)(sb[u] * lo[u].y);
-                o[2] = (__bf16)(sb[u] * lo[u].z);
-                o[3] = (__bf16)(sb[u] * lo[u].w);
-                o[4] = (__bf16)(sb[u] * hi[u].x);
-                o[5] = (__bf16)(sb[u] * hi[u].y);
-                o[6] = (__bf16)(sb[u] * hi[u].z);
-                o[7] = (__bf16)(sb[u] * hi[u].w);
-                *reinterpret_cast<bf16x8 *>(dz + (int64_t)(r + 8 * u) * C + c0) = o;
+                vec8<T> o;
+                o[0] = round16<T>(sb[u] * lo[u].x);
+                o[1] = round16<T>(sb[u] * lo[u].y);
+                o[2] = round16<T>(sb[u] * lo[u].z);
+                o[3] = round16<T>(sb[u] * lo[u].w);
+                o[4] = round16<T>(sb[u] * hi[u].x);
+                o[5] = round16<T>(sb[u] * hi[u].y);
+                o[6] = round16<T>(sb[u] * hi[u].z);
+                o[7] = round16<T>(sb[u] * hi[u].w);
+                *reinterpret_cast<vec8<T> *>(dz + (int64_t)(r + 8 * u) * C + c0) = o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[e] += (float)o[e];
             }
@@ -1162,10 +1179,10 @@ inline void strips_of_32(int64_t rows, int64_t *rpb, int64_t *parts) {
 // scale_residual_bwd plus the partial rows of the column sums of dz (*nparts = the launch's workgroups along the
 // rows): with a gamma the row-strip kernel with a second accumulator, without one the column-tiled kernel above
 // (the strip kernel where that one does not apply: C % 8 != 0 or 2^31 rows).  bpart: vah_reduce_ws_floats(C).
-inline int scale_residual_bwd_bsum(const char *fn, const float *g, const void *z, const float *gamma, const float *s,
+template <typename T>
+int scale_residual_bwd_bsum(const char *fn, const float *g, const void *z, const float *gamma, const float *s,
                                    int64_t batch, int64_t rows_per_batch, int64_t C, void *dz, float *dgamma, float *ws,
                                    float *bpart, int64_t *nparts, void *stream) {
-    typedef __bf16 T;
     clear_error();
     if (batch < 0 || rows_per_batch < 0 || C < 4 || C % 4) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (!bpart || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
@@ -1179,12 +1196,12 @@ inline int scale_residual_bwd_bsum(const char *fn, const float *g, const void *z
     if (!g || !z || !dz || (dgamma && !ws)) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (((uintptr_t)g | (uintptr_t)gamma | (uintptr_t)bpart) % 16 || ((uintptr_t)z | (uintptr_t)dz) % 8)
         return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    LaunchScope scope("scale_residual_bwd", rows * C * 8, st);
+    LaunchScope scope(tname<T>("scale_residual_bwd", "scale_residual_bwd_f16"), rows * C * 8, st);
     const bool dg = gamma && dgamma;
     if (!gamma && C % 8 == 0 && rows < ((int64_t)1 << 31)) {
         int64_t srows, parts;
         strips_of_32(rows, &srows, &parts);
-        hipLaunchKernelGGL(scale_bsum_bwd_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)parts), dim3(256), 0, st, g, s,
+        hipLaunchKernelGGL(scale_bsum_bwd_kernel<T>, dim3((unsigned)((C + 255) / 256), (unsigned)parts), dim3(256), 0, st, g, s,
                            (unsigned)rows, (unsigned)std::max<int64_t>(rows_per_batch, 1), (int)C, (int)srows, (T *)dz, bpart);
         *nparts = parts;
         return check_launch(fn);
@@ -1205,15 +1222,16 @@ inline int scale_residual_bwd_bsum(const char *fn, const float *g, const void *z
 }
 
 // ---------------------------------------------------------------------------------------
-// GELU backward (exact, erf) of a bf16 [rows, C] matrix with the column sums of its result: the gradient of
-// trunk mlp.fc1's output.  dh = bf16(da * (Phi(h) + h * phi(h))), fp32 math from the bf16 operands in the
+// GELU backward (exact, erf) of a 16-bit (T: bf16 or fp16) [rows, C] matrix with the column sums of its result: the gradient of
+// trunk mlp.fc1's output.  dh = T(da * (Phi(h) + h * phi(h))), fp32 math from the 16-bit operands in the
 // operation order of torch's GeluBackward kernel (so the two agree to the bit wherever erff / expf do).
 // The tiling of colsum_bf16_kernel: 32 column lanes x 8 bf16 x 8 row lanes over a strip of rows; the loads of
 // 4 rows are requested before the math of the first.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gelu_bwd_bsum_kernel(const __bf16 *__restrict__ da, const __bf16 *__restrict__ h,
+template <typename T>
+__global__ __launch_bounds__(256) void gelu_bwd_bsum_kernel(const T *__restrict__ da, const T *__restrict__ h,
                                                             int64_t rows, int C, int rows_per_block,
-                                                            __bf16 *__restrict__ dh, float *__restrict__ part) {
+                                                            T *__restrict__ dh, float *__restrict__ part) {
     __shared__ float s_acc[8][256 + 8];
     const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
     const int c0 = blockIdx.x * 256 + cl * 8;
@@ -1224,26 +1242,26 @@ __global__ __launch_bounds__(256) void gelu_bwd_bsum_kernel(const __bf16 *__rest
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (c0 < C) {
         for (int64_t r = r0 + rl; r < r1; r += 32) {
-            bf16x8 av[4], hv[4];
+            vec8<T> av[4], hv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int64_t rr = min(r + 8 * u, r1 - 1);          // clamped: a dead slot re-reads a live row
-                av[u] = *reinterpret_cast<const bf16x8 *>(da + rr * C + c0);
-                hv[u] = *reinterpret_cast<const bf16x8 *>(h + rr * C + c0);
+                av[u] = *reinterpret_cast<const vec8<T> *>(da + rr * C + c0);
+                hv[u] = *reinterpret_cast<const vec8<T> *>(h + rr * C + c0);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (r + 8 * u >= r1) break;
-                bf16x8 o;
+                vec8<T> o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float x = (float)hv[u][e];
                     const float cdf = 0.5f * (1.f + erff(x * kAlpha));
                     const float pdf = expf(-0.5f * x * x) * kBeta;
-                    o[e] = (__bf16)((float)av[u][e] * (cdf + x * pdf));
+                    o[e] = round16<T>((float)av[u][e] * (cdf + x * pdf));
                     acc[e] += (float)o[e];
                 }
-                *reinterpret_cast<bf16x8 *>(dh + (r + 8 * u) * C + c0) = o;
+                *reinterpret_cast<vec8<T> *>(dh + (r + 8 * u) * C + c0) = o;
             }
         }
     }
@@ -1257,6 +1275,70 @@ __global__ __launch_bounds__(256) void gelu_bwd_bsum_kernel(const __bf16 *__rest
         for (int u = 0; u < 8; ++u) t += s_acc[u][threadIdx.x];
         part[(int64_t)blockIdx.y * C + c] = t;
     }
+}
+
+template <typename T>
+int gelu_bwd_bsum(const char *fn, const void *da, const void *h, int64_t rows, int64_t C, void *dh, float *bpart,
+                  int64_t *nparts, void *stream) {
+    clear_error();
+    if (rows < 0 || C < 8 || C % 8 || C > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (!bpart || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (rows == 0) {
+        *nparts = 0;
+        return VAH_OK;
+    }
+    if (!da || !h || !dh) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if (((uintptr_t)da | (uintptr_t)h | (uintptr_t)dh) % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    const int ctiles = (int)((C + 255) / 256);
+    // colsum_bf16's tiling, not its strip rule: that one sizes strips to 2048 workgroups whatever the row count
+    // (8192 x 3072: 49 rows, 6.1 per row lane = a second, ragged batch of loads), which costs a kernel with this
+    // much math per element a quarter of its rate; strips of 32 rows are whole batches
+    int64_t parts, rpb;
+    strips_of_32(rows, &rpb, &parts);
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("gelu_bwd", "gelu_bwd_f16"), rows * C * 6, st);
+    hipLaunchKernelGGL(gelu_bwd_bsum_kernel<T>, dim3((unsigned)ctiles, (unsigned)parts), dim3(256), 0, st, (const T *)da,
+                       (const T *)h, rows, (int)C, (int)rpb, (T *)dh, bpart);
+    *nparts = parts;
+    return check_launch(fn);
+}
+
+template <typename T>
+int colsum16_partials(const char *fn, const void *g, int64_t rows, int64_t C, float *ws, int64_t *nparts, void *stream) {
+    clear_error();
+    if (rows < 1 || C < 8 || C % 8 || C > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
+    if (!g || !ws || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    if ((uintptr_t)g % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    const int ctiles = (int)((C + 255) / 256);
+    // enough strips to fill the chip, at least 32 rows each, at most kMaxParts partial rows
+    int64_t parts = std::min<int64_t>(kMaxParts, std::max<int64_t>(1, 2048 / ctiles));
+    int64_t rpb = std::max<int64_t>(32, (rows + parts - 1) / parts);
+    parts = (rows + rpb - 1) / rpb;
+    hipStream_t st = (hipStream_t)stream;
+    LaunchScope scope(tname<T>("colsum_bf16", "colsum_f16"), rows * C * 2, st);
+    hipLaunchKernelGGL(colsum_bf16_kernel<T>, dim3((unsigned)ctiles, (unsigned)parts), dim3(256), 0, st, (const T *)g, rows,
+                       (int)C, (int)rpb, ws);
+    *nparts = parts;
+    return check_launch(fn);
+}
+
+// fn_partials: the name the partials entry point reports its own refusals under
+template <typename T>
+int colsum16(const char *fn, const char *fn_partials, const void *g, int64_t rows, int64_t C, float *out, float *ws,
+             void *stream) {
+    clear_error();
+    if (rows < 0 || C < 8 || C % 8 || C > (1 << 20)) return fail(VAH_E_SHAPE, "%s: C=%lld unsupported", fn, (long long)C);
+    if (!out || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    hipStream_t st = (hipStream_t)stream;
+    if (rows == 0) {
+        (void)hipMemsetAsync(out, 0, C * 4, st);
+        return VAH_OK;
+    }
+    int64_t parts = 0;
+    if (int rc = colsum16_partials<T>(fn_partials, g, rows, C, ws, &parts, stream)) return rc;
+    hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, ws, (int)parts,
+                       (int)C, out, (int)C, (float *)nullptr, 1 << 30, (float *)nullptr);
+    return check_launch(fn);
 }
 
 // token ranges and sizes of the (2H,2W), (H,W), (H/2,W/2) maps of a (B, 21n, C) token tensor
@@ -1420,95 +1502,53 @@ VAH_ENTRY_PAIR(VAH_DWCONV_ENTRY, vah_dwconv3x3_tokens_bf16, vah_dwconv3x3_tokens
     }
 VAH_ENTRY_PAIR(VAH_DWCONV_WGRAD_ENTRY, vah_dwconv3x3_tokens_wgrad_bf16, vah_dwconv3x3_tokens_wgrad_f16)
 
-#undef VAH_ENTRY_PAIR
-
 // The row-streaming backward kernels that write the dY of a Linear, carrying the partial rows of dY's column sums
 // (that Linear's bias gradient) in the same pass: bpart (caller-owned, vah_reduce_ws_floats(C) floats) gets *nparts
-// <= 512 rows of C floats, for the finalize job of vah_gemm_bf16_fin.  Summed is every dY element after its rounding
-// to bf16 - the term vah_colsum_bf16_partials adds.  Every other output is that of the entry point without _bsum.
-int vah_residual_layernorm_bwd_bsum(const float *t, const void *gh, const float *w, const float *mean, const float *rstd,
-                                    const float *gt, const void *z, const float *gamma, const float *sc, int64_t batch,
-                                    int64_t rows_per_batch, int64_t C, float *dt, void *dz, float *dgamma, float *dw,
-                                    float *db, float *ws, float *bpart, int64_t *nparts, void *stream) {
-    return vah::residual_ln_bwd<__bf16, true>("vah_residual_layernorm_bwd_bsum", t, gh, w, mean, rstd, gt, z, gamma, sc,
-                                              batch, rows_per_batch, C, dt, dz, dgamma, dw, db, ws, stream, bpart, nparts);
-}
-
-int vah_scale_residual_bwd_bsum(const float *g, const void *z, const float *gamma, const float *s, int64_t batch,
-                                int64_t rows_per_batch, int64_t C, void *dz, float *dgamma, float *ws, float *bpart,
-                                int64_t *nparts, void *stream) {
-    return vah::scale_residual_bwd_bsum("vah_scale_residual_bwd_bsum", g, z, gamma, s, batch, rows_per_batch, C, dz,
-                                        dgamma, ws, bpart, nparts, stream);
-}
-
-int vah_gelu_bwd_bsum_bf16(const void *da, const void *h, int64_t rows, int64_t C, void *dh, float *bpart,
-                           int64_t *nparts, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_gelu_bwd_bsum_bf16";
-    if (rows < 0 || C < 8 || C % 8 || C > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (!bpart || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (rows == 0) {
-        *nparts = 0;
-        return VAH_OK;
+// <= 512 rows of C floats, for the finalize job of vah_gemm_bf16_fin / vah_gemm_f16_fin.  Summed is every dY element
+// after its rounding to the 16-bit type - the term vah_colsum_bf16_partials / _f16_partials adds.  Every other output is
+// that of the entry point without _bsum.
+#define VAH_RES_LN_BWD_BSUM_ENTRY(NAME, T)                                                                              \
+    int NAME(const float *t, const void *gh, const float *w, const float *mean, const float *rstd, const float *gt,     \
+             const void *z, const float *gamma, const float *sc, int64_t batch, int64_t rows_per_batch, int64_t C,      \
+             float *dt, void *dz, float *dgamma, float *dw, float *db, float *ws, float *bpart, int64_t *nparts,        \
+             void *stream) {                                                                                            \
+        return vah::residual_ln_bwd<T, true>(#NAME, t, gh, w, mean, rstd, gt, z, gamma, sc, batch, rows_per_batch, C,   \
+                                             dt, dz, dgamma, dw, db, ws, stream, bpart, nparts);                        \
     }
-    if (!da || !h || !dh) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if (((uintptr_t)da | (uintptr_t)h | (uintptr_t)dh) % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    const int ctiles = (int)((C + 255) / 256);
-    // colsum_bf16's tiling, not its strip rule: that one sizes strips to 2048 workgroups whatever the row count
-    // (8192 x 3072: 49 rows, 6.1 per row lane = a second, ragged batch of loads), which costs a kernel with this
-    // much math per element a quarter of its rate; strips of 32 rows are whole batches
-    int64_t parts, rpb;
-    strips_of_32(rows, &rpb, &parts);
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("gelu_bwd", rows * C * 6, st);
-    hipLaunchKernelGGL(gelu_bwd_bsum_kernel, dim3((unsigned)ctiles, (unsigned)parts), dim3(256), 0, st, (const __bf16 *)da,
-                       (const __bf16 *)h, rows, (int)C, (int)rpb, (__bf16 *)dh, bpart);
-    *nparts = parts;
-    return check_launch(fn);
-}
+VAH_ENTRY_PAIR(VAH_RES_LN_BWD_BSUM_ENTRY, vah_residual_layernorm_bwd_bsum, vah_residual_layernorm_bwd_f16_bsum)
 
-// Partial rows of the column sums of a bf16 [rows, C] matrix, C % 8 == 0: ws (vah_reduce_ws_floats(C)) gets
-// *nparts rows of C floats; whoever sums them (vah_colsum_bf16 below, or the finalize job of
-// vah_gemm_bf16_fin) has the column sums.  rows >= 1.
-int vah_colsum_bf16_partials(const void *g, int64_t rows, int64_t C, float *ws, int64_t *nparts, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_colsum_bf16_partials";
-    if (rows < 1 || C < 8 || C % 8 || C > (1 << 20)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (!g || !ws || !nparts) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    if ((uintptr_t)g % 16) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
-    const int ctiles = (int)((C + 255) / 256);
-    // enough strips to fill the chip, at least 32 rows each, at most kMaxParts partial rows
-    int64_t parts = std::min<int64_t>(kMaxParts, std::max<int64_t>(1, 2048 / ctiles));
-    int64_t rpb = std::max<int64_t>(32, (rows + parts - 1) / parts);
-    parts = (rows + rpb - 1) / rpb;
-    hipStream_t st = (hipStream_t)stream;
-    LaunchScope scope("colsum_bf16", rows * C * 2, st);
-    hipLaunchKernelGGL(colsum_bf16_kernel, dim3((unsigned)ctiles, (unsigned)parts), dim3(256), 0, st,
-                       (const __bf16 *)g, rows, (int)C, (int)rpb, ws);
-    *nparts = parts;
-    return check_launch(fn);
-}
-
-// out[c] = sum_r g[r][c] for a bf16 [rows, C] matrix, C % 8 == 0; ws: vah_reduce_ws_floats(C).
-int vah_colsum_bf16(const void *g, int64_t rows, int64_t C, float *out, float *ws, void *stream) {
-    using namespace vah;
-    clear_error();
-    const char *fn = "vah_colsum_bf16";
-    if (rows < 0 || C < 8 || C % 8 || C > (1 << 20)) return fail(VAH_E_SHAPE, "%s: C=%lld unsupported", fn, (long long)C);
-    if (!out || !ws) return fail(VAH_E_NULL, "%s: null pointer", fn);
-    hipStream_t st = (hipStream_t)stream;
-    if (rows == 0) {
-        (void)hipMemsetAsync(out, 0, C * 4, st);
-        return VAH_OK;
+#define VAH_SCALE_RES_BWD_BSUM_ENTRY(NAME, T)                                                                           \
+    int NAME(const float *g, const void *z, const float *gamma, const float *s, int64_t batch, int64_t rows_per_batch,  \
+             int64_t C, void *dz, float *dgamma, float *ws, float *bpart, int64_t *nparts, void *stream) {              \
+        return vah::scale_residual_bwd_bsum<T>(#NAME, g, z, gamma, s, batch, rows_per_batch, C, dz, dgamma, ws, bpart,  \
+                                               nparts, stream);                                                         \
     }
-    int64_t parts = 0;
-    if (int rc = vah_colsum_bf16_partials(g, rows, C, ws, &parts, stream)) return rc;
-    hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, ws, (int)parts,
-                       (int)C, out, (int)C, (float *)nullptr, 1 << 30, (float *)nullptr);
-    return check_launch(fn);
-}
+VAH_ENTRY_PAIR(VAH_SCALE_RES_BWD_BSUM_ENTRY, vah_scale_residual_bwd_bsum, vah_scale_residual_bwd_f16_bsum)
+
+#define VAH_GELU_BWD_BSUM_ENTRY(NAME, T)                                                                                \
+    int NAME(const void *da, const void *h, int64_t rows, int64_t C, void *dh, float *bpart, int64_t *nparts,           \
+             void *stream) {                                                                                            \
+        return vah::gelu_bwd_bsum<T>(#NAME, da, h, rows, C, dh, bpart, nparts, stream);                                 \
+    }
+VAH_ENTRY_PAIR(VAH_GELU_BWD_BSUM_ENTRY, vah_gelu_bwd_bsum_bf16, vah_gelu_bwd_bsum_f16)
+
+// Partial rows of the column sums of a 16-bit [rows, C] matrix, C % 8 == 0: ws (vah_reduce_ws_floats(C)) gets
+// *nparts rows of C floats; whoever sums them (vah_colsum_bf16 / _f16 below, or the finalize job of
+// vah_gemm_bf16_fin / vah_gemm_f16_fin) has the column sums.  rows >= 1.
+#define VAH_COLSUM_PARTIALS_ENTRY(NAME, T)                                                                              \
+    int NAME(const void *g, int64_t rows, int64_t C, float *ws, int64_t *nparts, void *stream) {                        \
+        return vah::colsum16_partials<T>(#NAME, g, rows, C, ws, nparts, stream);                                        \
+    }
+VAH_ENTRY_PAIR(VAH_COLSUM_PARTIALS_ENTRY, vah_colsum_bf16_partials, vah_colsum_f16_partials)
+
+// out[c] = sum_r g[r][c] for a 16-bit [rows, C] matrix, C % 8 == 0; ws: vah_reduce_ws_floats(C).
+#define VAH_COLSUM_ENTRY(NAME, T)                                                                                       \
+    int NAME(const void *g, int64_t rows, int64_t C, float *out, float *ws, void *stream) {                             \
+        return vah::colsum16<T>(#NAME, #NAME "_partials", g, rows, C, out, ws, stream);                                 \
+    }
+VAH_ENTRY_PAIR(VAH_COLSUM_ENTRY, vah_colsum_bf16, vah_colsum_f16)
+
+#undef VAH_ENTRY_PAIR
 
 // out[c] = sum over b < batch, r < rows of g[b * batch_stride + r * C + c]  (fp32, C % 4 == 0): column sums
 // of a token range of a (B, T, C) tensor - the gradient of a per-channel vector added to that range.

@@ -1,4 +1,4 @@
-// bf16 GEMMs of the Linear layers (reference: every nn.Linear of base/vit.py, adapter_modules.py and
+// bf16 and fp16 GEMMs of the Linear layers (reference: every nn.Linear of base/vit.py, adapter_modules.py and
 // ops/modules/ms_deform_attn.py, i.e. F.linear and its two backward products).
 //
 // The tiles come from hipBLASLt (plain library GEMMs are the one place a library is the right
@@ -14,6 +14,9 @@
 //     768 x 768: 18..72 output tiles for 256 CUs.  hipBLASLt runs them at 0.2 PFLOP/s; the same
 //     library run as a strided batch over S slices of the rows (S x more tiles) plus one reduction
 //     pass over the S fp32 partial products is 2-3x faster.  S is part of the timed choice.
+// The 16-bit operand type (bf16 autocast, or fp16 autocast: the vah_gemm_f16 entry points) is part of a problem's key:
+// the same shape in the two types is two entries with their own algorithms.  An fp16 result is the plain cast of the
+// fp32 accumulator: nearest even, overflow to +-inf (GradScaler has to see it), subnormals kept.
 // Row-major in, row-major out; hipBLASLt is column-major, so D^T = op(B)^T op(A)^T is what is run.
 #include <hip/hip_runtime.h>
 #include <hipblaslt/hipblaslt-ext.hpp>
@@ -29,6 +32,7 @@
 #include <sstream>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vitadapter_hip.h"
@@ -38,12 +42,14 @@ namespace vah {
 namespace {
 
 struct Key {
+    int f16;                 // 16-bit type of A, B, a 16-bit D and a 16-bit bias: 0 bf16, 1 fp16
     int ta, tb, d32, epi, bias32;
     int64_t M, N, K, lda, ldb, ldd;
     bool operator<(const Key &o) const {
-        return std::tie(ta, tb, d32, epi, bias32, M, N, K, lda, ldb, ldd) <
-               std::tie(o.ta, o.tb, o.d32, o.epi, o.bias32, o.M, o.N, o.K, o.lda, o.ldb, o.ldd);
+        return std::tie(f16, ta, tb, d32, epi, bias32, M, N, K, lda, ldb, ldd) <
+               std::tie(o.f16, o.ta, o.tb, o.d32, o.epi, o.bias32, o.M, o.N, o.K, o.lda, o.ldb, o.ldd);
     }
+    hipDataType t16() const { return f16 ? HIP_R_16F : HIP_R_16BF; }
 };
 
 struct Choice {
@@ -130,12 +136,12 @@ hipblasStatus_t make_problem(const Call &c, Problem &p, int split) {
     hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_TRANSA, &op1, sizeof(op1));
     hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_TRANSB, &op2, sizeof(op2));
     // our B row-major: (K x N) [tb = 0] or (N x K) [tb = 1]; as column-major (N x K) resp. (K x N)
-    s = hipblasLtMatrixLayoutCreate(&p.la, HIP_R_16BF, k.tb ? k.K : k.N, k.tb ? k.N : k.K, k.ldb);
+    s = hipblasLtMatrixLayoutCreate(&p.la, k.t16(), k.tb ? k.K : k.N, k.tb ? k.N : k.K, k.ldb);
     if (s != HIPBLAS_STATUS_SUCCESS) return s;
     // our A row-major: (M x K) [ta = 0] or (K x M) [ta = 1]; as column-major (K x M) resp. (M x K)
-    s = hipblasLtMatrixLayoutCreate(&p.lb, HIP_R_16BF, k.ta ? k.M : k.K, k.ta ? k.K : k.M, k.lda);
+    s = hipblasLtMatrixLayoutCreate(&p.lb, k.t16(), k.ta ? k.M : k.K, k.ta ? k.K : k.M, k.lda);
     if (s != HIPBLAS_STATUS_SUCCESS) return s;
-    s = hipblasLtMatrixLayoutCreate(&p.ld, k.d32 ? HIP_R_32F : HIP_R_16BF, k.N, k.M, k.ldd);
+    s = hipblasLtMatrixLayoutCreate(&p.ld, k.d32 ? HIP_R_32F : k.t16(), k.N, k.M, k.ldd);
     if (s != HIPBLAS_STATUS_SUCCESS) return s;
     if (split > 1) {
         const int32_t batch = split;
@@ -157,7 +163,7 @@ hipblasStatus_t make_problem(const Call &c, Problem &p, int split) {
     hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_EPILOGUE, &epi, sizeof(epi));
     if (c.bias) {
         hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &c.bias, sizeof(c.bias));
-        const int32_t bt = k.bias32 ? HIP_R_32F : HIP_R_16BF;
+        const int32_t bt = k.bias32 ? HIP_R_32F : k.t16();
         hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_DATA_TYPE, &bt, sizeof(bt));
     }
     return HIPBLAS_STATUS_SUCCESS;
@@ -220,8 +226,9 @@ __global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ p
 // holds another product's data - and whose first 64 columns are right).  So the candidate runs twice on an output
 // filled with NaN patterns, first over a workspace filled with 0x01 bytes, then over whatever it left there, and every element
 // of both results has to agree with the reference.
-__global__ __launch_bounds__(256) void ref_gemm(int ta, int tb, int M, int N, int K, const __bf16 *__restrict__ A, int64_t lda,
-                                                const __bf16 *__restrict__ B, int64_t ldb, const void *__restrict__ bias,
+template <typename T>
+__global__ __launch_bounds__(256) void ref_gemm(int ta, int tb, int M, int N, int K, const T *__restrict__ A, int64_t lda,
+                                                const T *__restrict__ B, int64_t ldb, const void *__restrict__ bias,
                                                 int bias32, float *__restrict__ ref) {
     __shared__ float sa[16][65], sb[16][65];
     const int tm = blockIdx.y * 64, tn = blockIdx.x * 64;
@@ -258,7 +265,7 @@ __global__ __launch_bounds__(256) void ref_gemm(int ta, int tb, int M, int N, in
             const int m = tm + ty * 4 + i, n = tn + tx * 4 + j;
             if (m >= M || n >= N) continue;
             float v = acc[i][j];
-            if (bias) v += bias32 ? ((const float *)bias)[n] : (float)((const __bf16 *)bias)[n];
+            if (bias) v += bias32 ? ((const float *)bias)[n] : (float)((const T *)bias)[n];
             ref[(int64_t)m * N + n] = v;
         }
 }
@@ -270,7 +277,13 @@ __global__ __launch_bounds__(256) void full_compare(const OT *__restrict__ D, in
     bool bad = false;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < MN; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / N;
-        const float v = (float)D[r * ldd + (i - r * N)], w = ref[i];
+        float v = (float)D[r * ldd + (i - r * N)];
+        const float w = ref[i];
+        if constexpr (std::is_same<OT, _Float16>::value) {
+            // an fp16 result that overflowed is right when the reference rounds to the same inf, and is otherwise held
+            // to the reference as the first value past fp16's range; finite results are compared as for bf16
+            if (isinf(v)) v = v == (float)(_Float16)w ? w : copysignf(65520.f, v);
+        }
         const float d = fabsf(v - w);
         bad = bad || !(d == d);
         md = fmaxf(md, d == d ? d : 0.f);
@@ -287,8 +300,13 @@ float *make_reference(const Call &c) {
     if (k.M > (64 << 16) || k.N > (int64_t)INT32_MAX || k.K > (int64_t)INT32_MAX) return nullptr;
     float *ref = nullptr;
     if (hipMalloc((void **)&ref, (size_t)k.M * k.N * sizeof(float)) != hipSuccess) return nullptr;
-    hipLaunchKernelGGL(ref_gemm, dim3((unsigned)((k.N + 63) / 64), (unsigned)((k.M + 63) / 64)), dim3(256), 0, c.st, k.ta, k.tb,
-                       (int)k.M, (int)k.N, (int)k.K, (const __bf16 *)c.A, k.lda, (const __bf16 *)c.B, k.ldb, c.bias, k.bias32, ref);
+    const dim3 grid((unsigned)((k.N + 63) / 64), (unsigned)((k.M + 63) / 64));
+    if (k.f16)
+        hipLaunchKernelGGL(ref_gemm<_Float16>, grid, dim3(256), 0, c.st, k.ta, k.tb, (int)k.M, (int)k.N, (int)k.K,
+                           (const _Float16 *)c.A, k.lda, (const _Float16 *)c.B, k.ldb, c.bias, k.bias32, ref);
+    else
+        hipLaunchKernelGGL(ref_gemm<__bf16>, grid, dim3(256), 0, c.st, k.ta, k.tb, (int)k.M, (int)k.N, (int)k.K,
+                           (const __bf16 *)c.A, k.lda, (const __bf16 *)c.B, k.ldb, c.bias, k.bias32, ref);
     if (hipGetLastError() != hipSuccess) {
         (void)hipFree(ref);
         return nullptr;
@@ -316,6 +334,8 @@ bool validate(State &S, const Call &c, Problem &p, const hipblasLtMatmulAlgo_t &
         if (run(S, c, p, algo, ws_need, split) != HIPBLAS_STATUS_SUCCESS) return false;
         if (k.d32)
             hipLaunchKernelGGL(full_compare<float>, dim3(blocks), dim3(256), 0, c.st, (const float *)c.D, k.ldd, MN, (int)k.N, ref, out2);
+        else if (k.f16)
+            hipLaunchKernelGGL(full_compare<_Float16>, dim3(blocks), dim3(256), 0, c.st, (const _Float16 *)c.D, k.ldd, MN, (int)k.N, ref, out2);
         else
             hipLaunchKernelGGL(full_compare<__bf16>, dim3(blocks), dim3(256), 0, c.st, (const __bf16 *)c.D, k.ldd, MN, (int)k.N, ref, out2);
         float h[2] = {0.f, 0.f};
@@ -344,6 +364,9 @@ hipblasStatus_t run(State &S, const Call &c, Problem &p, const hipblasLtMatmulAl
     if (c.k.d32)
         hipLaunchKernelGGL(reduce_splits<float>, dim3(rblocks + fblocks), dim3(256), 0, c.st, (const float *)c.ws, split, MN,
                            (int)c.k.N, c.k.ldd, (float *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
+    else if (c.k.f16)
+        hipLaunchKernelGGL(reduce_splits<_Float16>, dim3(rblocks + fblocks), dim3(256), 0, c.st, (const float *)c.ws, split, MN,
+                           (int)c.k.N, c.k.ldd, (_Float16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
     else
         hipLaunchKernelGGL(reduce_splits<__bf16>, dim3(rblocks + fblocks), dim3(256), 0, c.st, (const float *)c.ws, split, MN,
                            (int)c.k.N, c.k.ldd, (__bf16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
@@ -376,8 +399,8 @@ hipblasStatus_t choose_for_split(State &S, const Call &c, Problem &p, int split,
         const Key &k = c.k;
         hipblasStatus_t s = hipblaslt_ext::getAllAlgos(
             S.handle, hipblaslt_ext::GemmType::HIPBLASLT_GEMM, k.tb ? HIPBLAS_OP_T : HIPBLAS_OP_N,
-            k.ta ? HIPBLAS_OP_T : HIPBLAS_OP_N, HIP_R_16BF, HIP_R_16BF, d32 ? HIP_R_32F : HIP_R_16BF,
-            d32 ? HIP_R_32F : HIP_R_16BF, HIPBLAS_COMPUTE_32F, all);
+            k.ta ? HIPBLAS_OP_T : HIPBLAS_OP_N, k.t16(), k.t16(), d32 ? HIP_R_32F : k.t16(),
+            d32 ? HIP_R_32F : k.t16(), HIPBLAS_COMPUTE_32F, all);
         if (s == HIPBLAS_STATUS_SUCCESS)
             for (auto &r : all) {
                 size_t need = 0;
@@ -543,7 +566,7 @@ int vah_gemm_set_tuning(int mode, int candidates) {
     return VAH_OK;
 }
 
-static int gemm_impl(const char *fn, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+static int gemm_impl(const char *fn, int f16, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
                      const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue, const void *bias,
                      int bias_is_f32, void *workspace, int64_t workspace_bytes, void *stream, const float *fin_part,
                      int64_t fin_nparts, int64_t fin_C, float *fin_out);
@@ -551,7 +574,7 @@ static int gemm_impl(const char *fn, int trans_a, int trans_b, int64_t M, int64_
 int vah_gemm_bf16(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
                   const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue, const void *bias,
                   int bias_is_f32, void *workspace, int64_t workspace_bytes, void *stream) {
-    return gemm_impl("vah_gemm_bf16", trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, epilogue, bias, bias_is_f32,
+    return gemm_impl("vah_gemm_bf16", 0, trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, epilogue, bias, bias_is_f32,
                      workspace, workspace_bytes, stream, nullptr, 0, 0, nullptr);
 }
 
@@ -567,11 +590,32 @@ int vah_gemm_bf16_fin(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
         clear_error();
         return fail(VAH_E_SHAPE, "vah_gemm_bf16_fin: bad finalize job");
     }
-    return gemm_impl("vah_gemm_bf16_fin", trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, VAH_GEMM_EPI_NONE, nullptr,
+    return gemm_impl("vah_gemm_bf16_fin", 0, trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, VAH_GEMM_EPI_NONE, nullptr,
                      0, workspace, workspace_bytes, stream, fin_part, fin_nparts, fin_C, fin_out);
 }
 
-static int gemm_impl(const char *fn, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+// The fp16 twins: A, B, a 16-bit D and a 16-bit bias are _Float16; everything else as above.
+int vah_gemm_f16(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+                 const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue, const void *bias,
+                 int bias_is_f32, void *workspace, int64_t workspace_bytes, void *stream) {
+    return gemm_impl("vah_gemm_f16", 1, trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, epilogue, bias, bias_is_f32,
+                     workspace, workspace_bytes, stream, nullptr, 0, 0, nullptr);
+}
+
+int vah_gemm_f16_fin(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+                     const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, void *workspace,
+                     int64_t workspace_bytes, const float *fin_part, int64_t fin_nparts, int64_t fin_C, float *fin_out,
+                     void *stream) {
+    using namespace vah;
+    if (!fin_part || !fin_out || fin_nparts < 1 || fin_C < 1 || fin_nparts > (1 << 20) || fin_C > (1 << 24)) {
+        clear_error();
+        return fail(VAH_E_SHAPE, "vah_gemm_f16_fin: bad finalize job");
+    }
+    return gemm_impl("vah_gemm_f16_fin", 1, trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, VAH_GEMM_EPI_NONE, nullptr,
+                     0, workspace, workspace_bytes, stream, fin_part, fin_nparts, fin_C, fin_out);
+}
+
+static int gemm_impl(const char *fn, int f16, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
                      const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue, const void *bias,
                      int bias_is_f32, void *workspace, int64_t workspace_bytes, void *stream, const float *fin_part,
                      int64_t fin_nparts, int64_t fin_C, float *fin_out) {
@@ -585,6 +629,10 @@ static int gemm_impl(const char *fn, int trans_a, int trans_b, int64_t M, int64_
     if (epilogue != VAH_GEMM_EPI_NONE && epilogue != VAH_GEMM_EPI_BIAS) return fail(VAH_E_SHAPE, "%s: unknown epilogue", fn);
     if ((epilogue == VAH_GEMM_EPI_BIAS) != (bias != nullptr)) return fail(VAH_E_NULL, "%s: bias does not match the epilogue", fn);
     if (workspace_bytes < 0 || (workspace_bytes > 0 && !workspace)) return fail(VAH_E_NULL, "%s: workspace", fn);
+    // hipBLASLt's bias epilogue reads an fp16 bias correctly only into an fp16 D: into an fp32 D the result is garbage,
+    // with a success status (fused.gemm_16 widens such a bias to fp32 before the call)
+    if (f16 && bias && !bias_is_f32 && d_is_f32)
+        return fail(VAH_E_UNSUPPORTED, "%s: an fp16 bias into an fp32 output is not supported (pass the bias in fp32)", fn);
 
     State &S = state();
     std::lock_guard<std::mutex> lock(S.mu);
@@ -592,7 +640,7 @@ static int gemm_impl(const char *fn, int trans_a, int trans_b, int64_t M, int64_
         const hipblasStatus_t s = hipblasLtCreate(&S.handle);
         if (s != HIPBLAS_STATUS_SUCCESS) return fail(VAH_E_UNSUPPORTED, "%s: hipblasLtCreate: %s", fn, status_name(s));
     }
-    Call c{{trans_a ? 1 : 0, trans_b ? 1 : 0, d_is_f32 ? 1 : 0, epilogue, bias_is_f32 ? 1 : 0, M, N, K, lda, ldb, ldd},
+    Call c{{f16 ? 1 : 0, trans_a ? 1 : 0, trans_b ? 1 : 0, d_is_f32 ? 1 : 0, epilogue, bias_is_f32 ? 1 : 0, M, N, K, lda, ldb, ldd},
            A, B, bias, D, workspace, (size_t)workspace_bytes, (hipStream_t)stream};
     c.fin_part = fin_part;
     c.fin_nparts = (int)fin_nparts;
@@ -601,7 +649,8 @@ static int gemm_impl(const char *fn, int trans_a, int trans_b, int64_t M, int64_
     hipblasStatus_t s = HIPBLAS_STATUS_SUCCESS;
     // named by the product's role in a Linear layer: nt = forward (x W^T), nn = input gradient (g W), tn = weight gradient
     // (g^T x); flops for the MFMA roofline rows of bench.py
-    const char *role = trans_a ? (fin_part ? "gemm_tn_fin" : "gemm_tn") : (trans_b ? "gemm_nt" : "gemm_nn");
+    const char *role = f16 ? (trans_a ? (fin_part ? "gemm_tn_fin_f16" : "gemm_tn_f16") : (trans_b ? "gemm_nt_f16" : "gemm_nn_f16"))
+                           : (trans_a ? (fin_part ? "gemm_tn_fin" : "gemm_tn") : (trans_b ? "gemm_nt" : "gemm_nn"));
     LaunchScope scope(role, (M * K + K * N) * 2 + M * N * (d_is_f32 ? 4 : 2), c.st, 0, 2 * M * N * K);
     auto it = S.table.find(c.k);
     if (it != S.table.end() && !it->second.resolved) {
@@ -660,7 +709,8 @@ int64_t vah_gemm_library_version(void) {
     return v;
 }
 
-// One line per problem: "ta tb d32 epi bias32 M N K lda ldb ldd index split us".
+// One line per problem: "ta tb d32 epi bias32 M N K lda ldb ldd index split us"; an fp16 problem is the same line
+// behind a leading "f16 " token (so no fp16 line starts like a bf16 one).
 int64_t vah_gemm_table_dump(char *buf, int64_t cap) {
     using namespace vah;
     State &S = state();
@@ -668,6 +718,7 @@ int64_t vah_gemm_table_dump(char *buf, int64_t cap) {
     std::ostringstream os;
     for (auto &kv : S.table) {
         const Key &k = kv.first;
+        if (k.f16) os << "f16 ";
         os << k.ta << ' ' << k.tb << ' ' << k.d32 << ' ' << k.epi << ' ' << k.bias32 << ' ' << k.M << ' ' << k.N << ' '
            << k.K << ' ' << k.lda << ' ' << k.ldb << ' ' << k.ldd << ' ' << kv.second.index << ' ' << kv.second.split << ' '
            << kv.second.us << '\n';
@@ -696,6 +747,8 @@ int vah_gemm_table_load(const char *text) {
         std::istringstream ls(line);
         Key k;
         Choice ch;
+        k.f16 = line.compare(0, 4, "f16 ") == 0;
+        if (k.f16) ls.ignore(4);
         if (!(ls >> k.ta >> k.tb >> k.d32 >> k.epi >> k.bias32 >> k.M >> k.N >> k.K >> k.lda >> k.ldb >> k.ldd >> ch.index >> ch.split >> ch.us))
             return fail(VAH_E_SHAPE, "vah_gemm_table_load: malformed line '%s'", line.c_str());
         ch.resolved = false;

@@ -9,10 +9,15 @@ The row-streaming operators - LayerNorm (plain, keep, dual), residual, residual 
 DWConv - also take fp16 autocast (the reference's AMP mode): the same kernels instantiated on fp16
 (`*_f16` entry points), fp32 math, fp32 -> fp16 rounded to nearest even with overflow to inf and
 subnormals kept.  So does the output tail (csrc/tail_ops.hip: the BatchNorm tail, bn_relu, halve, the token <-> plane
-transposes, the NCHW max-pool and up_from_tokens, whose two products are torch's fp16 library GEMMs).  Linear, conv1x1,
-patch embedding and the MSDA pair core stay bf16-only; under fp16 autocast they are torch's - the deformable attention
-itself is not: MSDeformAttn's fp16 value / offsets / logits go to the fp16 instantiation of the fused MSDA kernels
-(ops/functions/ms_deform_attn_fused.py; ENABLED['fp16_msda']).
+transposes, the NCHW max-pool and up_from_tokens, whose two products are torch's fp16 library GEMMs).
+
+The Linear layers (linear, linear_pair with 16-bit outputs, the GELU between two Linears, forward_epoch's weight copies)
+run on the tuned GEMM dispatcher (csrc/gemm.hip) under bf16 autocast and, with ENABLED['fp16_linear'], under fp16
+autocast: fp16 operands, fp32 accumulation, dX an fp16 GEMM output that overflows to inf as torch's does, dW and db in
+fp32 straight from the accumulators (torch rounds dW to fp16 first), the same side-stream deferral, `fin` path and bias
+partials as for bf16.  conv1x1, patch embedding and the MSDA pair core stay bf16-only; under fp16 autocast they are
+torch's - the deformable attention itself is not: MSDeformAttn's fp16 value / offsets / logits go to the fp16
+instantiation of the fused MSDA kernels (ops/functions/ms_deform_attn_fused.py; ENABLED['fp16_msda']).
 """
 import os
 
@@ -24,6 +29,7 @@ import _vah
 ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln': True, 'dwconv': True, 'linear': True, 'bn_tail': True,
            'bn_relu': True, 'bias_fold': True, 'keep_feat': True, 'maps': True, 'maps_in': True, 'linear_pair': True, 'maxpool': True, 'conv1x1': True, 'ln_dual': True, 'wgrad_fin': True, 'spm_nhwc': True, 'up_gemm': True, 'patch_gemm': True, 'wgrad_overlap': True, 'drop_pool': True,
            'fp16_rows': True, 'fp16_spm': True, 'fp16_tail': True, 'bias_partials': True,
+           'fp16_linear': True,
            'fp16_msda': True}        # fp16_msda: read by ops.functions.ms_deform_attn_fused.fused_supported
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
@@ -42,6 +48,21 @@ def _scratch(K, device):
 
 def _bf16_autocast():
     return torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16
+
+
+def _linear_dtype():
+    """The 16-bit type the Linear path (GEMM dispatcher, weight copies, GELU backward, bias partials) runs in under the
+    active autocast: torch.bfloat16, torch.float16, or None (no autocast, another autocast type, or fp16 with its switch
+    off: VAH_FUSED_DISABLE=fp16_linear, torch's library calls under fp16 autocast, for A/B runs)."""
+    if not torch.is_autocast_enabled():
+        return None
+    dtype = torch.get_autocast_dtype('cuda')
+    return dtype if _linear_takes(dtype) else None
+
+
+def _linear_takes(dtype):
+    """Is ``dtype`` a 16-bit type the Linear path is instantiated on?  bf16 always; fp16 unless switched off."""
+    return dtype == torch.bfloat16 or (dtype == torch.float16 and ENABLED['fp16_linear'])
 
 
 def _rows_dtype(dtype):
@@ -63,7 +84,10 @@ def _sym(name, dtype):
     """The entry point ``name`` (its bf16 spelling) for 16-bit operands of ``dtype``: itself or its `_f16` twin."""
     if dtype == torch.bfloat16:
         return getattr(_vah.lib, name)
-    return getattr(_vah.lib, _vah.FUSED_F16_TWINS[name] if name in _vah.FUSED_F16_TWINS else _vah.TAIL_F16_TWINS[name])
+    for twins in (_vah.FUSED_F16_TWINS, _vah.LINEAR_F16_TWINS):
+        if name in twins:
+            return getattr(_vah.lib, twins[name])
+    return getattr(_vah.lib, _vah.TAIL_F16_TWINS[name])
 
 
 def _tail_dtype():
@@ -218,10 +242,10 @@ def layer_norm_keep(norm, x, fan_out=False):
 
 
 # ---------------------------------------------------------------------------------------
-# nn.Linear under bf16 autocast
+# nn.Linear under bf16 / fp16 autocast
 # ---------------------------------------------------------------------------------------
 class _Bf16Copies:
-    """bf16 working copies of fp32 parameters.  autocast makes the same copies, but one tiny cast
+    """16-bit (bf16, or fp16 under fp16 autocast) working copies of fp32 parameters.  autocast makes the same copies, but one tiny cast
     kernel per parameter per use (and one more per gradient on the way back).  Here a model's forward
     opens an EPOCH (``begin_forward``): ONE multi-tensor cast writes fresh copies of all its Linear
     parameters into one new flat buffer, and those copies serve every use until the forward ends
@@ -230,30 +254,33 @@ class _Bf16Copies:
     Nothing is keyed on ``Tensor._version``: in-place writes through ``.data`` (legacy optimizers,
     EMA / fp16 hooks, ``weight.data.normal_()``) do not bump it, and a cached copy would silently go
     stale.  Copies are never rewritten in place either, so a backward that saved one still sees the
-    values of its own forward whatever ran in between."""
+    values of its own forward whatever ran in between.  An entry is keyed by the copy's type as well: a model run under
+    bf16 and then under fp16 (or a Linear reached under another autocast type inside one forward) is never served the
+    other type's copy."""
 
     def __init__(self):
-        self.entries = {}          # id(param) -> (weakref(param), copy, epoch)
+        self.entries = {}          # (id(param), dtype) -> (weakref(param), copy, epoch)
         self.epoch = 0             # even: no forward open; odd: the open forward's epoch
 
-    def get(self, p):
-        e = self.entries.get(id(p))
-        if e is not None and e[2] == self.epoch and (self.epoch & 1) and e[0]() is p and e[1].device == p.device:
+    def get(self, p, dtype=torch.bfloat16):
+        e = self.entries.get((id(p), dtype))
+        if (e is not None and e[2] == self.epoch and (self.epoch & 1) and e[0]() is p and e[1].device == p.device
+                and e[1].dtype == dtype):
             return e[1]
-        return p.detach().to(torch.bfloat16)
+        return p.detach().to(dtype)
 
-    def begin(self, params):
+    def begin(self, params, dtype=torch.bfloat16):
         import weakref
         self.epoch += 1 if (self.epoch & 1) == 0 else 2          # a nested / aborted forward just opens a new epoch
         if not params:
             return
-        flat = torch.empty(sum(p.numel() for p in params), dtype=torch.bfloat16, device=params[0].device)
+        flat = torch.empty(sum(p.numel() for p in params), dtype=dtype, device=params[0].device)
         views = [v.view(p.shape) for v, p in zip(flat.split([p.numel() for p in params]), params)]
         torch._foreach_copy_(views, [p.detach() for p in params])
         if len(self.entries) > 4096:               # drop entries of collected parameters
             self.entries = {k: v for k, v in self.entries.items() if v[0]() is not None}
         for p, v in zip(params, views):
-            self.entries[id(p)] = (weakref.ref(p), v, self.epoch)
+            self.entries[(id(p), dtype)] = (weakref.ref(p), v, self.epoch)
 
     def end(self):
         if self.epoch & 1:
@@ -319,7 +346,7 @@ DROP_POOL = _DropPool()
 
 class forward_epoch:
     """``with fused.forward_epoch(model): ...`` around a model's forward: on entry ONE multi-tensor cast
-    makes the bf16 copies of all its fp32 nn.Linear parameters, which then serve every fused Linear of
+    makes the 16-bit copies (the autocast's type) of all its fp32 nn.Linear parameters, which then serve every fused Linear of
     this forward; on exit (also by an exception) the epoch closes and later uses cast on their own, so
     a parameter written between two forwards - by any means, `.data` included - is always seen."""
 
@@ -328,7 +355,8 @@ class forward_epoch:
 
     def __enter__(self):
         module = self.module
-        if not (ENABLED['linear'] and _bf16_autocast()):
+        t16 = _linear_dtype()
+        if not (ENABLED['linear'] and t16 is not None):
             return self
         # the list is cached on the module; a parameter that is replaced later is simply not part of the
         # bulk cast and gets its own cast on use (slower, never stale)
@@ -339,7 +367,7 @@ class forward_epoch:
             module.__dict__['_vah_linear_params'] = params
         live = [p for p in params if p.dtype == torch.float32 and p.is_cuda]
         if live:
-            BF16_COPIES.begin(live)
+            BF16_COPIES.begin(live, t16)
             SIDE.begin_epoch()
             BIAS_PARTIALS.begin_epoch()
             if module.training:
@@ -356,12 +384,13 @@ _GEMM_WS_BYTES = 32 << 20
 WGRAD_F32 = os.environ.get('VAH_LINEAR_WGRAD', 'f32') == 'f32'
 GEMM_TABLE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tuning',
                           'gemm_table_mi355x_base_det_1024.txt')
+GEMM_TABLE_F16 = GEMM_TABLE[:-len('.txt')] + '_f16.txt'       # the fp16 problems of the same step ('f16 ' lines only)
 
 
 def _configure_gemm():
     """VAH_GEMM_TUNING = mode[,candidates] (0 first heuristic answer, 1 time the heuristic
     candidates [default], 2 time every algorithm);  VAH_GEMM_TABLE = path of a tuned table to load
-    ('' = none; default: the committed table);  VAH_GEMM_TABLE_DUMP = path to write the table to
+    ('' = none; default: the committed tables, bf16 and fp16);  VAH_GEMM_TABLE_DUMP = path to write the table to
     at exit."""
     spec = os.environ.get('VAH_GEMM_TUNING')
     if spec:
@@ -381,14 +410,21 @@ def _load_gemm_table():
     """On the first GEMM (needs the GPU: the table is tied to the hipBLASLt build that is loaded)."""
     global _GEMM_TABLE_LOADED
     _GEMM_TABLE_LOADED = True
-    path = os.environ.get('VAH_GEMM_TABLE', GEMM_TABLE)
-    if path and os.path.exists(path):
-        _vah.gemm_table_load(open(path).read())
+    path = os.environ.get('VAH_GEMM_TABLE')
+    for path in ((GEMM_TABLE, GEMM_TABLE_F16) if path is None else (path,)):
+        if path and os.path.exists(path):
+            _vah.gemm_table_load(open(path).read())
 
 
-def gemm_bf16(a, b, trans_a=False, trans_b=False, out_dtype=torch.bfloat16, bias=None, out=None):
-    """op(a) @ op(b) for contiguous 2-D bf16 matrices on the tuned hipBLASLt dispatcher
-    (csrc/gemm.hip); fp32 accumulation, bf16 or fp32 result."""
+def gemm_16(a, b, trans_a=False, trans_b=False, out_dtype=None, bias=None, out=None):
+    """op(a) @ op(b) for contiguous 2-D matrices of one 16-bit type (bf16 or fp16) on the tuned hipBLASLt dispatcher
+    (csrc/gemm.hip); fp32 accumulation; the result in the operands' type (out_dtype None) or fp32.  A 16-bit bias is
+    of the operands' type."""
+    t16 = a.dtype
+    assert t16 in (torch.bfloat16, torch.float16) and b.dtype == t16, (a.dtype, b.dtype)
+    if out_dtype is None:
+        out_dtype = t16
+    assert out_dtype in (t16, torch.float32) and (bias is None or bias.dtype in (t16, torch.float32))
     M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
     N = b.shape[0] if trans_b else b.shape[1]
     assert (b.shape[1] if trans_b else b.shape[0]) == K and a.is_contiguous() and b.is_contiguous()
@@ -401,6 +437,8 @@ def gemm_bf16(a, b, trans_a=False, trans_b=False, out_dtype=torch.bfloat16, bias
         return d
     if K == 0:
         return d.zero_()
+    if bias is not None and bias.dtype == torch.float16 and out_dtype == torch.float32:
+        bias = bias.float()       # hipBLASLt misreads an fp16 bias into an fp32 output (the entry point refuses the pairing)
     if not _GEMM_TABLE_LOADED:
         _load_gemm_table()
     ws_bytes = _GEMM_WS_BYTES
@@ -409,22 +447,28 @@ def gemm_bf16(a, b, trans_a=False, trans_b=False, out_dtype=torch.bfloat16, bias
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
     epilogue = _vah.GEMM_EPI_BIAS if bias is not None else _vah.GEMM_EPI_NONE
     with _vah.on(a.device):
-        _vah.check(_vah.lib.vah_gemm_bf16(
+        _vah.check(_sym('vah_gemm_bf16', t16)(
             int(trans_a), int(trans_b), M, N, K, a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1],
             d.data_ptr(), N, int(out_dtype == torch.float32), epilogue,
             bias.data_ptr() if bias is not None else None,
-            int(bias is not None and bias.dtype == torch.float32), ws.data_ptr(), ws_bytes, _stream(a)), 'gemm_bf16')
+            int(bias is not None and bias.dtype == torch.float32), ws.data_ptr(), ws_bytes, _stream(a)), 'gemm_bf16' if t16 == torch.bfloat16 else 'gemm_f16')
     return d
+
+
+gemm_bf16 = gemm_16         # the name from before the dispatcher took fp16 operands
 
 
 def _wgrad_bgrad(g2, x2, partials=None):
     """(dW, db) = (g2^T x2 in fp32, column sums of g2) of a Linear backward: column-sum partials, the
-    (split-K) GEMM and ONE launch that both reduces the GEMM's slices and sums the partials.  ``partials``:
+    (split-K) GEMM and ONE launch that both reduces the GEMM's slices and sums the partials.  g2, x2: one 16-bit type
+    (bf16 or fp16), which picks the entry points.  ``partials``:
     (rows of partial column sums of g2, their number) left by the kernel that wrote g2 (_BiasPartials) - no
     column-sum launch and no second read of g2 then."""
     import ctypes
     R, N = g2.shape
     K = x2.shape[1]
+    t16 = g2.dtype
+    assert x2.dtype == t16
     if not _GEMM_TABLE_LOADED:
         _load_gemm_table()
     dev = g2.device
@@ -438,11 +482,11 @@ def _wgrad_bgrad(g2, x2, partials=None):
             cws, nparts = partials[0], ctypes.c_int64(partials[1])
         else:
             cws, nparts = _scratch(N, dev), ctypes.c_int64(0)
-            _vah.check(_vah.lib.vah_colsum_bf16_partials(g2.data_ptr(), R, N, cws.data_ptr(), ctypes.byref(nparts), st),
+            _vah.check(_sym('vah_colsum_bf16_partials', t16)(g2.data_ptr(), R, N, cws.data_ptr(), ctypes.byref(nparts), st),
                        'colsum_partials')
-        _vah.check(_vah.lib.vah_gemm_bf16_fin(1, 0, N, K, R, g2.data_ptr(), N, x2.data_ptr(), K, gw.data_ptr(), K, 1,
+        _vah.check(_sym('vah_gemm_bf16_fin', t16)(1, 0, N, K, R, g2.data_ptr(), N, x2.data_ptr(), K, gw.data_ptr(), K, 1,
                                               ws.data_ptr(), ws_bytes, cws.data_ptr(), nparts.value, N, gb.data_ptr(), st),
-                   'gemm_bf16_fin')
+                   'gemm_bf16_fin' if t16 == torch.bfloat16 else 'gemm_f16_fin')
     return gw, gb
 
 
@@ -580,7 +624,7 @@ class _BiasPartials:
 
     @staticmethod
     def wanted(z):
-        return bool(ENABLED['bias_partials'] and getattr(z, _BiasPartials.ATTR, False) and z.dtype == torch.bfloat16
+        return bool(ENABLED['bias_partials'] and getattr(z, _BiasPartials.ATTR, False) and _linear_takes(z.dtype)
                     and z.shape[-1] % 8 == 0)
 
     @staticmethod
@@ -633,19 +677,20 @@ def _bias_partials_out(C, device):
 
 
 class _LinearBF16(torch.autograd.Function):
-    """y = x W^T + b with bf16 operands and fp32 accumulation (what autocast makes of F.linear).
-    Backward: dX in bf16, dW straight into fp32 from the GEMM (no bf16 rounding, no cast kernel),
-    db by the column-sum kernel."""
+    """y = x W^T + b with 16-bit operands (``t16``: bf16 or fp16, the autocast's type) and fp32 accumulation (what
+    autocast makes of F.linear).  Backward: dX in t16 (an fp16 dX overflows to inf, as torch's does), dW straight into
+    fp32 from the GEMM (no 16-bit rounding, no cast kernel), db by the column-sum kernel.  The backward takes the type
+    from the saved operands."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, t16=torch.bfloat16):
         K = x.shape[-1]
         x2 = x.reshape(-1, K)
-        if x2.dtype != torch.bfloat16:
-            x2 = x2.to(torch.bfloat16)
+        if x2.dtype != t16:
+            x2 = x2.to(t16)
         x2 = x2.contiguous()
-        wb = BF16_COPIES.get(weight)
-        y = gemm_bf16(x2, wb, trans_b=True, bias=bias.detach() if bias is not None else None)
+        wb = BF16_COPIES.get(weight, t16)
+        y = gemm_16(x2, wb, trans_b=True, bias=bias.detach() if bias is not None else None)
         ctx.save_for_backward(x2, wb)
         ctx.has_bias = bias is not None
         ctx.side = SIDE.note(weight, bias)
@@ -657,9 +702,10 @@ class _LinearBF16(torch.autograd.Function):
     def backward(ctx, g):
         x2, wb = ctx.saved_tensors
         N = wb.shape[0]
+        t16 = wb.dtype
         g2 = g.reshape(-1, N)
-        if g2.dtype != torch.bfloat16:
-            g2 = g2.to(torch.bfloat16)
+        if g2.dtype != t16:
+            g2 = g2.to(t16)
         g2 = g2.contiguous()
         gx = gw = gb = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
@@ -688,27 +734,27 @@ class _LinearBF16(torch.autograd.Function):
                 gb = torch.empty(N, dtype=torch.float32, device=g2.device)
                 ws = _scratch(N, g2.device)
                 with _vah.on(g2.device):
-                    _vah.check(_vah.lib.vah_colsum_bf16(g2.data_ptr(), g2.shape[0], N, gb.data_ptr(),
-                                                        ws.data_ptr(), _stream(g2)), 'colsum')
-        return gx, gw, gb
+                    _vah.check(_sym('vah_colsum_bf16', t16)(g2.data_ptr(), g2.shape[0], N, gb.data_ptr(),
+                                                            ws.data_ptr(), _stream(g2)), 'colsum')
+        return gx, gw, gb, None
 
 
 class _PairCopies:
-    """bf16 [Wa; Wb] (rows concatenated) and fp32 [ba; bb] of two Linear layers that read the same
-    input: built once per forward epoch (see _Bf16Copies), on every use outside one."""
+    """16-bit [Wa; Wb] (rows concatenated) and fp32 [ba; bb] of two Linear layers that read the same
+    input: built once per forward epoch and 16-bit type (see _Bf16Copies), on every use outside one."""
 
     def __init__(self):
         self.entries = {}
 
-    def get(self, a, b):
-        key = (id(a.weight), id(b.weight))
+    def get(self, a, b, dtype=torch.bfloat16):
+        key = (id(a.weight), id(b.weight), dtype)
         epoch = BF16_COPIES.epoch
         e = self.entries.get(key)
         if e is not None and e[0] == epoch and (epoch & 1) and e[1].device == a.weight.device and e[3]() is a.weight:
             return e[1], e[2]
         import weakref
         with torch.no_grad():
-            w = torch.cat([a.weight.detach(), b.weight.detach()], 0).to(torch.bfloat16)
+            w = torch.cat([a.weight.detach(), b.weight.detach()], 0).to(dtype)
             bias = torch.cat([a.bias.detach(), b.bias.detach()], 0).float()
         if len(self.entries) > 1024:
             self.entries.clear()
@@ -730,11 +776,12 @@ class _LinearPairBF16(torch.autograd.Function):
     def forward(ctx, x, wa, ba, wb, bb, pair, f32_out=False):
         K = x.shape[-1]
         x2 = x.reshape(-1, K)
-        if x2.dtype != torch.bfloat16:
-            x2 = x2.to(torch.bfloat16)
-        x2 = x2.contiguous()
         w, bias = pair
-        y = gemm_bf16(x2, w, trans_b=True, bias=bias, out_dtype=torch.float32 if f32_out else torch.bfloat16)
+        t16 = w.dtype                          # bf16 or fp16: the type of the pair's weight copy
+        if x2.dtype != t16:
+            x2 = x2.to(t16)
+        x2 = x2.contiguous()
+        y = gemm_16(x2, w, trans_b=True, bias=bias, out_dtype=torch.float32 if f32_out else t16)
         na = wa.shape[0]
         ctx.save_for_backward(x2, w)
         ctx.na, ctx.in_shape, ctx.in_dtype = na, x.shape, x.dtype
@@ -747,7 +794,7 @@ class _LinearPairBF16(torch.autograd.Function):
         na = ctx.na
         nb = w.shape[0] - na
         R = x2.shape[0]
-        g = torch.empty((R, na + nb), dtype=torch.bfloat16, device=x2.device)
+        g = torch.empty((R, na + nb), dtype=w.dtype, device=x2.device)
         g[:, :na] = ga.reshape(R, na) if ga is not None else 0
         g[:, na:] = gb.reshape(R, nb) if gb is not None else 0
         gx = gw = gbias = None
@@ -766,8 +813,8 @@ class _LinearPairBF16(torch.autograd.Function):
                 gbias = torch.empty(na + nb, dtype=torch.float32, device=g.device)
                 ws = _scratch(na + nb, g.device)
                 with _vah.on(g.device):
-                    _vah.check(_vah.lib.vah_colsum_bf16(g.data_ptr(), R, na + nb, gbias.data_ptr(), ws.data_ptr(),
-                                                        _stream(g)), 'colsum')
+                    _vah.check(_sym('vah_colsum_bf16', g.dtype)(g.data_ptr(), R, na + nb, gbias.data_ptr(), ws.data_ptr(),
+                                                                _stream(g)), 'colsum')
         return (gx, gw[:na] if gw is not None else None, gbias[:na] if gbias is not None else None,
                 gw[na:] if gw is not None else None, gbias[na:] if gbias is not None else None, None, None)
 
@@ -777,12 +824,16 @@ def linear_pair(lin_a, lin_b, x, f32_out=False):
     accumulators (MSDeformAttn's sampling offsets: the reference keeps them in fp32, and d(out)/d(location) jumps at
     integer pixel coordinates, so 8-bit offsets cost the upstream gradients 0.3 - 0.7 of relative L2 on small maps)."""
     wa, wb = lin_a.weight, lin_b.weight
-    if (ENABLED['linear'] and ENABLED['linear_pair'] and x.is_cuda and _bf16_autocast() and wa.dtype == torch.float32
+    # fp16 autocast: the form with 16-bit outputs only (fp32 offsets under fp16 are MSDeformAttn's own business)
+    t16 = _linear_dtype()
+    if f32_out and t16 != torch.bfloat16:
+        t16 = None
+    if (ENABLED['linear'] and ENABLED['linear_pair'] and x.is_cuda and t16 is not None and wa.dtype == torch.float32
             and wb.dtype == torch.float32 and lin_a.bias is not None and lin_b.bias is not None
-            and x.dtype in (torch.bfloat16, torch.float32) and (wa.shape[0] + wb.shape[0]) % 8 == 0
+            and x.dtype in (t16, torch.float32) and (wa.shape[0] + wb.shape[0]) % 8 == 0
             and wa.shape[1] % 8 == 0 and wa.shape[1] == wb.shape[1] and x.numel() > 0
             and type(lin_a) is torch.nn.Linear and type(lin_b) is torch.nn.Linear):
-        return _LinearPairBF16.apply(x, wa, lin_a.bias, wb, lin_b.bias, PAIR_COPIES.get(lin_a, lin_b), f32_out)
+        return _LinearPairBF16.apply(x, wa, lin_a.bias, wb, lin_b.bias, PAIR_COPIES.get(lin_a, lin_b, t16), f32_out)
     if f32_out and x.is_cuda and _bf16_autocast():
         # widths the paired GEMM does not take (a single deformable head: 8 + 4 outputs): two plain fp32 Linears
         with torch.autocast('cuda', enabled=False):
@@ -962,8 +1013,8 @@ class _UpFromTokens(torch.autograd.Function):
     GEMM per image, U_b (4*Co, h*w) = Wcat (4*Co, C) rows_b^T with Wcat rows (dy, dx, co), followed by the 2 x 2 sub-pixel
     interleave (csrc/tail_ops.hip::pixel_shuffle2); the backward is the inverse interleave and two GEMMs.  MIOpen's
     NCHW transposed convolution took 494 + 846 us for this layer at base_det (2 x 768 x 128 x 128).
-    bf16: the products are gemm_bf16.  fp16: they are torch's fp16 library GEMMs on the token rows, as every Linear in
-    that mode; dW is what autocast gives conv_transpose2d - fp16 products per image, summed over the images in fp32."""
+    bf16: the products are gemm_bf16.  fp16: they are torch's fp16 library GEMMs on the token rows (this operator's fp16
+    form was not moved to the dispatcher with the Linear layers); dW is what autocast gives conv_transpose2d - fp16 products per image, summed over the images in fp32."""
 
     @staticmethod
     def forward(ctx, rows, weight, h, w, addend, t16):
@@ -1072,15 +1123,16 @@ def linear(lin, x):
     """``lin(x)`` for an nn.Linear (reference: every nn.Linear of base/vit.py, adapter_modules.py
     and ms_deform_attn.py)."""
     w = lin.weight
-    if (ENABLED['linear'] and x.is_cuda and _bf16_autocast() and w.dtype == torch.float32
-            and x.dtype in (torch.bfloat16, torch.float32) and w.shape[0] % 8 == 0
+    t16 = _linear_dtype()
+    if (ENABLED['linear'] and x.is_cuda and t16 is not None and w.dtype == torch.float32
+            and x.dtype in (t16, torch.float32) and w.shape[0] % 8 == 0
             and w.shape[1] % 8 == 0 and x.numel() > 0 and type(lin) is torch.nn.Linear):
-        return BIAS_PARTIALS.mark(_LinearBF16.apply(x, w, lin.bias), lin.bias)
+        return BIAS_PARTIALS.mark(_LinearBF16.apply(x, w, lin.bias, t16), lin.bias)
     return lin(x)
 
 
 class _GeluBF16(torch.autograd.Function):
-    """Exact GELU on the bf16 output of a fused Linear: torch's forward kernel; the backward is one kernel that writes
+    """Exact GELU on the 16-bit (bf16 or fp16: taken from h) output of a fused Linear: torch's forward kernel; the backward is one kernel that writes
     dh and the partial column sums of dh - the Linear's bias gradient (_BiasPartials)."""
 
     @staticmethod
@@ -1093,21 +1145,22 @@ class _GeluBF16(torch.autograd.Function):
         (h,) = ctx.saved_tensors
         C = h.shape[-1]
         hc = h.contiguous()
-        da = da.contiguous().to(torch.bfloat16)
-        dh = torch.empty(h.shape, dtype=torch.bfloat16, device=h.device)
+        da = da.contiguous().to(h.dtype)
+        dh = torch.empty(h.shape, dtype=h.dtype, device=h.device)
         bpart, nparts = _bias_partials_out(C, h.device)
         import ctypes
         with _vah.on(h.device):
-            _vah.check(_vah.lib.vah_gelu_bwd_bsum_bf16(da.data_ptr(), hc.data_ptr(), h.numel() // C, C, dh.data_ptr(),
-                                                       bpart.data_ptr(), ctypes.byref(nparts), _stream(h)), 'gelu_bwd_bsum')
+            _vah.check(_sym('vah_gelu_bwd_bsum_bf16', h.dtype)(da.data_ptr(), hc.data_ptr(), h.numel() // C, C, dh.data_ptr(),
+                                                               bpart.data_ptr(), ctypes.byref(nparts), _stream(h)),
+                       'gelu_bwd_bsum')
         BIAS_PARTIALS.record(dh, bpart, nparts.value)
         return dh
 
 
 def gelu(act, h):
-    """``act(h)`` for the activation between two Linears (base/vit.py Mlp): an exact nn.GELU on the marked bf16 output
-    of a fused Linear under bf16 autocast takes the backward kernel that also sums fc1's bias gradient."""
-    if (isinstance(act, torch.nn.GELU) and act.approximate == 'none' and h.is_cuda and _bf16_autocast()
+    """``act(h)`` for the activation between two Linears (base/vit.py Mlp): an exact nn.GELU on the marked 16-bit output
+    of a fused Linear under bf16 (or, ENABLED['fp16_linear'], fp16) autocast takes the backward kernel that also sums fc1's bias gradient."""
+    if (isinstance(act, torch.nn.GELU) and act.approximate == 'none' and h.is_cuda and _linear_dtype() is not None
             and BIAS_PARTIALS.wanted(h) and h.numel() > 0 and h.requires_grad and torch.is_grad_enabled()):
         return _GeluBF16.apply(h)
     return act(h)
@@ -1127,7 +1180,7 @@ def _scale_residual_bwd(g, z, gp, s, dims, bias_partials):
     with _vah.on(g.device):
         if bias_partials:
             bpart, nparts = _bias_partials_out(C, g.device)
-            _vah.check(_vah.lib.vah_scale_residual_bwd_bsum(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(g)),
+            _vah.check(_sym('vah_scale_residual_bwd_bsum', z.dtype)(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(g)),
                        'scale_residual_bwd_bsum')
             BIAS_PARTIALS.record(dz, bpart, nparts.value)
         else:
@@ -1230,7 +1283,7 @@ class _ResidualLN(torch.autograd.Function):
             if ctx.bias_partials and gp is None:
                 import ctypes
                 bpart, nparts = _bias_partials_out(C, dev)
-                _vah.check(_vah.lib.vah_residual_layernorm_bwd_bsum(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(t)),
+                _vah.check(_sym('vah_residual_layernorm_bwd_bsum', z.dtype)(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(t)),
                            'residual_layernorm_bwd_bsum')
                 BIAS_PARTIALS.record(dz, bpart, nparts.value)
             else:
