@@ -143,16 +143,16 @@ def test_host_gates_cpu():
     import torch
     from vitadapter import fused
     assert fused.ENABLED['fp16_rows'] is True
-    assert fused._rows_dtype(torch.bfloat16) and fused._rows_dtype(torch.float16) and not fused._rows_dtype(torch.float32)
-    assert fused._autocast_16() is None
+    assert fused.takes_16(torch.bfloat16, 'fp16_rows') and fused.takes_16(torch.float16, 'fp16_rows') and not fused.takes_16(torch.float32, 'fp16_rows')
+    assert fused.autocast_16('fp16_rows') is None
     fused.ENABLED['fp16_rows'] = False
     try:
-        assert fused._rows_dtype(torch.bfloat16) and not fused._rows_dtype(torch.float16)
+        assert fused.takes_16(torch.bfloat16, 'fp16_rows') and not fused.takes_16(torch.float16, 'fp16_rows')
     finally:
         fused.ENABLED['fp16_rows'] = True
     for b16, f16 in _vah.FUSED_F16_TWINS.items():
-        assert fused._sym(b16, torch.bfloat16) is getattr(lib, b16)
-        assert fused._sym(b16, torch.float16) is getattr(lib, f16)
+        assert _vah.sym(b16, torch.bfloat16) is getattr(lib, b16)
+        assert _vah.sym(b16, torch.float16) is getattr(lib, f16)
     norm = torch.nn.LayerNorm(8)
     x, z = torch.randn(2, 3, 8), torch.randn(2, 3, 8).half()
     t, h = fused.residual_ln(x, z, None, None, norm)

@@ -118,16 +118,16 @@ def test_f16_entry_checks_arguments_like_its_bf16_twin(name, build, cases):
 def test_host_picks_the_entry_by_type_cpu():
     import torch
     from vitadapter import fused
-    assert fused.ENABLED['fp16_linear'] is True and fused._linear_dtype() is None         # no autocast here
-    assert fused._linear_takes(torch.bfloat16) and fused._linear_takes(torch.float16) and not fused._linear_takes(torch.float32)
+    assert fused.ENABLED['fp16_linear'] is True and fused.autocast_16('fp16_linear') is None         # no autocast here
+    assert fused.takes_16(torch.bfloat16, 'fp16_linear') and fused.takes_16(torch.float16, 'fp16_linear') and not fused.takes_16(torch.float32, 'fp16_linear')
     fused.ENABLED['fp16_linear'] = False
     try:
-        assert fused._linear_takes(torch.bfloat16) and not fused._linear_takes(torch.float16)
+        assert fused.takes_16(torch.bfloat16, 'fp16_linear') and not fused.takes_16(torch.float16, 'fp16_linear')
     finally:
         fused.ENABLED['fp16_linear'] = True
     for b16, f16 in _vah.LINEAR_F16_TWINS.items():
-        assert fused._sym(b16, torch.bfloat16) is getattr(lib, b16)
-        assert fused._sym(b16, torch.float16) is getattr(lib, f16)
+        assert _vah.sym(b16, torch.bfloat16) is getattr(lib, b16)
+        assert _vah.sym(b16, torch.float16) is getattr(lib, f16)
     assert fused.gemm_bf16 is fused.gemm_16
     lin = torch.nn.Linear(8, 16)
     x = torch.randn(2, 3, 8)

@@ -169,11 +169,11 @@ def test_host_gates_cpu():
     assert fused.ENABLED['fp16_spm'] is True
     assert spm_nhwc.autocast_dtype() is None
     for b16, f16 in TWINS.items():
-        assert conv._sym(b16, torch.bfloat16) == (getattr(lib, b16), b16)
-        assert conv._sym(b16, torch.float16) == (getattr(lib, f16), f16)
-        assert spm_nhwc._sym(b16, torch.float16) is getattr(lib, f16)
-    with pytest.raises(AssertionError):
-        conv._sym('vah_conv_taps_nhwc_bf16', torch.float32)
+        assert (_vah.sym(b16, torch.bfloat16), _vah.sym(b16, torch.bfloat16).__name__) == (getattr(lib, b16), b16)
+        assert (_vah.sym(b16, torch.float16), _vah.sym(b16, torch.float16).__name__) == (getattr(lib, f16), f16)
+        assert _vah.sym(b16, torch.float16) is getattr(lib, f16)
+    with pytest.raises(ValueError):
+        _vah.sym('vah_conv_taps_nhwc_bf16', torch.float32)
     w = torch.randn(64, 16, 3, 3)
     for dtype in (torch.bfloat16, torch.float16):
         w9, wt9 = conv.forward_weight(w, dtype), conv.dgrad_weight(w, dtype)

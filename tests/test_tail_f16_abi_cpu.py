@@ -192,13 +192,13 @@ def test_host_gates_cpu():
     import torch
     from vitadapter import fused
     assert fused.ENABLED['fp16_tail'] is True
-    assert fused._tail_dtype() is None and fused.tail_dtype() is None
+    assert fused.autocast_16('fp16_tail') is None and fused.tail_dtype() is None
     assert fused._maps_dtype() == torch.bfloat16
     for b16, f16 in TWINS.items():
-        assert fused._sym(b16, torch.bfloat16) is getattr(lib, b16)
-        assert fused._sym(b16, torch.float16) is getattr(lib, f16)
+        assert _vah.sym(b16, torch.bfloat16) is getattr(lib, b16)
+        assert _vah.sym(b16, torch.float16) is getattr(lib, f16)
     for b16, f16 in _vah.FUSED_F16_TWINS.items():          # the row kernels' twins are still found
-        assert fused._sym(b16, torch.float16) is getattr(lib, f16)
+        assert _vah.sym(b16, torch.float16) is getattr(lib, f16)
     norm = torch.nn.BatchNorm2d(8)
     a = torch.randn(2, 8, 8, 8)
     assert not fused._bn_fusable(norm, a) and not fused.tail_takes_conv_bias(norm, a)

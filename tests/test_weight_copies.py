@@ -32,6 +32,28 @@ def test_copies_follow_data_writes_cpu():
     assert torch.equal(cp.get(p).float(), p.detach())
 
 
+def test_pair_core_permutation_is_not_taken_from_a_collected_module_cpu():
+    """_PairCoreCopies is keyed by id() of the two weights.  When a module is collected, another module's weights can
+    come to lie at the same addresses: the entry left under that key, permutation included, is the dead module's (one
+    head: 12 rows) and must not serve the new one (two heads: 24 rows in another order)."""
+    import weakref
+    cp = fused._PairCoreCopies()
+    a1, b1 = torch.nn.Linear(8, 8), torch.nn.Linear(8, 4)               # M = 1, L = 1, P = 4
+    _, _, perm1 = cp.get(a1, b1, 1)
+    a2, b2 = torch.nn.Linear(8, 16), torch.nn.Linear(8, 8)              # M = 2
+    dead = torch.nn.Parameter(torch.zeros(1))
+    ref = weakref.ref(dead)
+    del dead
+    assert ref() is None
+    cp.entries[(id(a2.weight), id(b2.weight))] = cp.entries[(id(a1.weight), id(b1.weight))][:4] + (ref,)
+    w, bias, perm = cp.get(a2, b2, 2)
+    want = torch.cat([torch.arange(0, 8), 16 + torch.arange(0, 4), torch.arange(8, 16), 16 + torch.arange(4, 8)])
+    assert torch.equal(perm[0], want) and torch.equal(perm[1][perm[0]], torch.arange(24))
+    assert w.shape == (24, 8) and torch.equal(w, torch.cat([a2.weight, b2.weight]).detach()[want].to(torch.bfloat16))
+    assert torch.equal(bias, torch.cat([a2.bias, b2.bias]).detach()[want])
+    assert cp.get(a2, b2, 2)[2] is perm and perm1[0].numel() == 12       # the module's own permutation is made once
+
+
 @pytest.mark.gpu
 def test_fused_linear_sees_data_writes_gpu():
     lin = torch.nn.Linear(64, 32).cuda()

@@ -39,8 +39,7 @@ def main():
     args = ap.parse_args()
     shapes = [(8192, 768), (43008, 768)] if len(args.dims) < 2 else [(args.dims[0], args.dims[1])]
     dt = torch.bfloat16 if args.dtype == 'bf16' else torch.float16
-    # the entry point of a kernel for the chosen type: the bf16 name or its fp16 twin
-    K = lambda name: getattr(L, name if dt == torch.bfloat16 else _vah.FUSED_F16_TWINS[name])
+    K = lambda name: _vah.sym(name, dt)       # the entry point of a kernel for the chosen type: the bf16 name or its fp16 twin
     st = torch.cuda.current_stream().cuda_stream
     d = 'cuda'
     for rows, C in shapes:

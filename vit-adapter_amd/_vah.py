@@ -23,156 +23,110 @@ if not os.path.exists(LIB_PATH):
 
 lib = ctypes.CDLL(LIB_PATH)
 
-_i64 = ctypes.c_int64
-_p = ctypes.c_void_p
+_int, _i64, _f, _p, _str, _pi64 = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_char_p,
+                                   ctypes.POINTER(ctypes.c_int64))
 
-lib.vah_abi_version.restype = ctypes.c_int
-lib.vah_last_error.restype = ctypes.c_char_p
-lib.vah_prof_enable.argtypes = [ctypes.c_int]
-lib.vah_prof_enable.restype = ctypes.c_int
-lib.vah_prof_filter.argtypes = [ctypes.c_char_p]
-lib.vah_prof_filter.restype = ctypes.c_int
-lib.vah_prof_report.argtypes = [ctypes.c_char_p, _i64]
-lib.vah_prof_report.restype = _i64
-for _sfx in ('f32', 'f64'):
-    _f = getattr(lib, 'vah_msda_forward_' + _sfx)
-    _f.argtypes = [_p] * 5 + [_i64] * 7 + [_p, _p]
-    _f.restype = ctypes.c_int
-    _b = getattr(lib, 'vah_msda_backward_' + _sfx)
-    _b.argtypes = [_p] * 6 + [_i64] * 7 + [_p] * 4
-    _b.restype = ctypes.c_int
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip.h declares, in the header's order, the fp16 twins
+# excepted: those take their parent's signature (F16_TWINS).  tests/test_binding_table_cpu.py holds each entry to its
+# prototype: a c_int where the library reads an int64_t is a garbage dimension inside a kernel.
+SIGNATURES = {
+    'vah_abi_version': (_int, []),
+    'vah_last_error': (_str, []),
+    'vah_msda_forward_f32': (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    'vah_msda_forward_f64': (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    'vah_msda_backward_f32': (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    'vah_msda_backward_f64': (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    'vah_msda_fused_supported': (_int, [_i64, _i64, _i64]),
+    'vah_msda_fused_forward': (_int, [_p, _int, _p, _p, _p, _p, _int, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    'vah_msda_fused_backward': (_int, [_p, _int, _p, _p, _p, _p, _int, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    'vah_msda_fused_forward_nref': (_int, [_p, _int, _p, _p, _p, _p, _int, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p,
+                                           _p]),
+    'vah_msda_fused_backward_nref': (_int, [_p, _int, _p, _p, _p, _p, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p,
+                                            _p]),
+    'vah_msda_win_ws_bytes': (_i64, [_i64, _i64]),
+    'vah_msda_fused_forward_win': (_int, [_p, _int, _p, _p, _p, _p, _int, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _int,
+                                          _p, _p]),
+    'vah_msda_tile_ws_bytes': (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    'vah_msda_backward_tiled_f32': (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p]),
+    'vah_msda_fused_backward_tiled': (_int, [_p, _int, _p, _p, _p, _p, _int, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p,
+                                             _int, _p, _p, _int, _i64, _i64, _p, _i64, _p]),
+    'vah_msda_fused_backward_tiled_nref': (_int, [_p, _int, _p, _p, _p, _p, _int, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64,
+                                                  _i64, _p, _int, _p, _p, _int, _i64, _i64, _p, _i64, _p]),
+    'vah_attn_padded_len': (_i64, [_i64]),
+    'vah_attn_fwd_bf16': (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _f, _p, _p, _i64, _p, _p]),
+    'vah_attn_win_fwd_bf16': (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _f, _p, _p, _i64, _p, _p]),
+    'vah_attn_bwd_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'vah_attn_bwd_bf16': (_int, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _f, _p, _p, _p, _p, _i64, _i64, _p]),
+    'vah_attn_bias_fwd_bf16': (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _f, _p, _i64, _p, _i64, _p, _p]),
+    'vah_attn_bias_bwd_bf16': (_int, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _f, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64,
+                                      _p]),
+    'vah_relpos_bias_build': (_int, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    'vah_relpos_bias_grad_ws_floats': (_i64, [_i64, _i64]),
+    'vah_relpos_bias_grad': (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    'vah_attn_win_bwd_bf16': (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _f, _p, _p, _p, _p, _i64, _p]),
+    'vah_reduce_ws_floats': (_i64, [_i64]),
+    'vah_layernorm_fwd_f32_bf16': (_int, [_p, _p, _p, _i64, _i64, _f, _p, _p, _p, _p]),
+    'vah_layernorm_bwd_f32_bf16': (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    'vah_residual_layernorm_fwd': (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _f, _p, _p, _p, _p, _p]),
+    'vah_residual_layernorm_bwd': (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    'vah_layernorm_dual_fwd': (_int, [_p, _p, _p, _p, _p, _i64, _i64, _f, _p, _p, _p, _p, _p]),
+    'vah_layernorm_dual_bwd': (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    'vah_colsum_bf16': (_int, [_p, _i64, _i64, _p, _p, _p]),
+    'vah_colsum_bf16_partials': (_int, [_p, _i64, _i64, _p, _pi64, _p]),
+    'vah_residual_layernorm_bwd_bsum': (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _pi64, _p]),
+    'vah_scale_residual_bwd_bsum': (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _pi64, _p]),
+    'vah_gelu_bwd_bsum_bf16': (_int, [_p, _p, _i64, _i64, _p, _p, _pi64, _p]),
+    'vah_colsum_f32': (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    'vah_bn_tail_ws_floats': (_i64, [_i64]),
+    'vah_bn_tail_supported': (_int, [_i64, _i64, _i64, _i64, _int, _int]),
+    'vah_bn_tail_stats': (_int, [_p, _int, _p, _int, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    'vah_bn_tail_apply': (_int, [_p, _int, _p, _int, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _int, _p]),
+    'vah_bn_tail_bwd_stats': (_int, [_p, _int, _p, _int, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _int, _p, _p, _p]),
+    'vah_bn_tail_bwd_apply': (_int, [_p, _int, _p, _int, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _int, _p, _p, _p, _p, _p,
+                                     _p]),
+    'vah_bn_finalize_stats': (_int, [_p, _i64, _f, _f, _p, _p, _p, _p, _p]),
+    'vah_pixel_shuffle2_bf16': (_int, [_p, _i64, _i64, _i64, _i64, _p, _int, _p, _p]),
+    'vah_transpose_tokens': (_int, [_p, _i64, _i64, _i64, _i64, _i64, _p, _int, _int, _p, _p]),
+    'vah_maxpool3s2_fwd_bf16': (_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
+    'vah_maxpool3s2_bwd_bf16': (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
+    'vah_conv_taps_nhwc_bf16': (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _int, _p, _p, _int, _p, _i64, _i64, _i64, _i64, _int, _int, _int, _p]),
+    'vah_conv3x3_dgrad_nhwc_bf16': (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _int, _p, _i64, _i64, _p]),
+    'vah_conv3x3_wgrad_ws_floats': (_i64, [_i64, _i64]),
+    'vah_conv3x3_wgrad_nhwc_bf16': (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _int, _p, _i64, _p, _p]),
+    'vah_image_to_nhwc16_bf16': (_int, [_p, _i64, _i64, _i64, _p, _p]),
+    'vah_patchify_bf16': (_int, [_p, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    'vah_bn_nhwc_ws_floats': (_i64, [_i64]),
+    'vah_bn_nhwc_stats': (_int, [_p, _i64, _i64, _p, _p, _p]),
+    'vah_bn_nhwc_apply': (_int, [_p, _i64, _i64, _p, _p, _p, _p, _int, _p, _p]),
+    'vah_bn_nhwc_bwd_stats': (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _p]),
+    'vah_bn_nhwc_bwd_apply': (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _p, _p]),
+    'vah_maxpool3s2_nhwc_fwd_bf16': (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    'vah_maxpool3s2_nhwc_bwd_bf16': (_int, [_p, _p, _i64, _i64, _i64, _i64, _p, _p]),
+    'vah_gemm_set_tuning': (_int, [_int, _int]),
+    'vah_gemm_bf16': (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _int, _int, _p, _int, _p, _i64, _p]),
+    'vah_gemm_bf16_fin': (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _int, _p, _i64, _p, _i64, _i64, _p, _p]),
+    'vah_gemm_library_version': (_i64, []),
+    'vah_gemm_rejected_candidates': (_i64, []),
+    'vah_gemm_table_dump': (_i64, [_str, _i64]),
+    'vah_gemm_table_load': (_int, [_str]),
+    'vah_scale_residual_fwd': (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    'vah_scale_residual_bwd': (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
+    'vah_dwconv3x3_tokens_bf16': (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _int, _p, _p]),
+    'vah_dwconv3x3_tokens_wgrad_bf16': (_int, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    'vah_prof_enable': (_int, [_int]),
+    'vah_prof_filter': (_int, [_str]),
+    'vah_prof_report': (_i64, [_str, _i64]),
+}
 
-lib.vah_attn_padded_len.argtypes = [_i64]
-lib.vah_attn_padded_len.restype = _i64
-lib.vah_attn_fwd_bf16.argtypes = [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _p, _p, _i64, _p, _p]
-lib.vah_attn_fwd_bf16.restype = ctypes.c_int
-
-lib.vah_attn_bwd_workspace_bytes.argtypes = [_i64, _i64, _i64]
-lib.vah_attn_bwd_workspace_bytes.restype = _i64
-lib.vah_attn_bwd_bf16.argtypes = ([_p, _p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, ctypes.c_float]
-                                  + [_p] * 4 + [_i64, _i64, _p])
-lib.vah_attn_bwd_bf16.restype = ctypes.c_int
-
-lib.vah_attn_bias_fwd_bf16.argtypes = [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _p, _i64, _p, _i64, _p, _p]
-lib.vah_attn_bias_bwd_bf16.argtypes = ([_p, _p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, ctypes.c_float, _p, _p, _i64, _p, _p,
-                                        _p, _p, _p, _i64, _i64, _p])
-lib.vah_relpos_bias_build.argtypes = [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]
-lib.vah_relpos_bias_grad_ws_floats.argtypes = [_i64, _i64]
-lib.vah_relpos_bias_grad_ws_floats.restype = _i64
-lib.vah_relpos_bias_grad.argtypes = [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p]
-lib.vah_attn_win_fwd_bf16.argtypes = [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _p, _p, _i64, _p, _p]
-lib.vah_attn_win_fwd_bf16.restype = ctypes.c_int
-lib.vah_attn_win_bwd_bf16.argtypes = [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, ctypes.c_float,
-                                      _p, _p, _p, _p, _i64, _p]
-lib.vah_attn_win_bwd_bf16.restype = ctypes.c_int
-# fp16 twins of the attention entry points: the bf16 signatures with the element type of the 16-bit operands changed
-for _n in ('vah_attn_fwd', 'vah_attn_bwd', 'vah_attn_win_fwd', 'vah_attn_win_bwd', 'vah_attn_bias_fwd', 'vah_attn_bias_bwd'):
-    _b16, _f16 = getattr(lib, _n + '_bf16'), getattr(lib, _n + '_f16')
-    _f16.argtypes, _f16.restype = _b16.argtypes, ctypes.c_int
-for _n in ('vah_relpos_bias_build', 'vah_relpos_bias_grad'):
-    getattr(lib, _n + '_f16').argtypes, getattr(lib, _n + '_f16').restype = getattr(lib, _n).argtypes, ctypes.c_int
-_ci = ctypes.c_int
-lib.vah_msda_fused_supported.argtypes = [_i64, _i64, _i64]
-lib.vah_msda_fused_supported.restype = ctypes.c_int
-lib.vah_msda_fused_forward.argtypes = [_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p, _i64] + [_i64] * 7 + [_p, _p]
-lib.vah_msda_fused_forward.restype = ctypes.c_int
-lib.vah_msda_fused_backward.argtypes = [_p, _ci, _p, _p, _p, _p, _ci, _p, _i64, _p] + [_i64] * 7 + [_p] * 4
-lib.vah_msda_fused_backward.restype = ctypes.c_int
-lib.vah_msda_fused_forward_win.argtypes = [_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p] + [_i64] * 7 + [_p, _i64, _ci, _p, _p]
-lib.vah_msda_win_ws_bytes.argtypes = [_i64, _i64]
-lib.vah_msda_win_ws_bytes.restype = _i64
-lib.vah_msda_fused_forward_win.restype = ctypes.c_int
-lib.vah_msda_tile_ws_bytes.argtypes = [_i64] * 6
-lib.vah_msda_tile_ws_bytes.restype = _i64
-lib.vah_msda_backward_tiled_f32.argtypes = [_p] * 6 + [_i64] * 7 + [_p] * 3 + [_p, _i64, _p]
-lib.vah_msda_backward_tiled_f32.restype = ctypes.c_int
-lib.vah_msda_fused_backward_tiled.argtypes = ([_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p, _i64, _p] + [_i64] * 7
-                                              + [_p, _ci, _p, _p, _ci, _i64, _i64, _p, _i64, _p])
-lib.vah_msda_fused_backward_tiled.restype = ctypes.c_int
-# reference points per image: one more int64 (ref_batch) directly after ref_levels
-lib.vah_msda_fused_forward_nref.argtypes = [_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p, _i64, _i64] + [_i64] * 7 + [_p, _p]
-lib.vah_msda_fused_forward_nref.restype = ctypes.c_int
-lib.vah_msda_fused_backward_nref.argtypes = [_p, _ci, _p, _p, _p, _p, _ci, _p, _i64, _i64, _p] + [_i64] * 7 + [_p] * 4
-lib.vah_msda_fused_backward_nref.restype = ctypes.c_int
-lib.vah_msda_fused_backward_tiled_nref.argtypes = ([_p, _ci, _p, _p, _p, _p, _ci, _i64, _i64, _p, _i64, _i64, _p] + [_i64] * 7
-                                                   + [_p, _ci, _p, _p, _ci, _i64, _i64, _p, _i64, _p])
-lib.vah_msda_fused_backward_tiled_nref.restype = ctypes.c_int
-_f = ctypes.c_float
-lib.vah_layernorm_fwd_f32_bf16.argtypes = [_p, _p, _p, _i64, _i64, _f, _p, _p, _p, _p]
-lib.vah_layernorm_bwd_f32_bf16.argtypes = [_p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]
-lib.vah_colsum_bf16.argtypes = [_p, _i64, _i64, _p, _p, _p]
-lib.vah_layernorm_dual_fwd.argtypes = [_p, _p, _p, _p, _p, _i64, _i64, _f, _p, _p, _p, _p, _p]
-lib.vah_layernorm_dual_bwd.argtypes = [_p] * 8 + [_i64, _i64, _p, _p, _p, _p]
-lib.vah_colsum_f32.argtypes = [_p, _i64, _i64, _i64, _i64, _p, _p, _p]
-lib.vah_residual_layernorm_fwd.argtypes = [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, ctypes.c_float, _p, _p, _p, _p, _p]
-lib.vah_residual_layernorm_bwd.argtypes = [_p] * 9 + [_i64] * 3 + [_p] * 7
-_int = ctypes.c_int
-lib.vah_gemm_set_tuning.argtypes = [_int, _int]
-lib.vah_gemm_bf16.argtypes = [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _int, _int, _p, _int,
-                              _p, _i64, _p]
-lib.vah_gemm_bf16_fin.argtypes = [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _int, _p, _i64, _p, _i64, _i64,
-                                  _p, _p]
-lib.vah_colsum_bf16_partials.argtypes = [_p, _i64, _i64, _p, ctypes.POINTER(_i64), _p]
-# the producers of a Linear's dY that carry its bias-gradient partials (fp16 twins: LINEAR_F16_TWINS)
-lib.vah_residual_layernorm_bwd_bsum.argtypes = [_p] * 9 + [_i64] * 3 + [_p] * 6 + [_p, ctypes.POINTER(_i64), _p]
-lib.vah_scale_residual_bwd_bsum.argtypes = [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, ctypes.POINTER(_i64), _p]
-lib.vah_gelu_bwd_bsum_bf16.argtypes = [_p, _p, _i64, _i64, _p, _p, ctypes.POINTER(_i64), _p]
-for _n in ('vah_residual_layernorm_bwd_bsum', 'vah_scale_residual_bwd_bsum', 'vah_gelu_bwd_bsum_bf16'):
-    getattr(lib, _n).restype = ctypes.c_int
-lib.vah_gemm_table_dump.argtypes = [ctypes.c_char_p, _i64]
-lib.vah_gemm_table_dump.restype = _i64
-lib.vah_gemm_table_load.argtypes = [ctypes.c_char_p]
-lib.vah_gemm_library_version.argtypes = []
-lib.vah_gemm_library_version.restype = _i64
-lib.vah_gemm_rejected_candidates.argtypes = []
-lib.vah_gemm_rejected_candidates.restype = _i64
-_tail_in = [_p, _int, _p, _int, _p, _int, _i64, _i64, _i64, _i64]
-lib.vah_bn_tail_ws_floats.argtypes = [_i64]
-lib.vah_bn_tail_ws_floats.restype = _i64
-lib.vah_bn_tail_supported.argtypes = [_i64, _i64, _i64, _i64, _int, _int]
-lib.vah_bn_tail_supported.restype = ctypes.c_int
-lib.vah_bn_tail_stats.argtypes = _tail_in + [_p, _p, _p, _p]
-lib.vah_bn_tail_apply.argtypes = _tail_in + [_p, _p, _p, _p, _int, _p, _p, _int, _p]
-lib.vah_bn_tail_bwd_stats.argtypes = _tail_in + [_p, _p, _p, _p, _int, _p, _p, _int, _p, _p, _p]
-lib.vah_bn_tail_bwd_apply.argtypes = _tail_in + [_p, _p, _p, _p, _int, _p, _p, _int, _p, _p, _p, _p, _p, _p]
-lib.vah_bn_finalize_stats.argtypes = [_p, _i64, _f, _f, _p, _p, _p, _p, _p]
-lib.vah_maxpool3s2_fwd_bf16.argtypes = [_p, _i64, _i64, _i64, _p, _p, _p]
-lib.vah_maxpool3s2_bwd_bf16.argtypes = [_p, _p, _i64, _i64, _i64, _p, _p]
-lib.vah_conv_taps_nhwc_bf16.argtypes = [_p, _i64, _i64, _i64, _i64, _p, _i64, _int, _p, _p, _int, _p, _i64, _i64, _i64, _i64, _int, _int,
-                                        _int, _p]
-lib.vah_conv3x3_dgrad_nhwc_bf16.argtypes = [_p, _i64, _i64, _i64, _i64, _p, _i64, _int, _p, _i64, _i64, _p]
-lib.vah_conv3x3_wgrad_ws_floats.argtypes = [_i64, _i64]
-lib.vah_conv3x3_wgrad_ws_floats.restype = _i64
-lib.vah_conv3x3_wgrad_nhwc_bf16.argtypes = [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _int, _p, _i64, _p, _p]
-lib.vah_image_to_nhwc16_bf16.argtypes = [_p, _i64, _i64, _i64, _p, _p]
-lib.vah_patchify_bf16.argtypes = [_p, _i64, _i64, _i64, _i64, _i64, _p, _p]
-lib.vah_bn_nhwc_ws_floats.argtypes = [_i64]
-lib.vah_bn_nhwc_ws_floats.restype = _i64
-lib.vah_bn_nhwc_stats.argtypes = [_p, _i64, _i64, _p, _p, _p]
-lib.vah_bn_nhwc_apply.argtypes = [_p, _i64, _i64, _p, _p, _p, _p, _int, _p, _p]
-lib.vah_bn_nhwc_bwd_stats.argtypes = [_p, _p, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _p]
-lib.vah_bn_nhwc_bwd_apply.argtypes = [_p, _p, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _p, _p]
-lib.vah_maxpool3s2_nhwc_fwd_bf16.argtypes = [_p, _i64, _i64, _i64, _i64, _p, _p, _p]
-lib.vah_maxpool3s2_nhwc_bwd_bf16.argtypes = [_p, _p, _i64, _i64, _i64, _i64, _p, _p]
-lib.vah_pixel_shuffle2_bf16.argtypes = [_p, _i64, _i64, _i64, _i64, _p, _int, _p, _p]
-lib.vah_transpose_tokens.argtypes = [_p, _i64, _i64, _i64, _i64, _i64, _p, _int, _int, _p, _p]
-lib.vah_reduce_ws_floats.argtypes = [_i64]
-lib.vah_reduce_ws_floats.restype = _i64
-lib.vah_scale_residual_fwd.argtypes = [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p]
-lib.vah_scale_residual_bwd.argtypes = [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p]
-lib.vah_dwconv3x3_tokens_bf16.argtypes = [_p, _p, _p, _i64, _i64, _i64, _i64, ctypes.c_int, _p, _p]
-lib.vah_dwconv3x3_tokens_wgrad_bf16.argtypes = [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]
-for _n in ('vah_layernorm_fwd_f32_bf16', 'vah_layernorm_bwd_f32_bf16', 'vah_scale_residual_fwd',
-           'vah_scale_residual_bwd', 'vah_dwconv3x3_tokens_bf16', 'vah_dwconv3x3_tokens_wgrad_bf16',
-           'vah_colsum_bf16', 'vah_colsum_f32', 'vah_layernorm_dual_fwd', 'vah_layernorm_dual_bwd', 'vah_residual_layernorm_fwd', 'vah_residual_layernorm_bwd', 'vah_gemm_set_tuning', 'vah_gemm_bf16', 'vah_gemm_bf16_fin', 'vah_colsum_bf16_partials', 'vah_gemm_table_load',
-           'vah_bn_tail_stats', 'vah_bn_tail_apply', 'vah_bn_tail_bwd_stats', 'vah_bn_tail_bwd_apply',
-           'vah_bn_finalize_stats', 'vah_transpose_tokens', 'vah_maxpool3s2_fwd_bf16', 'vah_maxpool3s2_bwd_bf16',
-           'vah_conv_taps_nhwc_bf16', 'vah_conv3x3_dgrad_nhwc_bf16', 'vah_conv3x3_wgrad_nhwc_bf16',
-           'vah_pixel_shuffle2_bf16', 'vah_patchify_bf16', 'vah_attn_bias_fwd_bf16', 'vah_attn_bias_bwd_bf16', 'vah_relpos_bias_build', 'vah_relpos_bias_grad', 'vah_image_to_nhwc16_bf16', 'vah_bn_nhwc_stats', 'vah_bn_nhwc_apply', 'vah_bn_nhwc_bwd_stats', 'vah_bn_nhwc_bwd_apply',
-           'vah_maxpool3s2_nhwc_fwd_bf16', 'vah_maxpool3s2_nhwc_bwd_bf16'):
-    getattr(lib, _n).restype = ctypes.c_int
-
-# fp16 twins of the row-streaming kernels of csrc/fused_ops.hip: the bf16 signatures, _Float16 in the 16-bit operands
+# The fp16 twins, bf16 spelling -> fp16 name: the bf16 signature with _Float16 in the 16-bit operands.  Five groups:
+# the attention / relative-position kernels (csrc/attn_*.hip, csrc/relpos.hip)
+ATTN_F16_TWINS = {
+    'vah_attn_fwd_bf16': 'vah_attn_fwd_f16', 'vah_attn_bwd_bf16': 'vah_attn_bwd_f16',
+    'vah_attn_win_fwd_bf16': 'vah_attn_win_fwd_f16', 'vah_attn_win_bwd_bf16': 'vah_attn_win_bwd_f16',
+    'vah_attn_bias_fwd_bf16': 'vah_attn_bias_fwd_f16', 'vah_attn_bias_bwd_bf16': 'vah_attn_bias_bwd_f16',
+    'vah_relpos_bias_build': 'vah_relpos_bias_build_f16', 'vah_relpos_bias_grad': 'vah_relpos_bias_grad_f16',
+}
+# the row-streaming kernels of csrc/fused_ops.hip
 FUSED_F16_TWINS = {
     'vah_layernorm_fwd_f32_bf16': 'vah_layernorm_fwd_f32_f16', 'vah_layernorm_bwd_f32_bf16': 'vah_layernorm_bwd_f32_f16',
     'vah_residual_layernorm_fwd': 'vah_residual_layernorm_fwd_f16', 'vah_residual_layernorm_bwd': 'vah_residual_layernorm_bwd_f16',
@@ -180,11 +134,8 @@ FUSED_F16_TWINS = {
     'vah_scale_residual_fwd': 'vah_scale_residual_fwd_f16', 'vah_scale_residual_bwd': 'vah_scale_residual_bwd_f16',
     'vah_dwconv3x3_tokens_bf16': 'vah_dwconv3x3_tokens_f16', 'vah_dwconv3x3_tokens_wgrad_bf16': 'vah_dwconv3x3_tokens_wgrad_f16',
 }
-for _b16, _f16 in FUSED_F16_TWINS.items():
-    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
-
-# fp16 twins of the Linear path: the GEMM dispatcher (csrc/gemm.hip) and its satellites in csrc/fused_ops.hip - column
-# sums, GELU backward, and the `_bsum` forms of the two residual backward kernels (named after their `_f16` parents)
+# the Linear path: the GEMM dispatcher (csrc/gemm.hip) and its satellites in csrc/fused_ops.hip - column sums, GELU
+# backward, and the `_bsum` forms of the two residual backward kernels (named after their `_f16` parents)
 LINEAR_F16_TWINS = {
     'vah_gemm_bf16': 'vah_gemm_f16', 'vah_gemm_bf16_fin': 'vah_gemm_f16_fin',
     'vah_colsum_bf16': 'vah_colsum_f16', 'vah_colsum_bf16_partials': 'vah_colsum_f16_partials',
@@ -192,11 +143,7 @@ LINEAR_F16_TWINS = {
     'vah_residual_layernorm_bwd_bsum': 'vah_residual_layernorm_bwd_f16_bsum',
     'vah_scale_residual_bwd_bsum': 'vah_scale_residual_bwd_f16_bsum',
 }
-for _b16, _f16 in LINEAR_F16_TWINS.items():
-    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
-
-# fp16 twins of the SpatialPriorModule kernels (csrc/conv.hip, csrc/spm_nhwc.hip); the workspace queries and
-# vah_bn_finalize_stats are shared
+# the SpatialPriorModule kernels (csrc/conv.hip, csrc/spm_nhwc.hip); the workspace queries and vah_bn_finalize_stats are shared
 SPM_F16_TWINS = {
     'vah_conv_taps_nhwc_bf16': 'vah_conv_taps_nhwc_f16', 'vah_conv3x3_dgrad_nhwc_bf16': 'vah_conv3x3_dgrad_nhwc_f16',
     'vah_conv3x3_wgrad_nhwc_bf16': 'vah_conv3x3_wgrad_nhwc_f16', 'vah_image_to_nhwc16_bf16': 'vah_image_to_nhwc16_f16',
@@ -204,10 +151,7 @@ SPM_F16_TWINS = {
     'vah_bn_nhwc_bwd_stats': 'vah_bn_nhwc_bwd_stats_f16', 'vah_bn_nhwc_bwd_apply': 'vah_bn_nhwc_bwd_apply_f16',
     'vah_maxpool3s2_nhwc_fwd_bf16': 'vah_maxpool3s2_nhwc_fwd_f16', 'vah_maxpool3s2_nhwc_bwd_bf16': 'vah_maxpool3s2_nhwc_bwd_f16',
 }
-for _b16, _f16 in SPM_F16_TWINS.items():
-    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
-
-# fp16 twins of the output-tail kernels (csrc/tail_ops.hip); in the twins the `*_bf16` flags read "fp16 (1) or fp32 (0)".
+# the output-tail kernels (csrc/tail_ops.hip); in the twins the `*_bf16` flags read "fp16 (1) or fp32 (0)".
 # vah_bn_tail_supported, vah_bn_tail_ws_floats and vah_bn_finalize_stats are shared
 TAIL_F16_TWINS = {
     'vah_bn_tail_stats': 'vah_bn_tail_stats_f16', 'vah_bn_tail_apply': 'vah_bn_tail_apply_f16',
@@ -215,48 +159,19 @@ TAIL_F16_TWINS = {
     'vah_transpose_tokens': 'vah_transpose_tokens_f16', 'vah_maxpool3s2_fwd_bf16': 'vah_maxpool3s2_fwd_f16',
     'vah_maxpool3s2_bwd_bf16': 'vah_maxpool3s2_bwd_f16', 'vah_pixel_shuffle2_bf16': 'vah_pixel_shuffle2_f16',
 }
-for _b16, _f16 in TAIL_F16_TWINS.items():
-    getattr(lib, _f16).argtypes, getattr(lib, _f16).restype = getattr(lib, _b16).argtypes, ctypes.c_int
+F16_TWINS = {**ATTN_F16_TWINS, **FUSED_F16_TWINS, **LINEAR_F16_TWINS, **SPM_F16_TWINS, **TAIL_F16_TWINS}
+
+# every symbol include/vitadapter_hip.h declares (checked by tests/test_capi_symbols.py): none without a signature
+EXPORTS = tuple(SIGNATURES) + tuple(F16_TWINS.values())
+
+_PARENT = {f16: b16 for b16, f16 in F16_TWINS.items()}
+for _name in EXPORTS:
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = SIGNATURES[_PARENT.get(_name, _name)]        # a twin: its parent's signature
 
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))
-
-# every symbol include/vitadapter_hip.h declares (checked by tests/test_capi_symbols.py)
-EXPORTS = (
-    'vah_abi_version', 'vah_last_error', 'vah_prof_enable', 'vah_prof_filter', 'vah_prof_report',
-    'vah_msda_forward_f32', 'vah_msda_forward_f64',
-    'vah_msda_backward_f32', 'vah_msda_backward_f64',
-    'vah_msda_fused_supported', 'vah_msda_fused_forward', 'vah_msda_fused_backward',
-    'vah_msda_fused_forward_win', 'vah_msda_win_ws_bytes', 'vah_msda_tile_ws_bytes', 'vah_msda_backward_tiled_f32', 'vah_msda_fused_backward_tiled',
-    'vah_msda_fused_forward_nref', 'vah_msda_fused_backward_nref', 'vah_msda_fused_backward_tiled_nref',
-    'vah_pixel_shuffle2_bf16', 'vah_patchify_bf16', 'vah_attn_bias_fwd_bf16', 'vah_attn_bias_bwd_bf16', 'vah_relpos_bias_build', 'vah_relpos_bias_grad_ws_floats',
-    'vah_relpos_bias_grad', 'vah_attn_padded_len', 'vah_attn_fwd_bf16', 'vah_attn_bwd_workspace_bytes', 'vah_attn_bwd_bf16',
-    'vah_attn_win_fwd_bf16', 'vah_attn_win_bwd_bf16',
-    'vah_attn_fwd_f16', 'vah_attn_bwd_f16', 'vah_attn_win_fwd_f16', 'vah_attn_win_bwd_f16', 'vah_attn_bias_fwd_f16',
-    'vah_attn_bias_bwd_f16', 'vah_relpos_bias_build_f16', 'vah_relpos_bias_grad_f16',
-    'vah_reduce_ws_floats', 'vah_layernorm_fwd_f32_bf16', 'vah_layernorm_bwd_f32_bf16', 'vah_scale_residual_fwd',
-    'vah_scale_residual_bwd', 'vah_dwconv3x3_tokens_bf16', 'vah_dwconv3x3_tokens_wgrad_bf16', 'vah_colsum_bf16', 'vah_colsum_f32',
-    'vah_layernorm_dual_fwd', 'vah_layernorm_dual_bwd',
-    'vah_residual_layernorm_fwd', 'vah_residual_layernorm_bwd',
-    'vah_layernorm_fwd_f32_f16', 'vah_layernorm_bwd_f32_f16', 'vah_residual_layernorm_fwd_f16', 'vah_residual_layernorm_bwd_f16',
-    'vah_layernorm_dual_fwd_f16', 'vah_layernorm_dual_bwd_f16', 'vah_scale_residual_fwd_f16', 'vah_scale_residual_bwd_f16',
-    'vah_dwconv3x3_tokens_f16', 'vah_dwconv3x3_tokens_wgrad_f16',
-    'vah_residual_layernorm_bwd_bsum', 'vah_scale_residual_bwd_bsum', 'vah_gelu_bwd_bsum_bf16',
-    'vah_gemm_set_tuning', 'vah_gemm_bf16', 'vah_gemm_bf16_fin', 'vah_colsum_bf16_partials', 'vah_gemm_table_dump', 'vah_gemm_table_load', 'vah_gemm_library_version', 'vah_gemm_rejected_candidates',
-    'vah_gemm_f16', 'vah_gemm_f16_fin', 'vah_colsum_f16', 'vah_colsum_f16_partials', 'vah_gelu_bwd_bsum_f16',
-    'vah_residual_layernorm_bwd_f16_bsum', 'vah_scale_residual_bwd_f16_bsum',
-    'vah_bn_tail_ws_floats', 'vah_bn_tail_supported', 'vah_bn_tail_stats', 'vah_bn_tail_apply', 'vah_bn_tail_bwd_stats', 'vah_bn_tail_bwd_apply',
-    'vah_bn_finalize_stats', 'vah_transpose_tokens', 'vah_maxpool3s2_fwd_bf16', 'vah_maxpool3s2_bwd_bf16',
-    'vah_image_to_nhwc16_bf16', 'vah_bn_nhwc_ws_floats', 'vah_bn_nhwc_stats', 'vah_bn_nhwc_apply', 'vah_bn_nhwc_bwd_stats',
-    'vah_bn_nhwc_bwd_apply', 'vah_maxpool3s2_nhwc_fwd_bf16', 'vah_maxpool3s2_nhwc_bwd_bf16',
-    'vah_conv_taps_nhwc_bf16', 'vah_conv3x3_dgrad_nhwc_bf16', 'vah_conv3x3_wgrad_ws_floats', 'vah_conv3x3_wgrad_nhwc_bf16',
-    'vah_conv_taps_nhwc_f16', 'vah_conv3x3_dgrad_nhwc_f16', 'vah_conv3x3_wgrad_nhwc_f16', 'vah_image_to_nhwc16_f16',
-    'vah_bn_nhwc_stats_f16', 'vah_bn_nhwc_apply_f16', 'vah_bn_nhwc_bwd_stats_f16', 'vah_bn_nhwc_bwd_apply_f16',
-    'vah_maxpool3s2_nhwc_fwd_f16', 'vah_maxpool3s2_nhwc_bwd_f16',
-    'vah_bn_tail_stats_f16', 'vah_bn_tail_apply_f16', 'vah_bn_tail_bwd_stats_f16', 'vah_bn_tail_bwd_apply_f16',
-    'vah_transpose_tokens_f16', 'vah_maxpool3s2_fwd_f16', 'vah_maxpool3s2_bwd_f16', 'vah_pixel_shuffle2_f16',
-)
 
 
 class _NoSwitch:
@@ -298,6 +213,24 @@ def check(rc, what):
     if rc != 0:
         msg = lib.vah_last_error().decode('utf-8', 'replace')
         raise RuntimeError('%s failed (code %d): %s' % (what, rc, msg))
+
+
+_SYM = {(b16, torch.bfloat16): getattr(lib, b16) for b16 in SIGNATURES}
+_SYM.update(((b16, torch.float16), getattr(lib, f16)) for b16, f16 in F16_TWINS.items())
+
+
+def sym(name, dtype):
+    """The entry point ``name`` (its bf16 spelling) for 16-bit operands of ``dtype``: itself (bf16) or its fp16 twin."""
+    try:
+        return _SYM[name, dtype]
+    except KeyError:
+        raise ValueError('no entry point %s for %s operands' % (name, dtype)) from None
+
+
+def call(name, dtype, *args):
+    """sym(name, dtype)(*args), a non-zero return code raised under the name of the symbol that ran."""
+    fn = sym(name, dtype)
+    check(fn(*args), fn.__name__)
 
 
 def prof_enable(on, prefix=''):

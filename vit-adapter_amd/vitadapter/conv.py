@@ -15,24 +15,14 @@ def _stream(t):
     return _vah.raw_stream(t.device)
 
 
-def _sym(name, dtype):
-    """(entry point, its name) for 16-bit operands of ``dtype``: ``name`` (the bf16 spelling) or its `_f16` twin."""
-    if dtype != torch.bfloat16:
-        assert dtype == torch.float16, dtype
-        name = _vah.SPM_F16_TWINS[name]
-    return getattr(_vah.lib, name), name
-
-
 def _taps(x, w, taps, S, out, ny, nx, OS, oy0, ox0):
     N, IH, IW, Cin = x.shape
     Cout, T = w.shape[0], len(taps)
     ty = (ctypes.c_int * T)(*[t[0] for t in taps])
     tx = (ctypes.c_int * T)(*[t[1] for t in taps])
-    fn, call = _sym('vah_conv_taps_nhwc_bf16', x.dtype)
     with _vah.on(x.device):
-        rc = fn(x.data_ptr(), N, IH, IW, Cin, w.data_ptr(), Cout, T, ty, tx, S, out.data_ptr(), ny, nx, out.shape[1],
-                out.shape[2], OS, oy0, ox0, _stream(x))
-    _vah.check(rc, call)
+        _vah.call('vah_conv_taps_nhwc_bf16', x.dtype, x.data_ptr(), N, IH, IW, Cin, w.data_ptr(), Cout, T, ty, tx, S, out.data_ptr(), ny, nx,
+                  out.shape[1], out.shape[2], OS, oy0, ox0, _stream(x))
 
 
 def forward_weight(weight, dtype=torch.bfloat16):
@@ -63,10 +53,9 @@ def conv3x3_input_grad(gy, wt9, stride, in_hw):
     cin = wt9.shape[0]
     assert wt9.dtype == gy.dtype
     gx = torch.empty((N, H, W, cin), dtype=gy.dtype, device=gy.device)
-    fn, call = _sym('vah_conv3x3_dgrad_nhwc_bf16', gy.dtype)
     with _vah.on(gy.device):
-        rc = fn(gy.data_ptr(), N, OH, OW, cout, wt9.data_ptr(), cin, stride, gx.data_ptr(), H, W, _stream(gy))
-    _vah.check(rc, call)
+        _vah.call('vah_conv3x3_dgrad_nhwc_bf16', gy.dtype, gy.data_ptr(), N, OH, OW, cout, wt9.data_ptr(), cin, stride, gx.data_ptr(), H, W,
+                  _stream(gy))
     return gx
 
 
@@ -79,8 +68,7 @@ def conv3x3_weight_grad(x, gy, stride):
     ws = torch.empty((nws,), dtype=torch.float32, device=x.device)
     dw = torch.empty((cout, 3, 3, cin), dtype=torch.float32, device=x.device)
     assert gy.dtype == x.dtype
-    fn, call = _sym('vah_conv3x3_wgrad_nhwc_bf16', x.dtype)
     with _vah.on(x.device):
-        rc = fn(x.data_ptr(), N, H, W, cin, gy.data_ptr(), OH, OW, cout, stride, ws.data_ptr(), nws, dw.data_ptr(), _stream(x))
-    _vah.check(rc, call)
+        _vah.call('vah_conv3x3_wgrad_nhwc_bf16', x.dtype, x.data_ptr(), N, H, W, cin, gy.data_ptr(), OH, OW, cout, stride, ws.data_ptr(), nws,
+                  dw.data_ptr(), _stream(x))
     return dw

@@ -50,59 +50,29 @@ def _bf16_autocast():
     return torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16
 
 
-def _linear_dtype():
-    """The 16-bit type the Linear path (GEMM dispatcher, weight copies, GELU backward, bias partials) runs in under the
-    active autocast: torch.bfloat16, torch.float16, or None (no autocast, another autocast type, or fp16 with its switch
-    off: VAH_FUSED_DISABLE=fp16_linear, torch's library calls under fp16 autocast, for A/B runs)."""
+def takes_16(dtype, switch):
+    """Is ``dtype`` a 16-bit type that the operator family behind ``switch`` is instantiated on?  bf16 always; fp16 unless
+    ENABLED[switch] is off (VAH_FUSED_DISABLE=<switch>: the torch expressions under fp16 autocast, for A/B runs).  The
+    switches: 'fp16_rows' (row-streaming kernels), 'fp16_linear' (GEMM dispatcher, weight copies, GELU backward, bias
+    partials), 'fp16_tail' (csrc/tail_ops.hip), 'fp16_spm' (the NHWC SpatialPriorModule)."""
+    return dtype == torch.bfloat16 or (dtype == torch.float16 and ENABLED[switch])
+
+
+def autocast_16(switch):
+    """The 16-bit type the family behind ``switch`` runs in under the active autocast: torch.bfloat16, torch.float16, or
+    None (no autocast, another autocast type, or fp16 with the switch off)."""
     if not torch.is_autocast_enabled():
         return None
     dtype = torch.get_autocast_dtype('cuda')
-    return dtype if _linear_takes(dtype) else None
-
-
-def _linear_takes(dtype):
-    """Is ``dtype`` a 16-bit type the Linear path is instantiated on?  bf16 always; fp16 unless switched off."""
-    return dtype == torch.bfloat16 or (dtype == torch.float16 and ENABLED['fp16_linear'])
-
-
-def _rows_dtype(dtype):
-    """Is ``dtype`` a 16-bit type the row-streaming kernels are instantiated on?  bf16 always; fp16 unless switched off
-    (VAH_FUSED_DISABLE=fp16_rows: the torch expressions under fp16 autocast, for A/B runs)."""
-    return dtype == torch.bfloat16 or (dtype == torch.float16 and ENABLED['fp16_rows'])
-
-
-def _autocast_16():
-    """The 16-bit type the row-streaming kernels write under the active autocast: torch.bfloat16, torch.float16, or
-    None (no autocast, another autocast type, or fp16 with its switch off)."""
-    if not torch.is_autocast_enabled():
-        return None
-    dtype = torch.get_autocast_dtype('cuda')
-    return dtype if _rows_dtype(dtype) else None
-
-
-def _sym(name, dtype):
-    """The entry point ``name`` (its bf16 spelling) for 16-bit operands of ``dtype``: itself or its `_f16` twin."""
-    if dtype == torch.bfloat16:
-        return getattr(_vah.lib, name)
-    for twins in (_vah.FUSED_F16_TWINS, _vah.LINEAR_F16_TWINS):
-        if name in twins:
-            return getattr(_vah.lib, twins[name])
-    return getattr(_vah.lib, _vah.TAIL_F16_TWINS[name])
-
-
-def _tail_dtype():
-    """The 16-bit type the output-tail kernels (csrc/tail_ops.hip) read and write under the active autocast:
-    torch.bfloat16, torch.float16, or None (no autocast, another autocast type, or fp16 with its switch off:
-    VAH_FUSED_DISABLE=fp16_tail, the torch expressions under fp16 autocast, for A/B runs)."""
-    if not torch.is_autocast_enabled():
-        return None
-    dtype = torch.get_autocast_dtype('cuda')
-    return dtype if dtype == torch.bfloat16 or (dtype == torch.float16 and ENABLED['fp16_tail']) else None
+    return dtype if takes_16(dtype, switch) else None
 
 
 def tail_dtype():
-    """Public spelling of _tail_dtype() for the backbones: the dtype of a ``c1`` that up_from_tokens can sum in."""
-    return _tail_dtype()
+    """For the backbones: the dtype of a ``c1`` that up_from_tokens can sum in."""
+    return autocast_16('fp16_tail')
+
+
+_tail_dtype = tail_dtype        # the name tests/test_tail_f16_fp64_gpu.py asks by
 
 
 class _LayerNormBF16(torch.autograd.Function):
@@ -123,9 +93,8 @@ class _LayerNormBF16(torch.autograd.Function):
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         w, b = weight.contiguous(), bias.contiguous()
         with _vah.on(x.device):
-            _vah.check(_sym('vah_layernorm_fwd_f32_bf16', dtype)(
-                x2.data_ptr(), w.data_ptr(), b.data_ptr(), rows, C, float(eps), y.data_ptr(),
-                mean.data_ptr(), rstd.data_ptr(), _stream(x)), 'layernorm_fwd')
+            _vah.call('vah_layernorm_fwd_f32_bf16', dtype, x2.data_ptr(), w.data_ptr(), b.data_ptr(), rows, C, float(eps), y.data_ptr(),
+                      mean.data_ptr(), rstd.data_ptr(), _stream(x))
         ctx.save_for_backward(x2, w, mean, rstd)
         ctx.shape, ctx.dtype = x.shape, dtype
         ctx.set_materialize_grads(False)
@@ -147,16 +116,14 @@ class _LayerNormBF16(torch.autograd.Function):
         dwb = torch.empty(2, C, dtype=torch.float32, device=x2.device)
         ws = _scratch(2 * C, x2.device)
         with _vah.on(x2.device):
-            _vah.check(_sym('vah_layernorm_bwd_f32_bf16', ctx.dtype)(
-                x2.data_ptr(), g.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                gres.data_ptr() if gres is not None else None, rows, C,
-                dx.data_ptr(), dwb[0].data_ptr(), dwb[1].data_ptr(), ws.data_ptr(), _stream(x2)),
-                'layernorm_bwd')
+            _vah.call('vah_layernorm_bwd_f32_bf16', ctx.dtype, x2.data_ptr(), g.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                      gres.data_ptr() if gres is not None else None, rows, C, dx.data_ptr(), dwb[0].data_ptr(), dwb[1].data_ptr(), ws.data_ptr(),
+                      _stream(x2))
         return dx.view(ctx.shape), dwb[0], dwb[1], None, None, None
 
 
 def _ln_fusable(norm, x):
-    return (ENABLED['layer_norm'] and x.is_cuda and x.dtype == torch.float32 and _autocast_16() is not None
+    return (ENABLED['layer_norm'] and x.is_cuda and x.dtype == torch.float32 and autocast_16('fp16_rows') is not None
             and isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine
             and x.shape[-1] % 4 == 0 and x.shape[-1] <= 2048 and x.numel() > 0)
 
@@ -178,9 +145,8 @@ class _LayerNormDualBF16(torch.autograd.Function):
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         wa, ba, wb, bb = (t.contiguous() for t in (wa, ba, wb, bb))
         with _vah.on(x.device):
-            _vah.check(_sym('vah_layernorm_dual_fwd', dtype)(
-                x2.data_ptr(), wa.data_ptr(), ba.data_ptr(), wb.data_ptr(), bb.data_ptr(), rows, C, float(eps),
-                ya.data_ptr(), yb.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(x)), 'layernorm_dual_fwd')
+            _vah.call('vah_layernorm_dual_fwd', dtype, x2.data_ptr(), wa.data_ptr(), ba.data_ptr(), wb.data_ptr(), bb.data_ptr(), rows, C,
+                      float(eps), ya.data_ptr(), yb.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(x))
         ctx.save_for_backward(x2, wa, wb, mean, rstd)
         ctx.shape, ctx.dtype = x.shape, dtype
         ctx.set_materialize_grads(False)
@@ -200,11 +166,9 @@ class _LayerNormDualBF16(torch.autograd.Function):
         dp = torch.empty(4, C, dtype=torch.float32, device=x2.device)
         ws = _scratch(2 * C, x2.device)
         with _vah.on(x2.device):
-            _vah.check(_sym('vah_layernorm_dual_bwd', ctx.dtype)(
-                x2.data_ptr(), ga.data_ptr() if ga is not None else None, gb.data_ptr() if gb is not None else None,
-                wa.data_ptr(), wb.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                gres.data_ptr() if gres is not None else None, rows, C, dx.data_ptr(), dp.data_ptr(), ws.data_ptr(),
-                _stream(x2)), 'layernorm_dual_bwd')
+            _vah.call('vah_layernorm_dual_bwd', ctx.dtype, x2.data_ptr(), ga.data_ptr() if ga is not None else None,
+                      gb.data_ptr() if gb is not None else None, wa.data_ptr(), wb.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                      gres.data_ptr() if gres is not None else None, rows, C, dx.data_ptr(), dp.data_ptr(), ws.data_ptr(), _stream(x2))
         return dx.view(ctx.shape), dp[0], dp[1], dp[2], dp[3], None, None
 
 
@@ -216,7 +180,7 @@ def layer_norm_dual_ok(norm_a, norm_b, x):
 def layer_norm_dual_keep(norm_a, norm_b, x):
     """``(x, norm_a(x), norm_b(x))``; use the returned x downstream (see layer_norm_keep)."""
     if layer_norm_dual_ok(norm_a, norm_b, x):
-        return _LayerNormDualBF16.apply(x, norm_a.weight, norm_a.bias, norm_b.weight, norm_b.bias, norm_a.eps, _autocast_16())
+        return _LayerNormDualBF16.apply(x, norm_a.weight, norm_a.bias, norm_b.weight, norm_b.bias, norm_a.eps, autocast_16('fp16_rows'))
     x, ya = layer_norm_keep(norm_a, x, fan_out=True)
     x, yb = layer_norm_keep(norm_b, x)
     return x, ya, yb
@@ -225,7 +189,7 @@ def layer_norm_dual_keep(norm_a, norm_b, x):
 def layer_norm(norm, x):
     """``norm(x)`` for an nn.LayerNorm; output in the autocast type (bf16 / fp16) when the consumer is a 16-bit GEMM."""
     if _ln_fusable(norm, x):
-        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, False, _autocast_16())
+        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, False, autocast_16('fp16_rows'))
     return norm(x)
 
 
@@ -237,7 +201,7 @@ def layer_norm_keep(norm, x, fan_out=False):
     if fan_out and not ENABLED['keep_feat']:
         return x, layer_norm(norm, x)
     if _ln_fusable(norm, x):
-        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, True, _autocast_16())
+        return _LayerNormBF16.apply(x, norm.weight, norm.bias, norm.eps, True, autocast_16('fp16_rows'))
     return x, norm(x)
 
 
@@ -355,7 +319,7 @@ class forward_epoch:
 
     def __enter__(self):
         module = self.module
-        t16 = _linear_dtype()
+        t16 = autocast_16('fp16_linear')
         if not (ENABLED['linear'] and t16 is not None):
             return self
         # the list is cached on the module; a parameter that is replaced later is simply not part of the
@@ -447,15 +411,13 @@ def gemm_16(a, b, trans_a=False, trans_b=False, out_dtype=None, bias=None, out=N
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
     epilogue = _vah.GEMM_EPI_BIAS if bias is not None else _vah.GEMM_EPI_NONE
     with _vah.on(a.device):
-        _vah.check(_sym('vah_gemm_bf16', t16)(
-            int(trans_a), int(trans_b), M, N, K, a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1],
-            d.data_ptr(), N, int(out_dtype == torch.float32), epilogue,
-            bias.data_ptr() if bias is not None else None,
-            int(bias is not None and bias.dtype == torch.float32), ws.data_ptr(), ws_bytes, _stream(a)), 'gemm_bf16' if t16 == torch.bfloat16 else 'gemm_f16')
+        _vah.call('vah_gemm_bf16', t16, int(trans_a), int(trans_b), M, N, K, a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1], d.data_ptr(), N,
+                  int(out_dtype == torch.float32), epilogue, bias.data_ptr() if bias is not None else None,
+                  int(bias is not None and bias.dtype == torch.float32), ws.data_ptr(), ws_bytes, _stream(a))
     return d
 
 
-gemm_bf16 = gemm_16         # the name from before the dispatcher took fp16 operands
+gemm_bf16 = gemm_16         # the name from before the dispatcher took fp16 operands: for callers outside this module
 
 
 def _wgrad_bgrad(g2, x2, partials=None):
@@ -482,11 +444,9 @@ def _wgrad_bgrad(g2, x2, partials=None):
             cws, nparts = partials[0], ctypes.c_int64(partials[1])
         else:
             cws, nparts = _scratch(N, dev), ctypes.c_int64(0)
-            _vah.check(_sym('vah_colsum_bf16_partials', t16)(g2.data_ptr(), R, N, cws.data_ptr(), ctypes.byref(nparts), st),
-                       'colsum_partials')
-        _vah.check(_sym('vah_gemm_bf16_fin', t16)(1, 0, N, K, R, g2.data_ptr(), N, x2.data_ptr(), K, gw.data_ptr(), K, 1,
-                                              ws.data_ptr(), ws_bytes, cws.data_ptr(), nparts.value, N, gb.data_ptr(), st),
-                   'gemm_bf16_fin' if t16 == torch.bfloat16 else 'gemm_f16_fin')
+            _vah.call('vah_colsum_bf16_partials', t16, g2.data_ptr(), R, N, cws.data_ptr(), ctypes.byref(nparts), st)
+        _vah.call('vah_gemm_bf16_fin', t16, 1, 0, N, K, R, g2.data_ptr(), N, x2.data_ptr(), K, gw.data_ptr(), K, 1, ws.data_ptr(), ws_bytes,
+                  cws.data_ptr(), nparts.value, N, gb.data_ptr(), st)
     return gw, gb
 
 
@@ -624,7 +584,7 @@ class _BiasPartials:
 
     @staticmethod
     def wanted(z):
-        return bool(ENABLED['bias_partials'] and getattr(z, _BiasPartials.ATTR, False) and _linear_takes(z.dtype)
+        return bool(ENABLED['bias_partials'] and getattr(z, _BiasPartials.ATTR, False) and takes_16(z.dtype, 'fp16_linear')
                     and z.shape[-1] % 8 == 0)
 
     @staticmethod
@@ -717,7 +677,7 @@ class _LinearBF16(torch.autograd.Function):
             with torch.cuda.stream(SIDE.fork(g2.device, keep)):
                 SIDE.deliver(g2.device, ctx.side, _wgrad_bgrad(g2, x2, partials))
         if ctx.needs_input_grad[0]:
-            gx = gemm_bf16(g2, wb).view(ctx.in_shape)
+            gx = gemm_16(g2, wb).view(ctx.in_shape)
             if gx.dtype != ctx.in_dtype:
                 gx = gx.to(ctx.in_dtype)
         if deferred:
@@ -727,15 +687,14 @@ class _LinearBF16(torch.autograd.Function):
         else:
             if ctx.needs_input_grad[1]:
                 if WGRAD_F32:
-                    gw = gemm_bf16(g2, x2, trans_a=True, out_dtype=torch.float32)
+                    gw = gemm_16(g2, x2, trans_a=True, out_dtype=torch.float32)
                 else:
-                    gw = gemm_bf16(g2, x2, trans_a=True).float()
+                    gw = gemm_16(g2, x2, trans_a=True).float()
             if want_b:
                 gb = torch.empty(N, dtype=torch.float32, device=g2.device)
                 ws = _scratch(N, g2.device)
                 with _vah.on(g2.device):
-                    _vah.check(_sym('vah_colsum_bf16', t16)(g2.data_ptr(), g2.shape[0], N, gb.data_ptr(),
-                                                            ws.data_ptr(), _stream(g2)), 'colsum')
+                    _vah.call('vah_colsum_bf16', t16, g2.data_ptr(), g2.shape[0], N, gb.data_ptr(), ws.data_ptr(), _stream(g2))
         return gx, gw, gb, None
 
 
@@ -799,7 +758,7 @@ class _LinearPairBF16(torch.autograd.Function):
         g[:, na:] = gb.reshape(R, nb) if gb is not None else 0
         gx = gw = gbias = None
         if ctx.needs_input_grad[0]:
-            gx = gemm_bf16(g, w).view(ctx.in_shape)
+            gx = gemm_16(g, w).view(ctx.in_shape)
             if gx.dtype != ctx.in_dtype:
                 gx = gx.to(ctx.in_dtype)
         want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[3]
@@ -808,13 +767,12 @@ class _LinearPairBF16(torch.autograd.Function):
             gw, gbias = _wgrad_bgrad(g, x2)
         else:
             if want_w:
-                gw = gemm_bf16(g, x2, trans_a=True, out_dtype=torch.float32)
+                gw = gemm_16(g, x2, trans_a=True, out_dtype=torch.float32)
             if want_b:
                 gbias = torch.empty(na + nb, dtype=torch.float32, device=g.device)
                 ws = _scratch(na + nb, g.device)
                 with _vah.on(g.device):
-                    _vah.check(_sym('vah_colsum_bf16', g.dtype)(g.data_ptr(), R, na + nb, gbias.data_ptr(), ws.data_ptr(),
-                                                                _stream(g)), 'colsum')
+                    _vah.call('vah_colsum_bf16', g.dtype, g.data_ptr(), R, na + nb, gbias.data_ptr(), ws.data_ptr(), _stream(g))
         return (gx, gw[:na] if gw is not None else None, gbias[:na] if gbias is not None else None,
                 gw[na:] if gw is not None else None, gbias[na:] if gbias is not None else None, None, None)
 
@@ -825,7 +783,7 @@ def linear_pair(lin_a, lin_b, x, f32_out=False):
     integer pixel coordinates, so 8-bit offsets cost the upstream gradients 0.3 - 0.7 of relative L2 on small maps)."""
     wa, wb = lin_a.weight, lin_b.weight
     # fp16 autocast: the form with 16-bit outputs only (fp32 offsets under fp16 are MSDeformAttn's own business)
-    t16 = _linear_dtype()
+    t16 = autocast_16('fp16_linear')
     if f32_out and t16 != torch.bfloat16:
         t16 = None
     if (ENABLED['linear'] and ENABLED['linear_pair'] and x.is_cuda and t16 is not None and wa.dtype == torch.float32
@@ -859,8 +817,8 @@ class _PairCoreCopies:
         na, nb = a.weight.shape[0], b.weight.shape[0]
         po, pl = na // M, nb // M
         dev = a.weight.device
-        if e is not None and e[3][0].device == dev:
-            perm = e[3]
+        if e is not None and e[4]() is a.weight and e[3][0].device == dev and e[3][0].numel() == na + nb:
+            perm = e[3]     # of this very module: id() of a collected module's weights comes back for another module's
         else:               # (permutation, its inverse): made once per module and device, not per call
             fw = torch.cat([torch.cat((torch.arange(m * po, (m + 1) * po), na + torch.arange(m * pl, (m + 1) * pl))) for m in range(M)])
             inv = torch.empty_like(fw)
@@ -898,7 +856,7 @@ class _MSDAPairCore(torch.autograd.Function):
             x2 = x2.to(torch.bfloat16)
         x2 = x2.contiguous()
         w, bias, perm = copies
-        y = gemm_bf16(x2, w, trans_b=True, bias=bias, out_dtype=torch.float32)         # (N * Lq, M * 3 * L * P) fp32
+        y = gemm_16(x2, w, trans_b=True, bias=bias, out_dtype=torch.float32)         # (N * Lq, M * 3 * L * P) fp32
         N, Lq = query.shape[0], query.shape[1]
         PS = 3 * L * P
         yv = y.view(N, Lq, M, PS)
@@ -935,7 +893,7 @@ class _MSDAPairCore(torch.autograd.Function):
         _vah.check(rc, 'vah_msda_fused_backward_tiled_nref')
         gx = gw = gbias = None
         if ctx.needs_input_grad[0]:
-            gx = gemm_bf16(g, w).view(ctx.in_shape)
+            gx = gemm_16(g, w).view(ctx.in_shape)
             if gx.dtype != ctx.in_dtype:
                 gx = gx.to(ctx.in_dtype)
         if any(ctx.needs_input_grad[5:9]):
@@ -984,7 +942,7 @@ class _Conv1x1BF16(torch.autograd.Function):
         wb = BF16_COPIES.get(weight).view(Co, Ci)
         out = torch.empty((B, Co, H, W), dtype=torch.bfloat16, device=x.device)
         for b in range(B):
-            gemm_bf16(wb, x[b].view(Ci, H * W), out=out[b].view(Co, H * W))
+            gemm_16(wb, x[b].view(Ci, H * W), out=out[b].view(Co, H * W))
         ctx.save_for_backward(x, wb)
         return out
 
@@ -998,10 +956,10 @@ class _Conv1x1BF16(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             for b in range(B):
-                gemm_bf16(wb, g[b].view(Co, H * W), trans_a=True, out=dx[b].view(Ci, H * W))
+                gemm_16(wb, g[b].view(Co, H * W), trans_a=True, out=dx[b].view(Ci, H * W))
         if ctx.needs_input_grad[1]:
             for b in range(B):
-                part = gemm_bf16(g[b].view(Co, H * W), x[b].view(Ci, H * W), trans_b=True, out_dtype=torch.float32)
+                part = gemm_16(g[b].view(Co, H * W), x[b].view(Ci, H * W), trans_b=True, out_dtype=torch.float32)
                 dw = part if dw is None else dw.add_(part)
             dw = dw.view(Co, Ci, 1, 1)
         return dx, dw
@@ -1013,7 +971,7 @@ class _UpFromTokens(torch.autograd.Function):
     GEMM per image, U_b (4*Co, h*w) = Wcat (4*Co, C) rows_b^T with Wcat rows (dy, dx, co), followed by the 2 x 2 sub-pixel
     interleave (csrc/tail_ops.hip::pixel_shuffle2); the backward is the inverse interleave and two GEMMs.  MIOpen's
     NCHW transposed convolution took 494 + 846 us for this layer at base_det (2 x 768 x 128 x 128).
-    bf16: the products are gemm_bf16.  fp16: they are torch's fp16 library GEMMs on the token rows (this operator's fp16
+    bf16: the products are gemm_16.  fp16: they are torch's fp16 library GEMMs on the token rows (this operator's fp16
     form was not moved to the dispatcher with the Linear layers); dW is what autocast gives conv_transpose2d - fp16 products per image, summed over the images in fp32."""
 
     @staticmethod
@@ -1025,15 +983,15 @@ class _UpFromTokens(torch.autograd.Function):
             wc = BF16_COPIES.get(weight).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()       # rows (dy, dx, co)
             U = torch.empty((B, 4 * Co, T), dtype=torch.bfloat16, device=rows.device)
             for b in range(B):
-                gemm_bf16(wc, xb[b], trans_b=True, out=U[b])
+                gemm_16(wc, xb[b], trans_b=True, out=U[b])
         else:
             wc = weight.detach().to(t16).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()
             U = torch.bmm(wc.unsqueeze(0).expand(B, 4 * Co, C), xb.transpose(1, 2))
         out = torch.empty((B, Co, 2 * h, 2 * w), dtype=t16, device=rows.device)
         add = addend.contiguous() if addend is not None else None
         with _vah.on(rows.device):
-            _vah.check(_sym('vah_pixel_shuffle2_bf16', t16)(U.data_ptr(), B, Co, h, w, out.data_ptr(), 0,
-                                                            add.data_ptr() if add is not None else None, _stream(rows)), 'pixel_shuffle2')
+            _vah.call('vah_pixel_shuffle2_bf16', t16, U.data_ptr(), B, Co, h, w, out.data_ptr(), 0, add.data_ptr() if add is not None else None,
+                      _stream(rows))
         ctx.save_for_backward(xb, wc)
         ctx.meta = (h, w, Co, rows.dtype, t16)
         return out
@@ -1046,13 +1004,13 @@ class _UpFromTokens(torch.autograd.Function):
         g = g.contiguous().to(t16)
         dU = torch.empty((B, 4 * Co, T), dtype=t16, device=g.device)
         with _vah.on(g.device):
-            _vah.check(_sym('vah_pixel_shuffle2_bf16', t16)(g.data_ptr(), B, Co, h, w, dU.data_ptr(), 1, None, _stream(g)), 'pixel_shuffle2')
+            _vah.call('vah_pixel_shuffle2_bf16', t16, g.data_ptr(), B, Co, h, w, dU.data_ptr(), 1, None, _stream(g))
         dx = dw = None
         if ctx.needs_input_grad[0]:
             if t16 == torch.bfloat16:
                 dx = torch.empty((B, T, C), dtype=torch.bfloat16, device=g.device)
                 for b in range(B):
-                    gemm_bf16(dU[b], wc, trans_a=True, out=dx[b])
+                    gemm_16(dU[b], wc, trans_a=True, out=dx[b])
             else:
                 dx = torch.matmul(dU.transpose(1, 2), wc)
             if dx.dtype != in_dtype:
@@ -1060,7 +1018,7 @@ class _UpFromTokens(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             if t16 == torch.bfloat16:
                 for b in range(B):
-                    part = gemm_bf16(dU[b], xb[b], out_dtype=torch.float32)
+                    part = gemm_16(dU[b], xb[b], out_dtype=torch.float32)
                     dw = part if dw is None else dw.add_(part)
             else:
                 dw = torch.bmm(dU, xb).float().sum(0)
@@ -1075,7 +1033,7 @@ def up_from_tokens(up, rows, h, w, addend=None):
     interleave pass - ``up(c2) + c1`` rounded once, as autocast rounds the sum of two half tensors - so the tail reads one
     operand instead of two.  bf16 or (ENABLED['fp16_tail']) fp16 autocast.  None when the GEMM form does not apply."""
     wt = up.weight
-    t16 = _tail_dtype()
+    t16 = autocast_16('fp16_tail')
     if (ENABLED['up_gemm'] and ENABLED['linear'] and rows.is_cuda and t16 is not None and isinstance(up, torch.nn.ConvTranspose2d)
             and up.kernel_size == (2, 2) and up.stride == (2, 2) and up.padding == (0, 0) and up.output_padding == (0, 0)
             and up.groups == 1 and up.dilation == (1, 1) and wt.dtype == torch.float32 and rows.dim() == 3
@@ -1123,7 +1081,7 @@ def linear(lin, x):
     """``lin(x)`` for an nn.Linear (reference: every nn.Linear of base/vit.py, adapter_modules.py
     and ms_deform_attn.py)."""
     w = lin.weight
-    t16 = _linear_dtype()
+    t16 = autocast_16('fp16_linear')
     if (ENABLED['linear'] and x.is_cuda and t16 is not None and w.dtype == torch.float32
             and x.dtype in (t16, torch.float32) and w.shape[0] % 8 == 0
             and w.shape[1] % 8 == 0 and x.numel() > 0 and type(lin) is torch.nn.Linear):
@@ -1150,9 +1108,8 @@ class _GeluBF16(torch.autograd.Function):
         bpart, nparts = _bias_partials_out(C, h.device)
         import ctypes
         with _vah.on(h.device):
-            _vah.check(_sym('vah_gelu_bwd_bsum_bf16', h.dtype)(da.data_ptr(), hc.data_ptr(), h.numel() // C, C, dh.data_ptr(),
-                                                               bpart.data_ptr(), ctypes.byref(nparts), _stream(h)),
-                       'gelu_bwd_bsum')
+            _vah.call('vah_gelu_bwd_bsum_bf16', h.dtype, da.data_ptr(), hc.data_ptr(), h.numel() // C, C, dh.data_ptr(), bpart.data_ptr(),
+                      ctypes.byref(nparts), _stream(h))
         BIAS_PARTIALS.record(dh, bpart, nparts.value)
         return dh
 
@@ -1160,7 +1117,7 @@ class _GeluBF16(torch.autograd.Function):
 def gelu(act, h):
     """``act(h)`` for the activation between two Linears (base/vit.py Mlp): an exact nn.GELU on the marked 16-bit output
     of a fused Linear under bf16 (or, ENABLED['fp16_linear'], fp16) autocast takes the backward kernel that also sums fc1's bias gradient."""
-    if (isinstance(act, torch.nn.GELU) and act.approximate == 'none' and h.is_cuda and _linear_dtype() is not None
+    if (isinstance(act, torch.nn.GELU) and act.approximate == 'none' and h.is_cuda and autocast_16('fp16_linear') is not None
             and BIAS_PARTIALS.wanted(h) and h.numel() > 0 and h.requires_grad and torch.is_grad_enabled()):
         return _GeluBF16.apply(h)
     return act(h)
@@ -1180,11 +1137,10 @@ def _scale_residual_bwd(g, z, gp, s, dims, bias_partials):
     with _vah.on(g.device):
         if bias_partials:
             bpart, nparts = _bias_partials_out(C, g.device)
-            _vah.check(_sym('vah_scale_residual_bwd_bsum', z.dtype)(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(g)),
-                       'scale_residual_bwd_bsum')
+            _vah.call('vah_scale_residual_bwd_bsum', z.dtype, *args, bpart.data_ptr(), ctypes.byref(nparts), _stream(g))
             BIAS_PARTIALS.record(dz, bpart, nparts.value)
         else:
-            _vah.check(_sym('vah_scale_residual_bwd', z.dtype)(*args, _stream(g)), 'scale_residual_bwd')
+            _vah.call('vah_scale_residual_bwd', z.dtype, *args, _stream(g))
     return dz, dgamma
 
 
@@ -1197,10 +1153,8 @@ class _ScaleResidual(torch.autograd.Function):
         y = torch.empty_like(x)
         gp = gamma.contiguous() if gamma is not None else None
         with _vah.on(x.device):
-            _vah.check(_sym('vah_scale_residual_fwd', z.dtype)(
-                x.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
-                s.data_ptr() if s is not None else None, B, rpb, C, y.data_ptr(), _stream(x)),
-                'scale_residual_fwd')
+            _vah.call('vah_scale_residual_fwd', z.dtype, x.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
+                      s.data_ptr() if s is not None else None, B, rpb, C, y.data_ptr(), _stream(x))
         ctx.save_for_backward(z, gp, s)
         ctx.dims = (B, rpb, C)
         ctx.bias_partials = bias_partials
@@ -1219,7 +1173,7 @@ def residual(x, z, gamma=None, drop_path=None):
     reference's Block / Injector / Extractor."""
     prob = float(getattr(drop_path, 'drop_prob', 0.) or 0.)
     training = bool(getattr(drop_path, 'training', False))
-    if (ENABLED['residual'] and x.is_cuda and x.dtype == torch.float32 and _rows_dtype(z.dtype)
+    if (ENABLED['residual'] and x.is_cuda and x.dtype == torch.float32 and takes_16(z.dtype, 'fp16_rows')
             and x.shape == z.shape and x.shape[-1] % 4 == 0 and x.numel() > 0
             and (gamma is None or gamma.dtype == torch.float32)):
         s = None
@@ -1247,10 +1201,9 @@ class _ResidualLN(torch.autograd.Function):
         gp = gamma.contiguous() if gamma is not None else None
         w, b = weight.contiguous(), bias.contiguous()
         with _vah.on(x.device):
-            _vah.check(_sym('vah_residual_layernorm_fwd', z.dtype)(
-                x.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
-                s.data_ptr() if s is not None else None, B, rpb, C, w.data_ptr(), b.data_ptr(), float(eps),
-                t.data_ptr(), h.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(x)), 'residual_layernorm_fwd')
+            _vah.call('vah_residual_layernorm_fwd', z.dtype, x.data_ptr(), z.data_ptr(), gp.data_ptr() if gp is not None else None,
+                      s.data_ptr() if s is not None else None, B, rpb, C, w.data_ptr(), b.data_ptr(), float(eps), t.data_ptr(), h.data_ptr(),
+                      mean.data_ptr(), rstd.data_ptr(), _stream(x))
         ctx.save_for_backward(t, z, gp, s, w, mean, rstd)
         ctx.dims = (B, rpb, C)
         ctx.bias_partials = bias_partials      # residual_ln asks only without a gamma
@@ -1283,11 +1236,10 @@ class _ResidualLN(torch.autograd.Function):
             if ctx.bias_partials and gp is None:
                 import ctypes
                 bpart, nparts = _bias_partials_out(C, dev)
-                _vah.check(_sym('vah_residual_layernorm_bwd_bsum', z.dtype)(*args, bpart.data_ptr(), ctypes.byref(nparts), _stream(t)),
-                           'residual_layernorm_bwd_bsum')
+                _vah.call('vah_residual_layernorm_bwd_bsum', z.dtype, *args, bpart.data_ptr(), ctypes.byref(nparts), _stream(t))
                 BIAS_PARTIALS.record(dz, bpart, nparts.value)
             else:
-                _vah.check(_sym('vah_residual_layernorm_bwd', z.dtype)(*args, _stream(t)), 'residual_layernorm_bwd')
+                _vah.call('vah_residual_layernorm_bwd', z.dtype, *args, _stream(t))
         return dt, dz, grads[2] if gp is not None else None, None, grads[0], grads[1], None, None
 
 
@@ -1302,12 +1254,12 @@ def residual_ln(x, z, gamma, drop_path, norm):
     """``t = x + drop_path(gamma * z); return t, norm(t)`` - a residual update followed by the
     LayerNorm of the next sub-block (base/vit.py:301-306), one pass over the rows each way."""
     # z in the type the LayerNorm will write: a bf16 z under fp16 autocast (or the reverse) takes the torch expression
-    if (ENABLED['residual'] and ENABLED['residual_ln'] and _ln_fusable(norm, x) and z.dtype == _autocast_16()
+    if (ENABLED['residual'] and ENABLED['residual_ln'] and _ln_fusable(norm, x) and z.dtype == autocast_16('fp16_rows')
             and x.shape == z.shape
             and x.dim() >= 2 and (gamma is None or gamma.dtype == torch.float32) and x.shape[-1] <= 1024):
         return _ResidualLN.apply(x, z, gamma, _drop_path_scale(x, drop_path), norm.weight, norm.bias, norm.eps,
                                  gamma is None and BIAS_PARTIALS.wanted(z))
-    ac = _autocast_16()
+    ac = autocast_16('fp16_rows')
     if ENABLED['fp16_rows'] and ac is not None and z.dtype != ac and z.dtype in (torch.bfloat16, torch.float16):
         # a branch output in the other 16-bit type than the one autocast is running: the torch expression, nothing fused
         t = gamma * z if gamma is not None else z
@@ -1325,9 +1277,8 @@ class _DWConvTokens(torch.autograd.Function):
         b = bias.detach().float().contiguous() if bias is not None else None
         y = torch.empty_like(x)
         with _vah.on(x.device):
-            _vah.check(_sym('vah_dwconv3x3_tokens_bf16', x.dtype)(
-                x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, B, H, W, C, 0,
-                y.data_ptr(), _stream(x)), 'dwconv_fwd')
+            _vah.call('vah_dwconv3x3_tokens_bf16', x.dtype, x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, B, H, W, C, 0,
+                      y.data_ptr(), _stream(x))
         ctx.save_for_backward(x, w)
         ctx.dims = (B, H, W, C, bias is not None, weight.dtype)
         return y
@@ -1341,11 +1292,9 @@ class _DWConvTokens(torch.autograd.Function):
         dw = torch.empty(C * 9 + C, dtype=torch.float32, device=x.device)
         ws = _scratch(10 * C, x.device)
         with _vah.on(x.device):
-            _vah.check(_sym('vah_dwconv3x3_tokens_bf16', x.dtype)(
-                g.data_ptr(), w.data_ptr(), None, B, H, W, C, 1, dx.data_ptr(), _stream(x)), 'dwconv_dgrad')
-            _vah.check(_sym('vah_dwconv3x3_tokens_wgrad_bf16', x.dtype)(
-                x.data_ptr(), g.data_ptr(), B, H, W, C, dw.data_ptr(),
-                dw[C * 9:].data_ptr() if has_bias else None, ws.data_ptr(), _stream(x)), 'dwconv_wgrad')
+            _vah.call('vah_dwconv3x3_tokens_bf16', x.dtype, g.data_ptr(), w.data_ptr(), None, B, H, W, C, 1, dx.data_ptr(), _stream(x))
+            _vah.call('vah_dwconv3x3_tokens_wgrad_bf16', x.dtype, x.data_ptr(), g.data_ptr(), B, H, W, C, dw.data_ptr(),
+                      dw[C * 9:].data_ptr() if has_bias else None, ws.data_ptr(), _stream(x))
         return (dx, dw[:C * 9].view(C, 1, 3, 3).to(wdtype),
                 dw[C * 9:].to(wdtype) if has_bias else None, None, None)
 
@@ -1353,7 +1302,7 @@ class _DWConvTokens(torch.autograd.Function):
 def dwconv_tokens(conv, x, H, W):
     """ConvFFN's DWConv on the concatenated token maps; None when the fused path does not apply."""
     B, N, C = x.shape
-    if (ENABLED['dwconv'] and x.is_cuda and _rows_dtype(x.dtype) and C % 4 == 0 and C <= 1024
+    if (ENABLED['dwconv'] and x.is_cuda and takes_16(x.dtype, 'fp16_rows') and C % 4 == 0 and C <= 1024
             and H % 2 == 0 and W % 2 == 0 and N == 21 * (H // 2) * (W // 2) and x.numel() > 0
             and conv.weight.shape == (C, 1, 3, 3)):
         return _DWConvTokens.apply(x, conv.weight, conv.bias, H, W)
@@ -1400,7 +1349,7 @@ class _BNTail(torch.autograd.Function):
             if training:
                 sums = torch.empty(2 * C + 1, dtype=torch.float32, device=dev)
                 ws = torch.empty(_vah.lib.vah_bn_tail_ws_floats(C), dtype=torch.float32, device=dev)
-                _vah.check(_sym('vah_bn_tail_stats', t16)(*ops, shp, sums.data_ptr(), ws.data_ptr(), st), 'bn_tail_stats')
+                _vah.call('vah_bn_tail_stats', t16, *ops, shp, sums.data_ptr(), ws.data_ptr(), st)
                 sums[2 * C:].fill_(float(N * H * W))
                 if group is not None:
                     import torch.distributed as dist
@@ -1421,10 +1370,8 @@ class _BNTail(torch.autograd.Function):
                 mean = norm.running_mean.float().contiguous()
                 rstd = torch.rsqrt(norm.running_var.float() + norm.eps)
             y = torch.empty((N, C, H, W), dtype=out_dtype, device=dev)
-            _vah.check(_sym('vah_bn_tail_apply', t16)(
-                *ops, mean.data_ptr(), rstd.data_ptr(), w.data_ptr() if w is not None else None,
-                bb.data_ptr() if bb is not None else None, int(relu), shp, y.data_ptr(),
-                int(out_dtype == t16), st), 'bn_tail_apply')
+            _vah.call('vah_bn_tail_apply', t16, *ops, mean.data_ptr(), rstd.data_ptr(), w.data_ptr() if w is not None else None,
+                      bb.data_ptr() if bb is not None else None, int(relu), shp, y.data_ptr(), int(out_dtype == t16), st)
         ctx.save_for_backward(a, b, x, mean, rstd, w, bb, count, sh)
         ctx.meta = (scale, training, group, weight is not None, bias is not None, relu, t16)
         return y
@@ -1448,9 +1395,8 @@ class _BNTail(torch.autograd.Function):
         with _vah.on(dev):
             sums = torch.empty(2 * C, dtype=torch.float32, device=dev)
             ws = torch.empty(_vah.lib.vah_bn_tail_ws_floats(C), dtype=torch.float32, device=dev)
-            _vah.check(_sym('vah_bn_tail_bwd_stats', t16)(*ops, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu), shp,
-                                                          dy.data_ptr(), dy_bf16, sums.data_ptr(), ws.data_ptr(), st),
-                       'bn_tail_bwd_stats')
+            _vah.call('vah_bn_tail_bwd_stats', t16, *ops, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu), shp, dy.data_ptr(), dy_bf16,
+                      sums.data_ptr(), ws.data_ptr(), st)
             local = sums.clone() if (training and group is not None) else sums      # dweight / dbias are per-rank sums
             dweight = local[C:] if has_w else None
             dbias = local[:C] if has_b else None
@@ -1468,11 +1414,9 @@ class _BNTail(torch.autograd.Function):
             if x is not None and need_x:
                 dx = torch.zeros_like(x) if scale > 1 else torch.empty_like(x)
             if da is not None or db is not None or dx is not None:
-                _vah.check(_sym('vah_bn_tail_bwd_apply', t16)(
-                    *ops, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu), shp, dy.data_ptr(), dy_bf16,
-                    means[:C].data_ptr(), means[C:].data_ptr(),
-                    da.data_ptr() if da is not None else None, db.data_ptr() if db is not None else None,
-                    dx.data_ptr() if dx is not None else None, st), 'bn_tail_bwd_apply')
+                _vah.call('vah_bn_tail_bwd_apply', t16, *ops, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu), shp, dy.data_ptr(), dy_bf16,
+                          means[:C].data_ptr(), means[C:].data_ptr(), da.data_ptr() if da is not None else None,
+                          db.data_ptr() if db is not None else None, dx.data_ptr() if dx is not None else None, st)
         dshift = None
         if sh is not None and ctx.needs_input_grad[5]:
             # d/d(shift) = sum of dt over the channel: BatchNorm in training removes channel constants
@@ -1484,7 +1428,7 @@ class _BNTail(torch.autograd.Function):
 def _bn_fusable(norm, a):
     """bf16 autocast, or fp16 autocast with ENABLED['fp16_tail']; ``a`` in the autocast's 16-bit type or fp32 (a tensor
     of the other 16-bit type takes the reference expression, nothing fused)."""
-    t16 = _tail_dtype()
+    t16 = autocast_16('fp16_tail')
     return (isinstance(norm, torch.nn.modules.batchnorm._BatchNorm) and a.is_cuda and t16 is not None
             and a.dim() == 4 and a.dtype in (t16, torch.float32) and a.shape[3] <= 8192
             and a.numel() > 0 and norm.momentum is not None
@@ -1511,7 +1455,7 @@ def halve(x):
     With even H, W the taps are (0.5, 0.5) in both directions: the 2x2 mean.  torch's bilinear
     kernel parallelises over output pixels only (706 us for 2x768x32x32 on MI355X); on the bf16 (and,
     ENABLED['fp16_tail'], fp16) GPU path the mean is taken with avg_pool2d, elsewhere the reference call is kept."""
-    if (ENABLED['bn_tail'] and x.is_cuda and _tail_dtype() is not None and x.dim() == 4 and x.shape[2] % 2 == 0
+    if (ENABLED['bn_tail'] and x.is_cuda and autocast_16('fp16_tail') is not None and x.dim() == 4 and x.shape[2] % 2 == 0
             and x.shape[3] % 2 == 0):
         return F.avg_pool2d(x.float(), 2)
     return F.interpolate(x, scale_factor=0.5, mode='bilinear', align_corners=False)
@@ -1522,7 +1466,7 @@ def bn_tail(norm, a, b=None, x=None, scale=1, shift=None):
     for a (Sync)BatchNorm2d ``norm`` - the output tail of the backbone (ref vit_adapter.py:106-127);
     ``b`` / ``x`` optional, ``scale == 1`` adds ``x`` as it is.  ``shift`` (C,): per-channel constant
     added to the sum (biases of the convolutions that made ``a`` / ``b``, applied here for free)."""
-    t16 = _tail_dtype()
+    t16 = autocast_16('fp16_tail')
     if (ENABLED['bn_tail'] and _bn_fusable(norm, a) and x is not None
             and (b is None or (b.shape == a.shape and b.dtype in (t16, torch.float32)))
             and scale in (1, 2, 4, 8) and a.shape[3] % (4 * scale) == 0 and a.shape[2] % scale == 0
@@ -1547,7 +1491,7 @@ def bn_relu(norm, a):
     # the two-pass form pays from a few million elements on (below that MIOpen's single kernel wins)
     if (ENABLED['bn_relu'] and _bn_fusable(norm, a) and a.shape[3] % 4 == 0 and a.numel() >= BN_RELU_MIN_NUMEL
             and _tail_shape_ok(a, 1, False)):
-        return _BNTail.apply(a, None, None, norm.weight, norm.bias, None, norm, 1, True, a.dtype, _tail_dtype())
+        return _BNTail.apply(a, None, None, norm.weight, norm.bias, None, norm, 1, True, a.dtype, autocast_16('fp16_tail'))
     return F.relu(norm(a))
 
 
@@ -1568,8 +1512,7 @@ class _TokensToMaps(torch.autograd.Function):
         with _vah.on(tokens.device):
             for h, w in hw:
                 o = torch.empty((B, C, h, w), dtype=torch.float32, device=tokens.device)
-                _vah.check(_sym('vah_transpose_tokens', t16)(tokens.data_ptr(), B, T, t0, h * w, C, o.data_ptr(), 1, 0, None,
-                                                             _stream(tokens)), 'transpose_tokens')
+                _vah.call('vah_transpose_tokens', t16, tokens.data_ptr(), B, T, t0, h * w, C, o.data_ptr(), 1, 0, None, _stream(tokens))
                 outs.append(o)
                 t0 += h * w
         ctx.hw, ctx.shape, ctx.t16 = hw, (B, T, C), t16
@@ -1588,8 +1531,7 @@ class _TokensToMaps(torch.autograd.Function):
                     gt[:, t0:t0 + h * w].zero_()
                 else:
                     g = g.contiguous().float()
-                    _vah.check(_sym('vah_transpose_tokens', ctx.t16)(g.data_ptr(), B, T, t0, h * w, C, gt.data_ptr(), 0, 0, None,
-                                                                     _stream(g)), 'transpose_tokens')
+                    _vah.call('vah_transpose_tokens', ctx.t16, g.data_ptr(), B, T, t0, h * w, C, gt.data_ptr(), 0, 0, None, _stream(g))
                 t0 += h * w
         return gt, None, None
 
@@ -1597,7 +1539,7 @@ class _TokensToMaps(torch.autograd.Function):
 def _maps_dtype():
     """The 16-bit type whose instantiation of the token <-> plane transposes serves the call: fp16 under fp16 autocast
     with ENABLED['fp16_tail'] (fp32 planes included, so that the step's profiler rows are all `_f16`), else bf16."""
-    return torch.float16 if _tail_dtype() == torch.float16 else torch.bfloat16
+    return torch.float16 if autocast_16('fp16_tail') == torch.float16 else torch.bfloat16
 
 
 def tokens_to_maps(tokens, hw):
@@ -1635,9 +1577,8 @@ class _MapsToTokens(torch.autograd.Function):
             for m, v, (h, w) in zip(maps, vecs, hw):
                 m = m.contiguous()
                 vv = v.detach().float().contiguous() if v is not None else None
-                _vah.check(_sym('vah_transpose_tokens', t16)(
-                    m.data_ptr(), B, T, t0, h * w, C, out.data_ptr(), 0, int(m.dtype == t16),
-                    vv.data_ptr() if vv is not None else None, _stream(m)), 'transpose_tokens')
+                _vah.call('vah_transpose_tokens', t16, m.data_ptr(), B, T, t0, h * w, C, out.data_ptr(), 0, int(m.dtype == t16),
+                          vv.data_ptr() if vv is not None else None, _stream(m))
                 t0 += h * w
         ctx.meta = (hw, [m.dtype for m in maps], [v is not None for v in vecs], (B, T, C), t16)
         return out
@@ -1650,8 +1591,7 @@ class _MapsToTokens(torch.autograd.Function):
         with _vah.on(g.device):
             for (h, w), dt, hv in zip(hw, dts, has_vec):
                 gm = torch.empty((B, C, h, w), dtype=dt, device=g.device)
-                _vah.check(_sym('vah_transpose_tokens', t16)(g.data_ptr(), B, T, t0, h * w, C, gm.data_ptr(), 1,
-                                                             int(dt == t16), None, _stream(g)), 'transpose_tokens')
+                _vah.call('vah_transpose_tokens', t16, g.data_ptr(), B, T, t0, h * w, C, gm.data_ptr(), 1, int(dt == t16), None, _stream(g))
                 gmaps.append(gm)
                 gv = None
                 if hv and C % 4 == 0:
@@ -1686,8 +1626,7 @@ class _MaxPool3s2(torch.autograd.Function):
         y = torch.empty((N, C, Ho, Wo), dtype=x.dtype, device=x.device)
         idx = torch.empty((N, C, Ho, Wo), dtype=torch.uint8, device=x.device)
         with _vah.on(x.device):
-            _vah.check(_sym('vah_maxpool3s2_fwd_bf16', x.dtype)(x.data_ptr(), N * C, H, W, y.data_ptr(), idx.data_ptr(),
-                                                                _stream(x)), 'maxpool_fwd')
+            _vah.call('vah_maxpool3s2_fwd_bf16', x.dtype, x.data_ptr(), N * C, H, W, y.data_ptr(), idx.data_ptr(), _stream(x))
         ctx.save_for_backward(idx)
         ctx.shape, ctx.t16 = (N, C, H, W), x.dtype
         return y
@@ -1699,8 +1638,7 @@ class _MaxPool3s2(torch.autograd.Function):
         gy = gy.contiguous().to(ctx.t16)
         gx = torch.empty((N, C, H, W), dtype=ctx.t16, device=gy.device)
         with _vah.on(gy.device):
-            _vah.check(_sym('vah_maxpool3s2_bwd_bf16', ctx.t16)(gy.data_ptr(), idx.data_ptr(), N * C, H, W, gx.data_ptr(),
-                                                                _stream(gy)), 'maxpool_bwd')
+            _vah.call('vah_maxpool3s2_bwd_bf16', ctx.t16, gy.data_ptr(), idx.data_ptr(), N * C, H, W, gx.data_ptr(), _stream(gy))
         return gx
 
 
@@ -1709,7 +1647,7 @@ def max_pool(pool, x):
     fp16 NCHW input."""
     def _is(v, k):
         return v == k or v == (k, k)
-    if (ENABLED['maxpool'] and x.is_cuda and (x.dtype == torch.bfloat16 or (x.dtype == torch.float16 and ENABLED['fp16_tail']))
+    if (ENABLED['maxpool'] and x.is_cuda and takes_16(x.dtype, 'fp16_tail')
             and x.dim() == 4 and x.numel() > 0
             and isinstance(pool, torch.nn.MaxPool2d) and _is(pool.kernel_size, 3) and _is(pool.stride, 2)
             and _is(pool.padding, 1) and _is(pool.dilation, 1) and not pool.ceil_mode and not pool.return_indices):

@@ -17,12 +17,7 @@ def _stream(t):
 _ATTN_DTYPES = (torch.bfloat16, torch.float16)
 
 
-def _call(name, dtype, *args):
-    """Calls C entry point `name` (its bf16 form: 'vah_attn_fwd_bf16', 'vah_relpos_bias_build', ...) for 16-bit operands of
-    `dtype` - the fp16 twins carry the same signature under an _f16 name - and raises on a non-zero return code."""
-    if dtype == torch.float16:
-        name = (name[:-len('_bf16')] if name.endswith('_bf16') else name) + '_f16'
-    _vah.check(getattr(_vah.lib, name)(*args), name)
+_call = _vah.call      # (bf16 spelling of the entry point, dtype of the 16-bit operands, *args): raises on a non-zero return code
 
 
 def _attention_math(qkv, scale, dropout_p=0.):

@@ -23,11 +23,6 @@ def _stream(t):
     return _vah.raw_stream(t.device)
 
 
-def _sym(name, dtype):
-    """The entry point ``name`` (its bf16 spelling) for 16-bit operands of ``dtype``: itself or its `_f16` twin."""
-    return conv._sym(name, dtype)[0]
-
-
 def image_to_nhwc16(x, dtype=torch.bfloat16):
     """(N, 3, H, W) fp32 -> (N, H, W, 16) ``dtype`` (bf16 | fp16) with channels 3..15 zero (no gradient: the image is a
     leaf input)."""
@@ -36,7 +31,7 @@ def image_to_nhwc16(x, dtype=torch.bfloat16):
     x = x.contiguous()
     y = torch.empty((N, H, W, 16), dtype=dtype, device=x.device)
     with _vah.on(x.device):
-        _vah.check(_sym('vah_image_to_nhwc16_bf16', dtype)(x.data_ptr(), N, H, W, y.data_ptr(), _stream(x)), 'image_to_nhwc16')
+        _vah.call('vah_image_to_nhwc16_bf16', dtype, x.data_ptr(), N, H, W, y.data_ptr(), _stream(x))
     return y
 
 
@@ -84,7 +79,7 @@ class _BNRelu(torch.autograd.Function):
             if training:
                 sums = torch.empty(2 * C + 1, dtype=torch.float32, device=dev)
                 ws = torch.empty(_vah.lib.vah_bn_nhwc_ws_floats(C), dtype=torch.float32, device=dev)
-                _vah.check(_sym('vah_bn_nhwc_stats', x.dtype)(x.data_ptr(), rows, C, sums.data_ptr(), ws.data_ptr(), st), 'bn_nhwc_stats')
+                _vah.call('vah_bn_nhwc_stats', x.dtype, x.data_ptr(), rows, C, sums.data_ptr(), ws.data_ptr(), st)
                 sums[2 * C:].fill_(float(rows))
                 if group is not None:
                     import torch.distributed as dist
@@ -105,10 +100,8 @@ class _BNRelu(torch.autograd.Function):
                 mean = norm.running_mean.float().contiguous()
                 rstd = torch.rsqrt(norm.running_var.float() + norm.eps)
             y = torch.empty_like(x)
-            _vah.check(_sym('vah_bn_nhwc_apply', x.dtype)(x.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(),
-                                                          w.data_ptr() if w is not None else None,
-                                                          b.data_ptr() if b is not None else None, int(relu), y.data_ptr(), st),
-                       'bn_nhwc_apply')
+            _vah.call('vah_bn_nhwc_apply', x.dtype, x.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(), w.data_ptr() if w is not None else None,
+                      b.data_ptr() if b is not None else None, int(relu), y.data_ptr(), st)
         ctx.save_for_backward(x, mean, rstd, w, b, count)
         ctx.meta = (training, group, weight is not None, bias is not None, relu)
         return y
@@ -126,9 +119,8 @@ class _BNRelu(torch.autograd.Function):
         with _vah.on(dev):
             sums = torch.empty(2 * C, dtype=torch.float32, device=dev)
             ws = torch.empty(_vah.lib.vah_bn_nhwc_ws_floats(C), dtype=torch.float32, device=dev)
-            _vah.check(_sym('vah_bn_nhwc_bwd_stats', x.dtype)(x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(),
-                                                              rstd.data_ptr(), wp, bp, int(relu), sums.data_ptr(), ws.data_ptr(),
-                                                              st), 'bn_nhwc_bwd_stats')
+            _vah.call('vah_bn_nhwc_bwd_stats', x.dtype, x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(), wp, bp, int(relu),
+                      sums.data_ptr(), ws.data_ptr(), st)
             local = sums.clone() if (training and group is not None) else sums      # dweight / dbias are per-rank sums
             dweight = local[C:] if has_w else None
             dbias = local[:C] if has_b else None
@@ -142,9 +134,8 @@ class _BNRelu(torch.autograd.Function):
                 else:
                     means = torch.zeros_like(sums)          # running statistics are constants
                 dx = torch.empty_like(x)
-                _vah.check(_sym('vah_bn_nhwc_bwd_apply', x.dtype)(x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(),
-                                                                  rstd.data_ptr(), wp, bp, int(relu), means[:C].data_ptr(),
-                                                                  means[C:].data_ptr(), dx.data_ptr(), st), 'bn_nhwc_bwd_apply')
+                _vah.call('vah_bn_nhwc_bwd_apply', x.dtype, x.data_ptr(), dy.data_ptr(), rows, C, mean.data_ptr(), rstd.data_ptr(), wp, bp,
+                          int(relu), means[:C].data_ptr(), means[C:].data_ptr(), dx.data_ptr(), st)
         return dx, dweight, dbias, None, None
 
 
@@ -158,8 +149,7 @@ class _MaxPool(torch.autograd.Function):
         y = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
         idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
         with _vah.on(x.device):
-            _vah.check(_sym('vah_maxpool3s2_nhwc_fwd_bf16', x.dtype)(x.data_ptr(), N, H, W, C, y.data_ptr(), idx.data_ptr(),
-                                                                     _stream(x)), 'maxpool_nhwc_fwd')
+            _vah.call('vah_maxpool3s2_nhwc_fwd_bf16', x.dtype, x.data_ptr(), N, H, W, C, y.data_ptr(), idx.data_ptr(), _stream(x))
         ctx.save_for_backward(idx)
         ctx.in_shape, ctx.in_dtype = x.shape, x.dtype
         return y
@@ -171,8 +161,7 @@ class _MaxPool(torch.autograd.Function):
         gy = gy.contiguous().to(ctx.in_dtype)
         gx = torch.empty(ctx.in_shape, dtype=ctx.in_dtype, device=gy.device)
         with _vah.on(gy.device):
-            _vah.check(_sym('vah_maxpool3s2_nhwc_bwd_bf16', ctx.in_dtype)(gy.data_ptr(), idx.data_ptr(), N, H, W, C, gx.data_ptr(),
-                                                                          _stream(gy)), 'maxpool_nhwc_bwd')
+            _vah.call('vah_maxpool3s2_nhwc_bwd_bf16', ctx.in_dtype, gy.data_ptr(), idx.data_ptr(), N, H, W, C, gx.data_ptr(), _stream(gy))
         return gx
 
 
@@ -213,12 +202,7 @@ class _Conv1x1ToPlanes(torch.autograd.Function):
 def autocast_dtype():
     """The 16-bit type the NHWC path runs in under the active autocast: torch.bfloat16, torch.float16, or None (no
     autocast, another autocast type, or fp16 with its switch off: VAH_FUSED_DISABLE=fp16_spm, for A/B runs)."""
-    if not torch.is_autocast_enabled():
-        return None
-    dtype = torch.get_autocast_dtype('cuda')
-    if dtype == torch.bfloat16 or (dtype == torch.float16 and fused.ENABLED['fp16_spm']):
-        return dtype
-    return None
+    return fused.autocast_16('fp16_spm')
 
 
 def takes(spm, x, fold):
