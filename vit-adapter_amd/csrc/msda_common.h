@@ -19,15 +19,20 @@ __device__ __forceinline__ Tap<T> make_tap(T lx, T ly, int H, int W) {
     Tap<T> t;
     const T h_im = ly * (T)H - (T)0.5;
     const T w_im = lx * (T)W - (T)0.5;
-    // strict gate of the reference (cuh:288); NaN locations fail every comparison.
-    const bool inside = h_im > (T)-1 && w_im > (T)-1 && h_im < (T)H && w_im < (T)W;
-    const T hs = inside ? h_im : (T)0;
-    const T ws = inside ? w_im : (T)0;
+    // strict gate of the reference (cuh:288); NaN and +-inf locations fail it.  They are not dropped as a sample outside
+    // the map is: `bad` is 0 for finite coordinates and NaN otherwise, such a sample sits on pixel (0, 0) - an address
+    // that exists - with NaN fractions, so its four weights, the output and every gradient it feeds are NaN, as
+    // torch's grid_sample makes them (GradScaler has to see an overflowed offset).
+    const bool gate = h_im > (T)-1 && w_im > (T)-1 && h_im < (T)H && w_im < (T)W;
+    const T bad = (h_im - h_im) + (w_im - w_im);
+    const bool inside = gate || bad != bad;
+    const T hs = gate ? h_im : (T)0;
+    const T ws = gate ? w_im : (T)0;
     const T hf = floor(hs), wf = floor(ws);
     const int h_low = (int)hf, w_low = (int)wf;
     const int h_high = h_low + 1, w_high = w_low + 1;
-    t.lh = hs - hf;
-    t.lw = ws - wf;
+    t.lh = hs - hf + bad;
+    t.lw = ws - wf + bad;
     t.hh = (T)1 - t.lh;
     t.hw = (T)1 - t.lw;
     t.cw[0] = t.hh * t.hw;

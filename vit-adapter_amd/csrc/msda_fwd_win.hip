@@ -321,11 +321,14 @@ __global__ __launch_bounds__(kWinThreads) void msda_fused_fwd_win(
                 // the same expressions as msda_fused_fwd: ref + off / W, then make_tap's arithmetic
                 const float lx = rp.x + word_elem<PT>(ow, 2 * p) / (float)W, ly = rp.y + word_elem<PT>(ow, 2 * p + 1) / (float)H;
                 const float h_im = ly * (float)H - 0.5f, w_im = lx * (float)W - 0.5f;
-                const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-                const float hs = inside ? h_im : 0.f, wsx = inside ? w_im : 0.f;
+                // (a NaN or +-inf coordinate: pixel (0, 0) with NaN fractions, see make_tap)
+                const bool gate = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
+                const float bad = (h_im - h_im) + (w_im - w_im);
+                const bool inside = gate || bad != bad;
+                const float hs = gate ? h_im : 0.f, wsx = gate ? w_im : 0.f;
                 const float hf = floorf(hs), wf = floorf(wsx);
                 const int y0 = (int)hf, x0 = (int)wf;
-                const float lh = hs - hf, lwt = wsx - wf, hh = 1.f - lh, hw = 1.f - lwt;
+                const float lh = hs - hf + bad, lwt = wsx - wf + bad, hh = 1.f - lh, hw = 1.f - lwt;
                 const float cw[4] = {hh * hw, hh * lwt, lh * hw, lh * lwt};
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {

@@ -550,14 +550,17 @@ __device__ __forceinline__ Base make_base(float lx, float ly, int H, int W) {
     Base b;
     const float h_im = ly * (float)H - 0.5f;
     const float w_im = lx * (float)W - 0.5f;
-    b.inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-    const float hs = b.inside ? h_im : 0.f;
-    const float ws = b.inside ? w_im : 0.f;
+    // a NaN or +-inf coordinate fails the gate but is not dropped: pixel (0, 0) with NaN fractions (msda_common.h::make_tap)
+    const bool gate = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
+    const float bad = (h_im - h_im) + (w_im - w_im);
+    b.inside = gate || bad != bad;
+    const float hs = gate ? h_im : 0.f;
+    const float ws = gate ? w_im : 0.f;
     const float hf = floorf(hs), wf = floorf(ws);
     b.y0 = (int)hf;
     b.x0 = (int)wf;
-    b.lh = hs - hf;
-    b.lw = ws - wf;
+    b.lh = hs - hf + bad;
+    b.lw = ws - wf + bad;
     return b;
 }
 

@@ -196,7 +196,8 @@ __global__ __launch_bounds__(256) void bn_nhwc_apply_kernel(const T *__restrict_
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float t = (float)v[j] * sc[j] + sh[j];
-            o[j] = (T)(relu ? fmaxf(t, 0.f) : t);
+            // IEEE maximum (one v_maximum3_f32), not fmaxf (which returns the other operand for a NaN): relu(NaN) = NaN
+            o[j] = (T)(relu ? __builtin_elementwise_maximum(t, 0.f) : t);
         }
         *reinterpret_cast<vec8<T> *>(y + i * 8) = o;
     }
@@ -231,7 +232,8 @@ __global__ __launch_bounds__(256) void bn_nhwc_bwd_apply_kernel(const T *__restr
 }
 
 // MaxPool2d(3, 2, 1) on (N, H, W, C): output piece = 8 channels of one output pixel; idx = window position 0..8 of the
-// first maximum in scan order (what torch's max_pool2d sends the gradient to)
+// first maximum in scan order (what torch's max_pool2d sends the gradient to); a NaN in the window is the result, and
+// idx the position of the window's last NaN (torch's rule: `val > max || isnan(val)`)
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_nhwc_fwd_kernel(const T *__restrict__ x, int N, int H, int W, int C, int OH,
                                                                int OW, T *__restrict__ y, uint8_t *__restrict__ idx) {
@@ -255,7 +257,8 @@ __global__ __launch_bounds__(256) void maxpool_nhwc_fwd_kernel(const T *__restri
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float f = (float)v[j];
-            if (f > best[j]) best[j] = f, bi[j] = (uint8_t)k;      // strict: ties keep the first position
+            // strict: ties keep the first position; a NaN takes the window (and its position), as torch's max_pool2d
+            if (f > best[j] || f != f) best[j] = f, bi[j] = (uint8_t)k;
         }
     }
     vec8<T> o;

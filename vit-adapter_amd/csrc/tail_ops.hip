@@ -240,6 +240,8 @@ __device__ __forceinline__ float block_sum(float v, float *s_red) {      // 256 
     return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
+__device__ __forceinline__ float nanmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 // part[(n * chunks + chunk)][2C]: (sum t | sum t^2) of the block's pixels, for its channel only.  The C planes of
 // one (n, chunk) between them write every column of its row and tail_finalize reads the N * chunks (<= kTailParts)
 // rows that were written and no other, so the partial buffer needs no initialisation.
@@ -284,9 +286,11 @@ __global__ __launch_bounds__(256) void tail_apply_kernel(Operands o, const float
     for (int i = threadIdx.x; i < (r1 - r0) * wv4; i += 256) {
         const int iy = wv4 == 1 ? i : (int)__umulhi((unsigned)i, o.quad_magic), yy = r0 + iy, x4 = (i - iy * wv4) * 4;
         const float4 t = sum4<T>(o, plane, yy, x4);
+        // nanmax: IEEE maximum (one v_maximum3_f32), not fmaxf (which returns the other operand for a NaN): a NaN
+        // result (an inf or NaN anywhere in the channel makes the batch variance NaN) stays NaN under the ReLU
         store4<T>(y, (plane * o.H + yy) * o.W + x4, o.y_bf16,
-               make_float4(fmaxf(t.x * sc + sh, lo), fmaxf(t.y * sc + sh, lo), fmaxf(t.z * sc + sh, lo),
-                           fmaxf(t.w * sc + sh, lo)));
+               make_float4(nanmax(t.x * sc + sh, lo), nanmax(t.y * sc + sh, lo), nanmax(t.z * sc + sh, lo),
+                           nanmax(t.w * sc + sh, lo)));
     }
 }
 
@@ -444,7 +448,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float *__restric
     if (c >= C) return;
     const float count = sums[2 * C];
     const float mu = sums[c] / count;
-    const float var = fmaxf(sums[C + c] / count - mu * mu, 0.f);
+    // nanmax: an inf or NaN in the channel gives a NaN variance, and BatchNorm then a NaN channel (as torch's)
+    const float var = nanmax(sums[C + c] / count - mu * mu, 0.f);
     mean[c] = mu;
     rstd[c] = rsqrtf(var + eps);
     if (running_mean) {
