@@ -739,71 +739,141 @@ struct Maps {          // token ranges [t0, t1) of the 3 maps and their (h, w)
 
 __device__ __forceinline__ int map_of(const Maps &mp, int tok) { return tok >= mp.t[2] ? 2 : (tok >= mp.t[1] ? 1 : 0); }
 
+// Work item of the depthwise kernels: one pixel column of a strip of R rows of one map of one image, for one group of
+// 4 channels.  Items are numbered image by image, map by map, strip by strip, left to right, so the token slots of a
+// workgroup are neighbouring columns and share their left / right neighbour rows in L1.  An item never leaves its map.
+__host__ __device__ inline int dw_items_per_image(const Maps &mp, int R) {
+    int n = 0;
+    for (int m = 0; m < 3; ++m) n += (mp.h[m] + R - 1) / R * mp.w[m];
+    return n;
+}
+
+struct DwItem {
+    int64_t tok0;      // first token of the item's map in its image, counted over the whole (B, N) tensor
+    int H, W, y0, px;  // the map's size, the strip's first row, the column
+};
+
+template <int R>
+__device__ __forceinline__ DwItem dw_item(const Maps &mp, int N, int items_per_img, int item) {
+    const int b = item / items_per_img;
+    int r = item - b * items_per_img, m = 0;
+    for (; m < 2; ++m) {
+        const int n = (mp.h[m] + R - 1) / R * mp.w[m];
+        if (r < n) break;
+        r -= n;
+    }
+    DwItem it;
+    it.H = mp.h[m], it.W = mp.w[m];
+    const int strip = r / it.W;
+    it.px = r - strip * it.W;
+    it.y0 = strip * R;
+    it.tok0 = (int64_t)b * N + mp.t[m];
+    return it;
+}
+
+// The R + 2 rows x 3 columns of neighbours an item needs, every one requested before the first is used.  Coordinates
+// are clamped into the map (the taps outside get a zero weight), so no load sits under a condition: loads under
+// `if (inside)` each got their own s_waitcnt vmcnt(0).
+template <typename T, int R>
+__device__ __forceinline__ void dw_load_window(const T *__restrict__ x, const DwItem &it, int C, int cv, vec4<T> (&v)[R + 2][3]) {
+    const T *base = x + it.tok0 * C + 4 * cv;
+#pragma unroll
+    for (int j = 0; j < R + 2; ++j) {
+        const int yc = min(max(it.y0 + j - 1, 0), it.H - 1);
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int xc = min(max(it.px + dx - 1, 0), it.W - 1);
+            v[j][dx] = *reinterpret_cast<const vec4<T> *>(base + (int64_t)(yc * it.W + xc) * C);
+        }
+    }
+}
+
+constexpr int kDwRows = 8;       // rows per item, forward and input gradient: 30 loads for 8 outputs (a thread per
+                                 // output took 9 each, and paid the 36 tap loads of its prologue for 2 outputs)
+constexpr int kDwRowsWgrad = 4;  // weight gradient: 18 + 4 loads for 4 tokens; shorter strips spread the items evenly
+                                 // over the at most kMaxParts workgroups
+
 // mode 0: out = conv(x) + bias      (weights as given)
 // mode 1: out = conv with the flipped kernel (input gradient), no bias
-// Thread = (token slot, channel group of 4): the 36 filter taps of its channels stay in registers
-// while it walks tokens with a grid stride (a per-output reload of the taps made the kernel
-// 8x slower than its memory traffic allows).
+// Thread = (item, channel group of 4): the 36 filter taps of its channels stay in registers while it walks down its
+// column; each output is the same sum in the same order as one thread per output gave (bias, taps 0..8, one cast).
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void dwconv_kernel(const T *__restrict__ x,
                                                      const float *__restrict__ w,
                                                      const float *__restrict__ bias, Maps mp, int N,
-                                                     int C, int64_t total_tok, T *__restrict__ y) {
+                                                     int C, int items_per_img, int total_items, T *__restrict__ y) {
+    constexpr int R = kDwRows;
     const int nvec = C >> 2;
     const int slots = 256 / nvec;
     const int slot = threadIdx.x / nvec, cv = threadIdx.x - slot * nvec;
-    if (slot >= slots) return;
+    const int item = (int)blockIdx.x * slots + slot;
+    if (slot >= slots || item >= total_items) return;
+    const DwItem it = dw_item<R>(mp, N, items_per_img, item);
+    // the 36 taps of 4 channels are 144 contiguous bytes
+    float wr[36];
+    const float *wp = w + 36 * cv;
+    if (((uintptr_t)w & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            const float4 t = *reinterpret_cast<const float4 *>(wp + 4 * q);
+            wr[4 * q] = t.x, wr[4 * q + 1] = t.y, wr[4 * q + 2] = t.z, wr[4 * q + 3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 36; ++k) wr[k] = wp[k];
+    }
+    // flipped taps and the column's left / right border folded into the weights once
+    const bool in_l = it.px > 0, in_r = it.px + 1 < it.W;
     float wt[4][9];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-        for (int t = 0; t < 9; ++t) wt[c][t] = w[(4 * cv + c) * 9 + (MODE == 0 ? t : 8 - t)];
+        for (int t = 0; t < 9; ++t) {
+            const float v = wr[c * 9 + (MODE == 0 ? t : 8 - t)];
+            wt[c][t] = t % 3 == 0 ? (in_l ? v : 0.f) : (t % 3 == 2 ? (in_r ? v : 0.f) : v);
+        }
     float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (MODE == 0 && bias) b4 = *reinterpret_cast<const float4 *>(bias + 4 * cv);
-    for (int64_t tokg = (int64_t)blockIdx.x * slots + slot; tokg < total_tok; tokg += (int64_t)gridDim.x * slots) {
-        const int64_t b = (int)tokg / N;              // total_tok < 2^31 (checked by the host): 32-bit divisions
-        const int tok = (int)tokg - (int)b * N;
-        const int m = map_of(mp, tok);
-        const int H = mp.h[m], W = mp.w[m], t0 = mp.t[m];
-        const int py = (tok - t0) / W, px = (tok - t0) - py * W;
+    vec4<T> v[R + 2][3];
+    dw_load_window<T, R>(x, it, C, cv, v);
+    __builtin_amdgcn_sched_barrier(0);                  // keep the loads above their uses (the scheduler sank them)
+    T *yp = y + (it.tok0 + (int64_t)it.y0 * it.W + it.px) * C + 4 * cv;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int py = it.y0 + r;
         float4 acc = b4;
-        // all 9 neighbour rows are requested before the first is used (clamped coordinates, zero weight
-        // outside the map): loads under `if (inside)` each got their own s_waitcnt vmcnt(0)
-        vec4<T> v[9];
-        bool in[9];
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
-            in[tap] = yy >= 0 && yy < H && xx >= 0 && xx < W;
-            const int yc = min(max(yy, 0), H - 1), xc = min(max(xx, 0), W - 1);
-            v[tap] = *reinterpret_cast<const vec4<T> *>(x + ((b * N + t0 + (int64_t)yc * W + xc) * C + 4 * cv));
-        }
-        __builtin_amdgcn_sched_barrier(0);                  // keep the 9 loads above their uses (the scheduler sank them)
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {                 // flipped taps already folded into wt
-            acc.x += (in[tap] ? wt[0][tap] : 0.f) * (float)v[tap][0];
-            acc.y += (in[tap] ? wt[1][tap] : 0.f) * (float)v[tap][1];
-            acc.z += (in[tap] ? wt[2][tap] : 0.f) * (float)v[tap][2];
-            acc.w += (in[tap] ? wt[3][tap] : 0.f) * (float)v[tap][3];
+            // row above: outside only for the first row of the map; row below: outside for the last
+            const bool in = tap < 3 ? (r > 0 || it.y0 > 0) : (tap < 6 ? true : py + 1 < it.H);
+            const vec4<T> &n = v[r + tap / 3][tap % 3];
+            acc.x += (in ? wt[0][tap] : 0.f) * (float)n[0];
+            acc.y += (in ? wt[1][tap] : 0.f) * (float)n[1];
+            acc.z += (in ? wt[2][tap] : 0.f) * (float)n[2];
+            acc.w += (in ? wt[3][tap] : 0.f) * (float)n[3];
         }
         vec4<T> o;
         o[0] = (T)acc.x;
         o[1] = (T)acc.y;
         o[2] = (T)acc.z;
         o[3] = (T)acc.w;
-        *reinterpret_cast<vec4<T> *>(y + tokg * C + 4 * cv) = o;
+        // a strip may end below the map; its first row never does (said so that the row above it is not loaded under
+        // this condition, after the wait for all the other rows)
+        if (r == 0 || py < it.H) *reinterpret_cast<vec4<T> *>(yp + (int64_t)r * it.W * C) = o;
     }
 }
 
-// dw[c][tap] = sum_tok g[tok,c] * x[neighbour(tok,tap), c];  db[c] = sum g.  Thread = (token slot,
-// channel group): walks tokens with a grid stride, 40 partial sums in registers; the slots of a
-// workgroup are summed through LDS into one partial row [dw (C*9) | db (C)].
+// dw[c][tap] = sum_tok g[tok,c] * x[neighbour(tok,tap), c];  db[c] = sum g.  Thread = (token slot, channel group):
+// walks items with a grid stride, 40 partial sums in registers; the slots of a workgroup are summed through LDS into
+// one partial row [dw (C*9) | db (C)].  Items, slots and the order of every sum are fixed by the shape: two calls
+// agree bit for bit.
 template <typename T>
 __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const T *__restrict__ x,
                                                            const T *__restrict__ g, Maps mp, int N,
-                                                           int C, int64_t total_tok,
+                                                           int C, int items_per_img, int total_items,
                                                            float *__restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float s_red[];      // [slots][C*10]
+    constexpr int R = kDwRowsWgrad;
     const int nvec = C >> 2;
     const int slots = 256 / nvec;                    // token slots per block (>= 1 when C <= 1024)
     const int slot = threadIdx.x / nvec, cv = threadIdx.x - slot * nvec;
@@ -814,29 +884,33 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const T *__restrict__
 #pragma unroll
         for (int t = 0; t < 9; ++t) aw[c][t] = 0.f;
     if (live)
-        for (int64_t tokg = (int64_t)blockIdx.x * slots + slot; tokg < total_tok; tokg += (int64_t)gridDim.x * slots) {
-            const int tok = (int)(tokg % N);
-            const int64_t b = tokg / N;
-            const int m = map_of(mp, tok);
-            const int H = mp.h[m], W = mp.w[m], t0 = mp.t[m];
-            const int py = (tok - t0) / W, px = (tok - t0) - py * W;
-            const vec4<T> gv = *reinterpret_cast<const vec4<T> *>(g + tokg * C + 4 * cv);
-            const float gf[4] = {(float)gv[0], (float)gv[1], (float)gv[2], (float)gv[3]};
+        for (int item = (int)blockIdx.x * slots + slot; item < total_items; item += (int)gridDim.x * slots) {
+            const DwItem it = dw_item<R>(mp, N, items_per_img, item);
+            const bool in_l = it.px > 0, in_r = it.px + 1 < it.W;
+            vec4<T> v[R + 2][3], gv[R];
+            dw_load_window<T, R>(x, it, C, cv, v);
+            const T *gp = g + (it.tok0 + it.px) * C + 4 * cv;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) ab[c] += gf[c];
-            vec4<T> v[9];                                        // all 9 neighbour rows in flight at once
-            bool in[9];
+            for (int r = 0; r < R; ++r)                       // rows past the map's last: its last row again, weight zero
+                gv[r] = *reinterpret_cast<const vec4<T> *>(gp + (int64_t)min(it.y0 + r, it.H - 1) * it.W * C);
 #pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
-                in[tap] = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                const int yc = min(max(yy, 0), H - 1), xc = min(max(xx, 0), W - 1);
-                v[tap] = *reinterpret_cast<const vec4<T> *>(x + ((b * N + t0 + (int64_t)yc * W + xc) * C + 4 * cv));
+            for (int r = 0; r < R; ++r) {
+                const int py = it.y0 + r;
+                const bool row = py < it.H;
+                float gf[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    gf[c] = row ? (float)gv[r][c] : 0.f;
+                    ab[c] += gf[c];
+                }
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) {
+                    const bool in = (tap < 3 ? (r > 0 || it.y0 > 0) : (tap < 6 ? true : py + 1 < it.H)) &&
+                                    (tap % 3 == 0 ? in_l : (tap % 3 == 2 ? in_r : true));
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) aw[c][tap] += (in ? gf[c] : 0.f) * (float)v[r + tap / 3][tap % 3][c];
+                }
             }
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) aw[c][tap] += (in[tap] ? gf[c] : 0.f) * (float)v[tap][c];
         }
     const int K = C * 10;
     if (live) {
@@ -1366,16 +1440,19 @@ int dwconv_tokens(const char *fn, const void *x, const float *w, const float *bi
     const int64_t total_tok = B * N;
     if (total_tok >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "%s: too many tokens", fn);
     const int slots = 256 / (int)(C / 4);
+    const int items_per_img = dw_items_per_image(mp, kDwRows);
+    const int total_items = (int)(B * items_per_img);                  // at most one item per token
+    const dim3 grid((unsigned)((total_items + slots - 1) / slots));
     hipStream_t st = (hipStream_t)stream;
     LaunchScope scope(mode == 0 ? tname<T>("dwconv_tokens_fwd", "dwconv_tokens_fwd_f16")
                                 : tname<T>("dwconv_tokens_dgrad", "dwconv_tokens_dgrad_f16"),
                       total_tok * C * 4, st);
     if (mode == 0)
-        hipLaunchKernelGGL((dwconv_kernel<T, 0>), dim3(grid_for(total_tok, slots * 2)), dim3(256), 0, st,
-                           (const T *)x, w, bias, mp, N, (int)C, total_tok, (T *)y);
+        hipLaunchKernelGGL((dwconv_kernel<T, 0>), grid, dim3(256), 0, st,
+                           (const T *)x, w, bias, mp, N, (int)C, items_per_img, total_items, (T *)y);
     else
-        hipLaunchKernelGGL((dwconv_kernel<T, 1>), dim3(grid_for(total_tok, slots * 2)), dim3(256), 0, st,
-                           (const T *)x, w, bias, mp, N, (int)C, total_tok, (T *)y);
+        hipLaunchKernelGGL((dwconv_kernel<T, 1>), grid, dim3(256), 0, st,
+                           (const T *)x, w, bias, mp, N, (int)C, items_per_img, total_items, (T *)y);
     return check_launch(fn);
 }
 
@@ -1397,8 +1474,11 @@ int dwconv_tokens_wgrad(const char *fn, const void *x, const void *g, int64_t B,
     const Maps mp = maps_of(H, W);
     const int N = mp.t[3];
     const int64_t total_tok = B * N;
+    if (total_tok >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "%s: too many tokens", fn);
     const int slots = 256 / (int)(C / 4);
-    int64_t nblocks = (total_tok + slots * 16 - 1) / (slots * 16);
+    const int items_per_img = dw_items_per_image(mp, kDwRowsWgrad);
+    const int total_items = (int)(B * items_per_img);                  // at most one item per token
+    int64_t nblocks = (total_items + slots - 1) / slots;
     if (nblocks > kMaxParts) nblocks = kMaxParts;
     if (nblocks < 1) nblocks = 1;
     const size_t smem = (size_t)slots * C * 10 * sizeof(float);
@@ -1406,7 +1486,7 @@ int dwconv_tokens_wgrad(const char *fn, const void *x, const void *g, int64_t B,
     if (int rc = allow_dynamic_lds((const void *)dwconv_wgrad_kernel<T>, 160 * 1024 - 512, fn)) return rc;
     LaunchScope scope(tname<T>("dwconv_tokens_wgrad", "dwconv_tokens_wgrad_f16"), total_tok * C * 4, st);
     hipLaunchKernelGGL(dwconv_wgrad_kernel<T>, dim3((unsigned)nblocks), dim3(256), smem, st,
-                       (const T *)x, (const T *)g, mp, N, (int)C, total_tok, ws);
+                       (const T *)x, (const T *)g, mp, N, (int)C, items_per_img, total_items, ws);
     hipLaunchKernelGGL(finalize_partials, dim3((unsigned)((10 * C + 31) / 32)), dim3(256), 0, st, ws,
                        (int)nblocks, (int)(10 * C), dw, (int)(9 * C), db, 1 << 30, (float *)nullptr);
     return check_launch(fn);

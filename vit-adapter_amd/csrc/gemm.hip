@@ -173,9 +173,31 @@ size_t partial_bytes(const Key &k, int split) {
     return split > 1 ? ((size_t)split * k.M * k.N * sizeof(float) + 255) / 256 * 256 : 0;
 }
 
+// G slices of one float4 position: all G loads are issued, then added to `acc` in slice order (FIRST: the first of
+// them starts the sum), so the result is the one chain p0 + p1 + ... whatever the grouping.
+template <int G, bool FIRST>
+__device__ __forceinline__ void add_slices(const float *__restrict__ p, int64_t MN, float4 &acc) {
+    float4 v[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) v[u] = *reinterpret_cast<const float4 *>(p + u * MN);
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+        if (FIRST && u == 0) {
+            acc = v[0];
+        } else {
+            acc.x += v[u].x;
+            acc.y += v[u].y;
+            acc.z += v[u].z;
+            acc.w += v[u].w;
+        }
+    }
+}
+
+// vec (decided by the host): N, ldd and the output pointer allow one 16-byte (fp32) or 8-byte (16-bit) store per
+// position; otherwise four scalar stores.
 template <typename OT>
 __global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ part, int split, int64_t MN, int N,
-                                                     int64_t ldd, OT *__restrict__ out, int reduce_blocks,
+                                                     int64_t ldd, int vec, OT *__restrict__ out, int reduce_blocks,
                                                      const float *__restrict__ fin_part, int fin_nparts, int fin_C,
                                                      float *__restrict__ fin_out) {
     if ((int)blockIdx.x >= reduce_blocks) {
@@ -203,20 +225,53 @@ __global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ p
         return;
     }
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < MN; i += (int64_t)reduce_blocks * 1024) {
-        float4 acc = *reinterpret_cast<const float4 *>(part + i);
-        for (int s = 1; s < split; ++s) {
-            const float4 v = *reinterpret_cast<const float4 *>(part + s * MN + i);
-            acc.x += v.x;
-            acc.y += v.y;
-            acc.z += v.z;
-            acc.w += v.w;
+        // the largest power-of-two group first (the table's splits are powers of two: one group of loads up to 8,
+        // groups of 8 beyond), then what is left in groups of 8, 4, 2, 1
+        const float *p = part + i;
+        float4 acc;
+        int s;
+        if (split >= 8) {
+            add_slices<8, true>(p, MN, acc);
+            s = 8;
+        } else if (split >= 4) {
+            add_slices<4, true>(p, MN, acc);
+            s = 4;
+        } else if (split >= 2) {
+            add_slices<2, true>(p, MN, acc);
+            s = 2;
+        } else {
+            add_slices<1, true>(p, MN, acc);
+            s = 1;
         }
-        const int64_t row = i / N;
-        OT *o = out + row * ldd + (i - row * N);
-        o[0] = (OT)acc.x;
-        o[1] = (OT)acc.y;
-        o[2] = (OT)acc.z;
-        o[3] = (OT)acc.w;
+        for (; s + 8 <= split; s += 8) add_slices<8, false>(p + s * MN, MN, acc);
+        if (s + 4 <= split) {
+            add_slices<4, false>(p + s * MN, MN, acc);
+            s += 4;
+        }
+        if (s + 2 <= split) {
+            add_slices<2, false>(p + s * MN, MN, acc);
+            s += 2;
+        }
+        if (s < split) add_slices<1, false>(p + s * MN, MN, acc);
+        int64_t o = i;                                 // ldd == N: D is the same flat array
+        if (ldd != N) {
+            const int64_t row = i / N;
+            o = row * ldd + (i - row * N);
+        }
+        typedef OT ov4 __attribute__((ext_vector_type(4)));
+        ov4 r;
+        r[0] = (OT)acc.x;
+        r[1] = (OT)acc.y;
+        r[2] = (OT)acc.z;
+        r[3] = (OT)acc.w;
+        if (vec) {
+            *reinterpret_cast<ov4 *>(out + o) = r;
+        } else {
+            out[o] = r[0];
+            out[o + 1] = r[1];
+            out[o + 2] = r[2];
+            out[o + 3] = r[3];
+        }
     }
 }
 
@@ -359,17 +414,21 @@ hipblasStatus_t run(State &S, const Call &c, Problem &p, const hipblasLtMatmulAl
     const bool fin = c.fin_part != nullptr;
     if (split == 1 && !fin) return s;
     const int64_t MN = c.k.M * c.k.N;
-    const unsigned rblocks = split > 1 ? (unsigned)std::min<int64_t>(2048, (MN / 4 + 255) / 256) : 0u;
+    // one float4 position per thread up to 8192 workgroups (the largest product of the table, 3072 x 768, takes 2304):
+    // with a lower cap a part of the threads ran a second position after the others had finished
+    const unsigned rblocks = split > 1 ? (unsigned)std::min<int64_t>(8192, (MN / 4 + 255) / 256) : 0u;
     const unsigned fblocks = fin ? (unsigned)((c.fin_C + 31) / 32) : 0u;
+    // a position is 4 consecutive elements of one row (N % 4 == 0): it leaves as one store where every row starts aligned
+    const int vec = c.k.N % 4 == 0 && c.k.ldd % 4 == 0 && (uintptr_t)c.D % (c.k.d32 ? 16 : 8) == 0;
     if (c.k.d32)
         hipLaunchKernelGGL(reduce_splits<float>, dim3(rblocks + fblocks), dim3(256), 0, c.st, (const float *)c.ws, split, MN,
-                           (int)c.k.N, c.k.ldd, (float *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
+                           (int)c.k.N, c.k.ldd, vec, (float *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
     else if (c.k.f16)
         hipLaunchKernelGGL(reduce_splits<_Float16>, dim3(rblocks + fblocks), dim3(256), 0, c.st, (const float *)c.ws, split, MN,
-                           (int)c.k.N, c.k.ldd, (_Float16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
+                           (int)c.k.N, c.k.ldd, vec, (_Float16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
     else
         hipLaunchKernelGGL(reduce_splits<__bf16>, dim3(rblocks + fblocks), dim3(256), 0, c.st, (const float *)c.ws, split, MN,
-                           (int)c.k.N, c.k.ldd, (__bf16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
+                           (int)c.k.N, c.k.ldd, vec, (__bf16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
     return HIPBLAS_STATUS_SUCCESS;
 }
 
