@@ -1,14 +1,9 @@
 // Shared pieces of the 16-bit MFMA attention kernels (gfx950, head_dim 64).
 //
-// The kernels are templates on the 16-bit element type T of q, k, v, out and the gradients: __bf16 (bf16 autocast) or
-// _Float16 (fp16 autocast).  v_mfma_f32_32x32x16_bf16 and _f16 share operand layout and cycles, ds_read_b64_tr_b16
-// reads either type: only the typedefs, mfma() and the float -> T conversions differ.  Scores, softmax statistics,
-// lse, delta and every accumulator are fp32 for both; P (forward) and dS (backward) are rounded to T as MFMA operands.
+// The kernels are templates on the 16-bit element type T of q, k, v, out and the gradients (elem16.h: the vector types,
+// mfma() and the operand layout its lane / register names r, h, i, j refer to).  Scores, softmax statistics, lse,
+// delta and every accumulator are fp32 for both types; P (forward) and dS (backward) are rounded to T as MFMA operands.
 //
-// Lane l = (r = l & 31, h = l >> 5):
-//   A operand element j : A[row r][k = 8h + j]         (8 x T)
-//   B operand element j : B[k = 8h + j][col r]         (8 x T)
-//   C/D register i      : C[row (i&3) + 8(i>>2) + 4h][col r]
 // A 32x32 f32 accumulator X (rows on registers, column on the lane) can feed the next MFMA
 // without touching LDS when that product sums over X's ROW index: registers 8s..8s+7, converted
 // to T, are the k-step-s fragment, whose element j is X row 16s + 8(j>>2) + 4h + (j&3); the
@@ -17,54 +12,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "elem16.h"
+
 namespace vah {
 namespace attn {
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
-typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
-
-// vectors of 8 / 4 elements of the kernels' 16-bit type T
-template <typename T> struct Vec16;
-template <> struct Vec16<__bf16> {
-    typedef bf16x8 x8;
-    typedef bf16x4 x4;
-};
-template <> struct Vec16<_Float16> {
-    typedef f16x8 x8;
-    typedef f16x4 x4;
-};
-template <typename T> using vec8 = typename Vec16<T>::x8;
-template <typename T> using vec4 = typename Vec16<T>::x4;
-
-// profiler row / launch name of the instantiation: the bf16 name or its _f16 twin
-template <typename T> constexpr const char *tname(const char *bf16_name, const char *f16_name);
-template <> constexpr const char *tname<__bf16>(const char *bf16_name, const char *) { return bf16_name; }
-template <> constexpr const char *tname<_Float16>(const char *, const char *f16_name) { return f16_name; }
 
 constexpr int kHD = 64;          // head dim
 constexpr int kPadRow = 72;      // LDS row stride (elements) of a [rows][64] tile read with b128: 144 B
 constexpr int kPadT = 68;        // LDS row stride (elements) of a [64 d][64 keys] transposed tile, b64 reads
 constexpr int kPadT32 = 36;      // LDS row stride (elements) of a [64 d][32 queries] transposed tile
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma(f16x8 a, f16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-// row of a C/D tile held in register i by lane half h
-__device__ __forceinline__ int crow(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) z[i] = 0.f;
-    return z;
-}
 
 // registers 8s..8s+7 of an accumulator -> T fragment of k-step s
 template <typename T>

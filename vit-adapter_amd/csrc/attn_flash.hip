@@ -18,8 +18,6 @@ namespace vah {
 namespace attn {
 namespace {
 
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8;
 
 template <typename T>
 __device__ __forceinline__ const T *tile_lane_base(const T *tile, int lane) {
@@ -30,9 +28,7 @@ __device__ __forceinline__ const T *tile_lane_base(const T *tile, int lane) {
 template <typename T>
 __device__ __forceinline__ vec8<T> load_tr(const T *base, int tok0, int db) {
     const T *p0 = base + tok0 * kPadRow + 32 * db;
-    const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p0);
-    const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(p0 + 8 * kPadRow));
-    return __builtin_bit_cast(vec8<T>, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
+    return tr_frag<T>(p0, p0 + 8 * kPadRow);
 }
 // Exchange across the two 32-lane halves on the VALU: after v_permlane32_swap a = [x.lo, x.lo], b = [x.hi, x.hi].
 // Inline asm: with the builtin and one value for both operands the compiler folds max(a, b) to a.  The s_nop covers

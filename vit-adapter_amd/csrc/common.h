@@ -45,11 +45,17 @@ __device__ __forceinline__ float dpp_mov(float x) {
                                                                  ROW_MASK, 0xF, false));
 }
 
-// Sum over each aligned group of 16 lanes; every lane of the group ends up with the sum.
-__device__ __forceinline__ float dpp_sum16(float x) {
+// Sum over each aligned group of 8 lanes; every lane of the group ends up with the sum.
+__device__ __forceinline__ float dpp_sum8(float x) {
     x += dpp_mov<0xB1, 0xF>(x);     // quad_perm [1,0,3,2]
     x += dpp_mov<0x4E, 0xF>(x);     // quad_perm [2,3,0,1]
-    x += dpp_mov<0x141, 0xF>(x);    // row_half_mirror
+    x += dpp_mov<0x141, 0xF>(x);    // row_half_mirror: lanes 0-7 <-> 7-0 within each 8
+    return x;
+}
+
+// Sum over each aligned group of 16 lanes; every lane of the group ends up with the sum.
+__device__ __forceinline__ float dpp_sum16(float x) {
+    x = dpp_sum8(x);
     x += dpp_mov<0x140, 0xF>(x);    // row_mirror
     return x;
 }

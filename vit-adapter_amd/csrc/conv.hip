@@ -29,19 +29,11 @@
 
 #include <cstdint>
 
-#include "attn_common.h"
 #include "common.h"
+#include "elem16.h"
 
 namespace vah {
 namespace {
-
-using attn::crow;
-using attn::f32x16;
-using attn::mfma;
-using attn::tname;
-using attn::vec4;
-using attn::vec8;
-using attn::zero16;
 
 constexpr int kMaxTaps = 9;
 constexpr int kCoutTile = 64;
@@ -241,22 +233,10 @@ int dispatch_taps(const void *in, const void *w, void *out, TapGeom &g, hipStrea
 // Every workgroup adds up its tiles in registers and writes one fp32 partial (64 x 9 x CK) to the workspace;
 // conv_wgrad_reduce sums the partials of a (co tile, c tile) in slot order: bitwise reproducible, no atomics.
 // ---------------------------------------------------------------------------------------
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8;
-
 struct WgradGeom {
     int S, N, IH, IW, Cin, OH, OW, Cout;
     int HY, HX, tiles_y, tiles_x, ntiles;
 };
-
-// transposed fragment: rows row0 + 4 * hf + q (q = 0..3) and 8 rows further, columns col0 + 16 * (grp & 1) + 4 p ..;
-// the lane receives column (lane & 31) of the 8 rows in the k order of a standard fragment pair (4 hf.., 8 + 4 hf..)
-template <typename T>
-__device__ __forceinline__ vec8<T> tr_frag(const unsigned char *p0, const unsigned char *p1) {
-    const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p0);
-    const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p1);
-    return __builtin_bit_cast(vec8<T>, __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 template <typename T, int CK, int WY>
 __global__ __launch_bounds__(512) void conv_wgrad_kernel(const T *__restrict__ x, const T *__restrict__ dy,

@@ -25,26 +25,10 @@
 #include <type_traits>
 
 #include "common.h"
+#include "elem16.h"
 
 namespace vah {
 namespace {
-
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
-typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8;
-
-// vector of 4 elements of the kernels' 16-bit type T
-template <typename T> struct Vec16;
-template <> struct Vec16<__bf16> { typedef bf16x4 x4; typedef bf16x8 x8; };
-template <> struct Vec16<_Float16> { typedef f16x4 x4; typedef f16x8 x8; };
-template <typename T> using vec4 = typename Vec16<T>::x4;
-template <typename T> using vec8 = typename Vec16<T>::x8;
-
-// profiler row of the instantiation: the bf16 name or its _f16 twin
-template <typename T> constexpr const char *tname(const char *bf16_name, const char *f16_name);
-template <> constexpr const char *tname<__bf16>(const char *bf16_name, const char *) { return bf16_name; }
-template <> constexpr const char *tname<_Float16>(const char *, const char *f16_name) { return f16_name; }
 
 // fp32 -> T where a kernel both stores the rounded value and sums it (the bias partials), or has to agree bit for bit
 // with another kernel's store: every dz / dh store of the residual, residual + LayerNorm and GELU backward kernels.  For _Float16 the fp32 value is made opaque first: with -ffp-contract=fast the compiler

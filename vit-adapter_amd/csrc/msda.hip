@@ -245,13 +245,6 @@ struct TapG {           // 32 bytes: token index of each corner inside its level
     int level;
 };
 
-__device__ __forceinline__ float sum8_dpp(float x) {
-    x += dpp_mov<0xB1, 0xF>(x);     // quad_perm [1,0,3,2]
-    x += dpp_mov<0x4E, 0xF>(x);     // quad_perm [2,3,0,1]
-    x += dpp_mov<0x141, 0xF>(x);    // row_half_mirror: lanes 0-7 <-> 7-0 within each 8
-    return x;                       // every lane of the 8-lane group holds the sum
-}
-
 template <int PU>
 __global__ __launch_bounds__(kBlock) void msda_bwd_taps_vec4(
     const float *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
@@ -332,9 +325,9 @@ __global__ __launch_bounds__(kBlock) void msda_bwd_taps_vec4(
             const float val = hh * hw * d0 + hh * lw * d1 + lh * hw * d2 + lh * lw * d3;
             const float gh = hw * (d2 - d0) + lw * (d3 - d1);
             const float gw = hh * (d1 - d0) + lh * (d3 - d2);
-            const float pa = sum8_dpp(val);
-            const float pw = sum8_dpp((float)lv[u].W * gw * a);
-            const float ph = sum8_dpp((float)lv[u].H * gh * a);
+            const float pa = dpp_sum8(val);
+            const float pw = dpp_sum8((float)lv[u].W * gw * a);
+            const float ph = dpp_sum8((float)lv[u].H * gh * a);
             if (sub == ((s0 + u) & 7)) {
                 *reinterpret_cast<float2 *>(glp + 2 * (s0 + u)) = lv[u].valid ? make_float2(pw, ph) : make_float2(0.f, 0.f);
                 gap[s0 + u] = lv[u].valid ? pa : 0.f;

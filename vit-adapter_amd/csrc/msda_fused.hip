@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "elem16.h"
 #include "msda_common.h"
 #include "msda_internal.h"
 
@@ -33,11 +34,6 @@ namespace vah {
 namespace {
 
 using namespace vah::msda;
-
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
-typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2;
-typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
-typedef __attribute__((__vector_size__(2 * sizeof(_Float16)))) _Float16 f16x2;
 
 __device__ __forceinline__ float4 load4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ float4 load4(const __bf16 *p) {
@@ -287,12 +283,6 @@ __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
 // Gather-only variant of the backward above: d(offsets), d(logits), no grad_value (the tile pass of msda_tile.hip
 // owns it).  8 lanes x 4 channels per row (16-byte corner loads as in the forward: 4x fewer gather instructions
 // than one channel per lane).
-__device__ __forceinline__ float sum8(float x) {
-    x += dpp_mov<0xB1, 0xF>(x);     // quad_perm [1,0,3,2]
-    x += dpp_mov<0x4E, 0xF>(x);     // quad_perm [2,3,0,1]
-    x += dpp_mov<0x141, 0xF>(x);    // row_half_mirror: lanes 0-7 <-> 7-0 within each 8
-    return x;                       // every lane of the 8-lane group holds the sum
-}
 
 // One sampling tap as the 8 channel lanes of a row read it back from LDS.
 struct TapL {
@@ -403,7 +393,7 @@ void msda_fused_bwd_vec4(
             const float val = cw[0] * d0 + cw[1] * d1 + cw[2] * d2 + cw[3] * d3;
             const float gh = hw * (d2 - d0) + lw * (d3 - d1);
             const float gw = hh * (d1 - d0) + lh * (d3 - d2);
-            const float gas = sum8(val), gxs = sum8(gw * a), gys = sum8(gh * a);
+            const float gas = dpp_sum8(val), gxs = dpp_sum8(gw * a), gys = dpp_sum8(gh * a);
             dot += a * gas;
             const bool mine = (s & 7) == sub;
             ga_m[s >> 3] = mine ? gas : ga_m[s >> 3];

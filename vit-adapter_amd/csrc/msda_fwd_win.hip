@@ -16,6 +16,7 @@
 // so any offsets give the same result; they only cost time.
 #include <type_traits>
 
+#include "elem16.h"
 #include "msda_common.h"
 #include "msda_internal.h"
 
@@ -27,18 +28,6 @@ using namespace vah::msda;
 constexpr int kD = 32;
 constexpr int kP = 4;
 constexpr int kWinThreads = 128;
-
-typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2;
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8;
-
-template <typename T>
-__device__ __forceinline__ float word_elem(const uint32_t *w, int i) {       // element i of a packed T array
-    if constexpr (sizeof(T) == 4) return __builtin_bit_cast(float, w[i]);
-    else if constexpr (std::is_same<T, _Float16>::value)                      // v_cvt_f32_f16: exact, subnormals kept
-        return (float)__builtin_bit_cast(_Float16, (unsigned short)((i & 1) ? w[i >> 1] >> 16 : w[i >> 1] & 0xFFFFu));
-    else return __builtin_bit_cast(float, (i & 1) ? (w[i >> 1] & 0xFFFF0000u) : (w[i >> 1] << 16));
-}
 
 // acc[0..31] += w * row, row = 32 channels of VT at p (LDS or global, 16-byte aligned)
 template <typename VT>

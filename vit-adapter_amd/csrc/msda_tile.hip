@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "elem16.h"
 #include "msda_common.h"
 #include "msda_internal.h"
 
@@ -77,35 +78,10 @@ constexpr int kBinTable = 2048;    // tiles of one level the LDS tables of the b
 constexpr int kChunksPerWg = 8;    // a list longer than this many 64-entry chunks (by its even load) is shared
 constexpr int kWinW = kTW + 2, kWinH = kTH + 2, kWinPx = kWinW * kWinH;   // value window: tile + 1 pixel all around
 
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
-typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2;
-typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
-typedef __attribute__((__vector_size__(2 * sizeof(_Float16)))) _Float16 f16x2;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
-
-// The 16-bit row type of an instantiation and its vectors.  fp32 rows never touch them: they get the bf16 spelling so
-// that the declarations shared by all three compile.
-template <typename T>
-struct Half {
-    typedef __bf16 elem;
-    typedef bf16x8 x8;
-    typedef bf16x4 x4;
-    typedef bf16x2 x2;
-};
-template <>
-struct Half<_Float16> {
-    typedef _Float16 elem;
-    typedef f16x8 x8;
-    typedef f16x4 x4;
-    typedef f16x2 x2;
-};
-// same fragment layout for both 16-bit types (8 consecutive k per lane, lanes 32.. the second 8)
-__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8;
+// The 16-bit row type of an instantiation and its vectors (Vec16).  fp32 rows never touch them: they get the bf16
+// spelling so that the declarations shared by all three compile.
+template <typename T> struct Half : Vec16<__bf16> { typedef __bf16 elem; };
+template <> struct Half<_Float16> : Vec16<_Float16> { typedef _Float16 elem; };
 
 // ---- the plan: computed on the device, kept at the head of the workspace -----------------------------------------
 struct PlanDev {
@@ -396,14 +372,6 @@ struct PlainSrc {
         a[0] = r.a.x, a[1] = r.a.y, a[2] = r.a.z, a[3] = r.a.w;
     }
 };
-
-template <typename PT>
-__device__ __forceinline__ float word_elem(const uint32_t *w, int i) {       // element i of a packed PT array
-    if constexpr (sizeof(PT) == 4) return __builtin_bit_cast(float, w[i]);
-    else if constexpr (std::is_same<PT, _Float16>::value)                                                // v_cvt_f32_f16: exact
-        return (float)__builtin_bit_cast(_Float16, (unsigned short)((i & 1) ? w[i >> 1] >> 16 : w[i >> 1] & 0xFFFFu));
-    else return __builtin_bit_cast(float, (i & 1) ? (w[i >> 1] & 0xFFFF0000u) : (w[i >> 1] << 16));     // bf16 -> f32
-}
 
 // Fused: raw sampling_offsets / attention logits of the MSDeformAttn module + the reference grid
 // (arithmetic of msda_fused.hip: loc = ref + off / (W, H), softmax over the L*P logits).
@@ -987,8 +955,8 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                             f32x16 dd;
 #pragma unroll
                             for (int i = 0; i < 16; ++i) dd[i] = 0.f;
-                            dd = mfma16(pb ? vf.v10 : vf.v00, b0, dd);
-                            dd = mfma16(pb ? vf.v11 : vf.v01, b1, dd);
+                            dd = mfma(pb ? vf.v10 : vf.v00, b0, dd);
+                            dd = mfma(pb ? vf.v11 : vf.v01, b1, dd);
 #pragma unroll
                             for (int gq = 0; gq < 4; ++gq)
                                 *reinterpret_cast<float4 *>(drow + 32 * pb + 8 * gq) = make_float4(dd[4 * gq], dd[4 * gq + 1], dd[4 * gq + 2], dd[4 * gq + 3]);
@@ -1074,12 +1042,7 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                     const HT *gbase = reinterpret_cast<const HT *>(Gs) + (8 * (grp >> 1) + qq) * kD + 16 * (grp & 1) + 4 * pp;
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
-                        const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (s16x4 __attribute__((address_space(3))) *)(gbase + (16 * s) * kD));
-                        const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (s16x4 __attribute__((address_space(3))) *)(gbase + (16 * s + 4) * kD));
-                        const s16x8 t01 = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
-                        const h8 gfr = __builtin_bit_cast(h8, t01);
+                        const h8 gfr = tr_frag<HT>(gbase + (16 * s) * kD, gbase + (16 * s + 4) * kD);
                         const float *wp = Wt + r * WS + 16 * s + 8 * h;
                         const float4 w0 = *reinterpret_cast<const float4 *>(wp);
                         const float4 w1 = *reinterpret_cast<const float4 *>(wp + 4);
@@ -1092,8 +1055,8 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                             whi[jj] = (HT)wv[jj];
                             wlo[jj] = (HT)(wv[jj] - (float)whi[jj]);
                         }
-                        acc = mfma16(gfr, whi, acc);
-                        acc = mfma16(gfr, wlo, acc);
+                        acc = mfma(gfr, whi, acc);
+                        acc = mfma(gfr, wlo, acc);
                     }
                 }
                 VAH_PHASE();

@@ -17,15 +17,11 @@
 
 #include <cstdint>
 
-#include "attn_common.h"
 #include "common.h"
+#include "elem16.h"
 
 namespace vah {
 namespace {
-
-using attn::bf16x8;
-using attn::tname;
-using attn::vec8;
 
 constexpr int kStatParts = 512;         // partial rows of the statistics passes (two workgroups per CU)
 

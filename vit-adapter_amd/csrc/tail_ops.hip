@@ -25,15 +25,11 @@
 #include <cstdint>
 
 #include "../../include/vitadapter_hip.h"
-#include "attn_common.h"
 #include "common.h"
+#include "elem16.h"
 
 namespace vah {
 namespace {
-
-using attn::tname;
-using attn::vec4;
-using attn::vec8;
 
 constexpr int kTilePx = 8192;           // hi-res pixels of one plane per workgroup
 constexpr int kTailParts = 512;         // partial rows of the channel sums (finalised below)
@@ -101,7 +97,6 @@ __device__ __forceinline__ float4 widen4<__bf16>(uint32_t w0, uint32_t w1) {
 }
 template <>
 __device__ __forceinline__ float4 widen4<_Float16>(uint32_t w0, uint32_t w1) {
-    typedef __attribute__((__vector_size__(2 * sizeof(_Float16)))) _Float16 f16x2;
     const f16x2 lo = __builtin_bit_cast(f16x2, w0), hi = __builtin_bit_cast(f16x2, w1);
     return make_float4((float)lo[0], (float)lo[1], (float)hi[0], (float)hi[1]);
 }
