@@ -95,14 +95,20 @@ int vah_msda_backward_f64(const double *value, const int64_t *shapes, const int6
  * sampling-location arithmetic + the gather in one kernel, and their gradients in one more.
  * Replaces lines 108-128 of /root/reference/detection/ops/modules/ms_deform_attn.py.
  *
- *   value     (N,S,M,32)        value_dtype: 0 = fp32, 1 = bf16, 2 = fp16   (out and grad_out use this dtype)
+ *   value     (N,S,M,D)         value_dtype: 0 = fp32, 1 = bf16, 2 = fp16   (out and grad_out use this dtype)
  *   offsets   (N,Lq,M,L,P,2)    raw sampling_offsets Linear output, param_dtype 0 = fp32 / 1 = bf16 / 2 = fp16
  *   logits    (N,Lq,M,L*P)      raw attention_weights Linear output (softmax is done in-kernel)
  *   ref       (Lq, ref_levels, 2) fp32 reference points (x, y) in [0,1], ref_levels = 1 or L,
  *             shared by the batch (the adapter's reference grids); the *_nref entry points take
  *             (ref_batch, Lq, ref_levels, 2) with ref_batch = 1 or N: one grid per image
  *   location  = ref + offsets / (W_l, H_l)
- * Supported: D == 32 and (L, P) in {(1,4), (3,4), (4,4)}  (vah_msda_fused_supported).
+ * Supported: D in {32, 64} and (L, P) in {(1,4), (3,4), (4,4)}  (vah_msda_fused_supported).
+ * D == 64 (ViT-Adapter-S: 384 channels over 6 heads): a (N,S,M,64) tensor is bit for bit a (N,S,2M,32) one, and the
+ * kernels treat a head as two adjacent 32-channel half-heads that share one row of offsets and logits - same dtype
+ * forms, strides, (L, P) and reference points as D == 32, same arithmetic (fp32 math, one rounding at each store).  It is
+ * taken by vah_msda_fused_forward[_nref], vah_msda_fused_forward_win and vah_msda_fused_backward_tiled[_nref]; the
+ * atomic vah_msda_fused_backward[_nref] stays at D == 32 and answers VAH_E_UNSUPPORTED for 64 (like fp16: a form that
+ * exists only where the tile pass serves).  Any other D is VAH_E_UNSUPPORTED everywhere.
  * Dtype codes: 0 and 1 mix freely between value_dtype and param_dtype.  Code 2 (fp16, what fp16 autocast hands the
  * module) is accepted in ONE form: value / out / grad_out / grad_value fp16 AND offsets / logits / d_offsets / d_logits
  * fp16, contiguous or row-strided, by vah_msda_fused_forward[_nref], vah_msda_fused_forward_win and
@@ -114,7 +120,7 @@ int vah_msda_backward_f64(const double *value, const int64_t *shapes, const int6
  * Row strides of fp16 offsets need 8-byte alignment (16 for the other types in the window forward and the tiled
  * backward).  Profile rows of fp16 calls: msda_fused_fwd_f16 / msda_fused_bwd_f16; other calls: msda_fused_fwd /
  * msda_fused_bwd.
- * Backward (vah_msda_fused_backward): grad_value fp32 (N,S,M,32) zero on entry (float atomics, one per
+ * Backward (vah_msda_fused_backward; D == 32 only): grad_value fp32 (N,S,M,32) zero on entry (float atomics, one per
  * sample, corner and channel as the reference); d_offsets / d_logits in param_dtype, fully written.  It is
  * the fallback of vah_msda_fused_backward_tiled below, which is what the modules call.
  * ------------------------------------------------------------------------------------ */
@@ -158,7 +164,7 @@ int vah_msda_fused_backward_nref(const void *value, int value_dtype, const int64
                                  float *grad_value, void *d_offsets, void *d_logits, void *stream);
 
 /* ------------------------------------------------------------------------------------
- * Fused forward over LDS value windows (csrc/msda_fwd_win.hip), single-level calls (L == 1, D == 32, P == 4,
+ * Fused forward over LDS value windows (csrc/msda_fwd_win.hip), single-level calls (L == 1, D in {32, 64}, P == 4,
  * reference points shared by the batch: the adapter's extractor).  Same result as vah_msda_fused_forward for ANY
  * offsets; the windows only decide which corner rows are served from LDS.  The queries are grouped by the 8 x 8-pixel
  * tile of the value map their reference point falls in; a group's window is the tile + halo + 1 pixels on every side.
@@ -172,7 +178,9 @@ int vah_msda_fused_backward_nref(const void *value, int value_dtype, const int64
  *                   deform inputs): only the forward kernel runs.  The forward kernel does not write to ws.
  * A workgroup walks (n, group, head) items: it stages the window once, then one lane per query evaluates its four
  * samples against it (replaces ms_deform_im2col_cuda.cuh:237-299 + the module's softmax / location lines).
- * out (N, Lq, M*32) is fully written by every call that returns VAH_OK: if the level is no valid window of the S value
+ * D == 64: items are (n, group, half-head) and a lane evaluates one (query, head, half) row over the half-head's
+ * window, so the LDS a call needs does not depend on D.
+ * out (N, Lq, M*D) is fully written by every call that returns VAH_OK: if the level is no valid window of the S value
  * rows (level guard above: H < 1, W < 1, start < 0, start + H*W > S) the schedule is empty and the forward kernel
  * writes zeros, as vah_msda_fused_forward does - with ws_holds_schedule = 1 on such a schedule as well.
  * ------------------------------------------------------------------------------------ */
@@ -203,7 +211,13 @@ int vah_msda_fused_forward_win(const void *value, int value_dtype, const int64_t
  * products against the tile's 10x6-pixel value window on the matrix cores) + a softmax-backward pass.
  *   ws / ws_bytes          : device workspace of at least vah_msda_tile_ws_bytes(...) bytes, 16-byte
  *                            aligned, contents arbitrary (plan, list counters, entries, partial tiles, d(out)/d(p))
- *   needs D == 32, P == 4, 1 <= L <= 4 (VAH_E_UNSUPPORTED otherwise: use the functions above)
+ *   needs P == 4, 1 <= L <= 4, and D == 32 - the fused core (vah_msda_fused_backward_tiled[_nref]) also takes D == 64 -
+ *   (VAH_E_UNSUPPORTED otherwise: use the functions above)
+ * vah_msda_tile_ws_bytes has no D argument: its `M` is the number of 32-CHANNEL HEAD SLICES, heads * (D / 32) - the
+ * heads themselves at D == 32, twice as many at D == 64, where the lists, slabs and gradient records are kept per
+ * half-head.  The tiled entry points check ws_bytes against the bound for their own D: a workspace sized for `heads`
+ * at D == 64 is refused as too small (VAH_E_SHAPE).  At D == 64 a sample's {d(offset), d(out)/d(p)} come as two fp32
+ * partial records, one per half-head, which the finishing pass adds and rounds once.
  * fp16 values (code 2, one form, see the fused core above): as bf16 with v_mfma_f32_32x32x16_f16 and the weights as
  * fp16 hi + lo; grad_value_dtype = grad_param_dtype = 2.
  * vah_msda_fused_backward_tiled: grad_value_dtype 0 = fp32, 1 = bf16 (bf16 values only); grad_param_dtype: type of

@@ -18,7 +18,14 @@
 // the fp32 math of the other forms, and out is rounded once by the plain cast (nearest even, overflow to +-inf,
 // subnormals kept: what torch's .to(float16) does, see fused_ops.hip).
 //
-// Restrictions of this path: D == 32, (L, P) in {(1,4), (3,4), (4,4)}, reference points with last dim 2,
+// Head widths: D == 32, and D == 64 (ViT-Adapter-S: embed_dim 384 over 6 heads).  A (N,S,M,64) tensor is bit for bit a
+// (N,S,2M,32) one: a 64-channel head is two adjacent 32-channel half-heads that share one row of offsets and logits.
+// The gather kernels here take D as a template parameter and give a row D / 4 channel lanes (8 or 16); the window
+// forward (msda_fwd_win.hip) and the tile pass (msda_tile.hip) run the half-heads as heads of their own and read
+// parameter row `row >> 1`.  The atomic backward (vah_msda_fused_backward[_nref]) stays at D == 32: like fp16, D == 64
+// exists only where the tile pass serves.
+//
+// Restrictions of this path: D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, reference points with last dim 2,
 // shared by the batch (the adapter's) or one grid per image (the Mask2Former pixel decoder's grid times
 // valid ratios, segmentation/mmseg_custom/models/plugins/msdeformattn_pixel_decoder.py:224-240): `rq`, the
 // rows of ref between consecutive images, is a run-time kernel argument, 0 for a shared grid.
@@ -98,25 +105,25 @@ __device__ __forceinline__ void row_softmax(const PT *__restrict__ lg, float (&p
     for (int s = 0; s < LP; ++s) p[s] *= inv;
 }
 
-constexpr int kD = 32;
+constexpr int kD = 32;                  // the one-lane-per-channel backward (atomics) and the half-head width
 constexpr float kNoScatter = -2.f;      // near_radius sentinel: the gather kernels scatter nothing
 
 // ---------------------------------------------------------------------------------------
-// forward: 8 lanes x 4 channels per row, query-major work order (see msda.hip)
+// forward: D / 4 lanes (8, or 16 at D == 64) x 4 channels per row, query-major work order (see msda.hip)
 // ---------------------------------------------------------------------------------------
-struct TapF {           // one sampling tap as the 8 channel lanes of a row read it back from LDS
+struct TapF {           // one sampling tap as the channel lanes of a row read it back from LDS
     int row[4];         // token index of the corner inside its level (0 for an invalid corner)
     float w[4];         // bilinear weight of the corner (0 for an invalid corner)
 };
 
-template <typename VT, typename PT, int L, int P>
+template <typename VT, typename PT, int L, int P, int D>
 __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const PT *__restrict__ off, const PT *__restrict__ logit, int64_t os, int64_t ls, const float *__restrict__ ref,
     int ref_levels, int64_t rq, int64_t S, int M, int64_t Lq, int64_t total_rows, int64_t nblocks,
     VT *__restrict__ out) {
     constexpr int LP = L * P;
-    constexpr int ROWS = kBlock / 8;
+    constexpr int LANES = D / 4, ROWS = kBlock / LANES;
     __shared__ __attribute__((aligned(16))) TapF s_tap[ROWS * LP];
     const int64_t blk = xcd_chunked_block(nblocks);
     if (blk >= nblocks) return;
@@ -146,15 +153,15 @@ __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
         s_tap[i] = tl;
     }
     __syncthreads();
-    const int sub = threadIdx.x & 7, rl = threadIdx.x >> 3;
+    const int sub = threadIdx.x % LANES, rl = threadIdx.x / LANES;
     const int64_t work = blk * ROWS + rl;
     if (work >= total_rows) return;
     const int64_t q = work % Lq;
     const int m = (int)((work / Lq) % M);
     const int64_t n = work / Lq / M;
     const int64_t row = (n * Lq + q) * M + m;
-    const int64_t stride = (int64_t)M * kD;
-    const VT *vhead = value + n * S * stride + m * kD + sub * 4;
+    const int64_t stride = (int64_t)M * D;
+    const VT *vhead = value + n * S * stride + m * D + sub * 4;
 
     float p[LP];
     row_softmax<PT, LP>(logit + row * ls, p);
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
             acc.w += s4.w * a;
         }
     }
-    store4(out + row * kD + sub * 4, acc);
+    store4(out + row * D + sub * 4, acc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -281,10 +288,11 @@ __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
 }
 
 // Gather-only variant of the backward above: d(offsets), d(logits), no grad_value (the tile pass of msda_tile.hip
-// owns it).  8 lanes x 4 channels per row (16-byte corner loads as in the forward: 4x fewer gather instructions
-// than one channel per lane).
+// owns it).  D / 4 lanes x 4 channels per row (16-byte corner loads as in the forward: 4x fewer gather instructions
+// than one channel per lane).  D == 64 (16 lanes; fp32 values only: 16-bit rows get these gradients from the tile pass)
+// forms its addresses in 64 bits, so it has no 4 GB limit and needs no second kernel behind it.
 
-// One sampling tap as the 8 channel lanes of a row read it back from LDS.
+// One sampling tap as the channel lanes of a row read it back from LDS.
 struct TapL {
     int row[4];        // token index of the corner inside its level, -1 = invalid corner
     float lh, lw;
@@ -297,7 +305,7 @@ struct TapL {
 #ifndef VAH_BWDA_WAVESN
 #define VAH_BWDA_WAVESN 3
 #endif
-template <typename VT, typename PT, int L, int P>
+template <typename VT, typename PT, int L, int P, int D>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(VT) == 2 ? (L == 1 ? VAH_BWDA_WAVES1 : VAH_BWDA_WAVESN) : 1)))   // fp32 values would spill
 void msda_fused_bwd_vec4(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
@@ -306,7 +314,8 @@ void msda_fused_bwd_vec4(
     int64_t nblocks, float near_radius, float *__restrict__ grad_value, PT *__restrict__ d_off,
     PT *__restrict__ d_logit) {
     constexpr int LP = L * P;
-    constexpr int ROWS = kBlock / 8;
+    constexpr int LANES = D / 4, ROWS = kBlock / LANES;
+    typedef typename std::conditional<D == kD, uint32_t, uint64_t>::type boff_t;      // byte offsets from the tensor base
     __shared__ __attribute__((aligned(16))) TapL s_tap[ROWS * LP];
     const int64_t blk = xcd_chunked_block(nblocks);
     if (blk >= nblocks) return;
@@ -336,35 +345,35 @@ void msda_fused_bwd_vec4(
         s_tap[i] = tl;
     }
     __syncthreads();
-    const int sub = threadIdx.x & 7, rl = threadIdx.x >> 3;
+    const int sub = threadIdx.x % LANES, rl = threadIdx.x / LANES;
     const int64_t work = blk * ROWS + rl;
-    if (work >= total_rows) return;          // whole 8-lane groups leave together (after the barrier)
+    if (work >= total_rows) return;          // whole lane groups leave together (after the barrier)
     const int64_t q = work % Lq;
     const int m = (int)((work / Lq) % M);
     const int64_t n = work / Lq / M;
     const int64_t row = (n * Lq + q) * M + m;
-    const int64_t stride = (int64_t)M * kD;
-    const int64_t head_off = n * S * stride + m * kD + sub * 4;
+    const int64_t stride = (int64_t)M * D;
+    const int64_t head_off = n * S * stride + m * D + sub * 4;
 
     // Register diet (this kernel waits on gathers: time ~ 1 / loads in flight per SIMD, i.e. it is
     // paid in occupancy): the reduced per-sample sums are needed by ONE lane of the row only, so each
-    // lane keeps just the samples it will store (s & 7 == sub) instead of all LP x 3 of them.
-    constexpr int NM = (LP + 7) / 8;
+    // lane keeps just the samples it will store (s % LANES == sub) instead of all LP x 3 of them.
+    constexpr int NM = (LP + LANES - 1) / LANES;
     float p[LP], ga_m[NM], gx_m[NM], gy_m[NM], p_m[NM];
     row_softmax<PT, LP>(logit + row * LP, p);
 #pragma unroll
     for (int i = 0; i < NM; ++i) ga_m[i] = gx_m[i] = gy_m[i] = p_m[i] = 0.f;
     float dot = 0.f;
-    const uint32_t row_bytes = (uint32_t)(stride * sizeof(VT));
-    const uint32_t lane_off = (uint32_t)(head_off * sizeof(VT));
-    const float4 g = load4(grad_out + row * kD + sub * 4);
+    const boff_t row_bytes = (boff_t)(stride * sizeof(VT));
+    const boff_t lane_off = (boff_t)(head_off * sizeof(VT));
+    const float4 g = load4(grad_out + row * D + sub * 4);
 #pragma unroll
     for (int l = 0; l < L; ++l) {
         const Level lv = read_level(shapes, lsi, l, S);
         // 32-bit byte offsets from the (uniform) tensor base: one address register per gather instead
-        // of two (the host routes value tensors of 4 GB and more to msda_fused_bwd)
+        // of two (D == 32; the host routes value tensors of 4 GB and more to msda_fused_bwd)
         const int64_t lstart = lv.valid ? lv.start : 0;      // invalid level: rows are -1 -> token 0, selected away
-        const uint32_t lvl_off = lane_off + (uint32_t)lstart * row_bytes;
+        const boff_t lvl_off = lane_off + (boff_t)lstart * row_bytes;
         const TapL *tp = s_tap + rl * LP + l * P;
         float4 v[P][4];
 #pragma unroll
@@ -376,7 +385,7 @@ void msda_fused_bwd_vec4(
                 // unconditional (clamped) load + select: a load under `if (valid)` gets its own
                 // s_waitcnt and the 16 gathers of a row run one after the other
                 const float4 x = load4(reinterpret_cast<const VT *>(
-                    reinterpret_cast<const char *>(value) + (lvl_off + (uint32_t)max(r4[k], 0) * row_bytes)));
+                    reinterpret_cast<const char *>(value) + (lvl_off + (boff_t)max(r4[k], 0) * row_bytes)));
                 const bool ok = r4[k] >= 0;
                 v[u][k] = make_float4(ok ? x.x : 0.f, ok ? x.y : 0.f, ok ? x.z : 0.f, ok ? x.w : 0.f);
             }
@@ -393,19 +402,20 @@ void msda_fused_bwd_vec4(
             const float val = cw[0] * d0 + cw[1] * d1 + cw[2] * d2 + cw[3] * d3;
             const float gh = hw * (d2 - d0) + lw * (d3 - d1);
             const float gw = hh * (d1 - d0) + lh * (d3 - d2);
-            const float gas = dpp_sum8(val), gxs = dpp_sum8(gw * a), gys = dpp_sum8(gh * a);
+            auto row_sum = [](float x) { return LANES == 8 ? dpp_sum8(x) : dpp_sum16(x); };
+            const float gas = row_sum(val), gxs = row_sum(gw * a), gys = row_sum(gh * a);
             dot += a * gas;
-            const bool mine = (s & 7) == sub;
-            ga_m[s >> 3] = mine ? gas : ga_m[s >> 3];
-            gx_m[s >> 3] = mine ? gxs : gx_m[s >> 3];
-            gy_m[s >> 3] = mine ? gys : gy_m[s >> 3];
-            p_m[s >> 3] = mine ? a : p_m[s >> 3];
+            const bool mine = (s % LANES) == sub;
+            ga_m[s / LANES] = mine ? gas : ga_m[s / LANES];
+            gx_m[s / LANES] = mine ? gxs : gx_m[s / LANES];
+            gy_m[s / LANES] = mine ? gys : gy_m[s / LANES];
+            p_m[s / LANES] = mine ? a : p_m[s / LANES];
         }
     }
-    // LP <= 16 samples, 8 lanes: lane `sub` stores samples sub and sub + 8
+    // LP <= 16 samples, 8 lanes: lane `sub` stores samples sub and sub + 8 (16 lanes: sample sub)
 #pragma unroll
     for (int i = 0; i < NM; ++i) {
-        const int s = i * 8 + sub;
+        const int s = i * LANES + sub;
         if (s < LP) {
             d_logit[row * LP + s] = (PT)(p_m[i] * (ga_m[i] - dot));
             store2(d_off + (row * LP + s) * 2, gx_m[i], gy_m[i]);
@@ -420,6 +430,7 @@ struct FusedArgs {
     int ref_levels;
     int64_t rq = 0;                  // rows of ref between consecutive images: Lq for a per-image grid, 0 for a shared one
     int64_t N, S, M, L, Lq, P;
+    int64_t D = kD;                  // channels per head: 32 or 64
     void *out;
     float *grad_value;
     void *d_off, *d_logit;
@@ -428,21 +439,39 @@ struct FusedArgs {
     hipStream_t st;
 };
 
-template <typename VT, typename PT, int L, int P>
+template <typename VT, typename PT, int L, int P, int D>
 int launch_fwd(const FusedArgs &a) {
+    constexpr int RPB = kBlock / (D / 4);          // rows per block
     const int64_t rows = a.N * a.Lq * a.M;
-    const int64_t nblocks = (rows + (kBlock / 8) - 1) / (kBlock / 8);
+    const int64_t nblocks = (rows + RPB - 1) / RPB;
     const int64_t grid = (nblocks + 7) / 8 * 8;
     if (grid >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "msda fused forward: grid too large");
-    hipLaunchKernelGGL((msda_fused_fwd<VT, PT, L, P>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
+    hipLaunchKernelGGL((msda_fused_fwd<VT, PT, L, P, D>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
                        (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.os ? a.os : L * P * 2,
                        a.ls ? a.ls : L * P, a.ref, a.ref_levels, a.rq, a.S, (int)a.M, a.Lq, rows, nblocks, (VT *)a.out);
     return check_launch("msda fused forward launch");
 }
 
-template <typename VT, typename PT, int L, int P>
+template <typename VT, typename PT, int L, int P, int D>
 int launch_bwd(const FusedArgs &a) {
     const int64_t rows = a.N * a.Lq * a.M;
+    if constexpr (D != kD) {
+        // D == 64: the gradients of the parameters for the tile pass, fp32 values (see msda_fused_bwd_vec4)
+        if constexpr (std::is_same<VT, float>::value) {
+            if (!a.taps_only) return fail(VAH_E_UNSUPPORTED, "msda fused backward: the atomic backward serves D == 32 only");
+            constexpr int RPB = kBlock / (D / 4);
+            const int64_t nb = (rows + RPB - 1) / RPB;
+            const int64_t gridd = (nb + 7) / 8 * 8;
+            if (gridd >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "msda fused backward: grid too large");
+            hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P, D>), dim3((unsigned)gridd), dim3(kBlock), 0, a.st,
+                               (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.ref,
+                               a.ref_levels, a.rq, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nb, kNoScatter,
+                               a.grad_value, (PT *)a.d_off, (PT *)a.d_logit);
+            return check_launch("msda fused backward (gather) launch");
+        } else {
+            return fail(VAH_E_UNSUPPORTED, "msda fused backward: D == 64 gather gradients exist for fp32 values only");
+        }
+    } else {
     const int64_t nblocks = (rows + (kBlock / kD) - 1) / (kBlock / kD);
     const int64_t grid = (nblocks + 7) / 8 * 8;
     if (grid >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "msda fused backward: grid too large");
@@ -457,25 +486,31 @@ int launch_bwd(const FusedArgs &a) {
     }
     const int64_t nb8 = (rows + (kBlock / 8) - 1) / (kBlock / 8);
     const int64_t grid8 = (nb8 + 7) / 8 * 8;
-    hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P>), dim3((unsigned)grid8), dim3(kBlock), 0, a.st,
+    hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P, kD>), dim3((unsigned)grid8), dim3(kBlock), 0, a.st,
                        (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.ref,
                        a.ref_levels, a.rq, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nb8, kNoScatter,
                        a.grad_value, (PT *)a.d_off, (PT *)a.d_logit);
     return check_launch("msda fused backward (gather) launch");
+    }
 }
 
-template <bool BWD, typename VT, typename PT>
-int dispatch_lp(const FusedArgs &a) {
+template <bool BWD, typename VT, typename PT, int D>
+int dispatch_lpd(const FusedArgs &a) {
 #define VAH_CASE(LL, PP)                                                        \
     if (a.L == LL && a.P == PP) {                                               \
-        if constexpr (BWD) return launch_bwd<VT, PT, LL, PP>(a);                \
-        else return launch_fwd<VT, PT, LL, PP>(a);       /* (fp16 has no backward instantiation here) */ \
+        if constexpr (BWD) return launch_bwd<VT, PT, LL, PP, D>(a);             \
+        else return launch_fwd<VT, PT, LL, PP, D>(a);    /* (fp16 has no backward instantiation here) */ \
     }
     VAH_CASE(1, 4);
     VAH_CASE(3, 4);
     VAH_CASE(4, 4);
 #undef VAH_CASE
     return fail(VAH_E_UNSUPPORTED, "msda fused: (L, P) = (%lld, %lld) not instantiated", (long long)a.L, (long long)a.P);
+}
+
+template <bool BWD, typename VT, typename PT>
+int dispatch_lp(const FusedArgs &a) {
+    return a.D == kD ? dispatch_lpd<BWD, VT, PT, kD>(a) : dispatch_lpd<BWD, VT, PT, 2 * kD>(a);
 }
 
 template <bool BWD>
@@ -494,7 +529,7 @@ int check_common(const char *fn, int64_t N, int64_t S, int64_t M, int64_t D, int
                  int64_t ref_levels, int64_t ref_batch) {
     if (N < 0 || S < 1 || M < 1 || L < 1 || Lq < 0 || P < 1 || M * D >= (1LL << 31))
         return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (D != kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32", fn);
+    if (D != kD && D != 2 * kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32 or D == 64", fn);
     if (ref_levels != 1 && ref_levels != L) return fail(VAH_E_SHAPE, "%s: ref_levels must be 1 or L", fn);
     if (ref_batch != 1 && ref_batch != N)
         return fail(VAH_E_SHAPE, "%s: ref_batch must be 1 or N (%lld), got %lld", fn, (long long)N, (long long)ref_batch);
@@ -518,9 +553,10 @@ int msda_check_dtypes(const char *fn, int value_dtype, int param_dtype, bool f16
 
 int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi, const void *offsets,
                          const void *logits, int param_dtype, const float *ref, int64_t ref_levels, int64_t rq,
-                         const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t L, int64_t Lq, int64_t P, void *d_offsets,
-                         void *d_logits, hipStream_t st) {
+                         const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
+                         void *d_offsets, void *d_logits, hipStream_t st) {
     FusedArgs a{};
+    a.D = D;
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
     a.ref_levels = (int)ref_levels, a.rq = rq, a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P;
     a.grad_out = grad_out, a.d_off = d_offsets, a.d_logit = d_logits;
@@ -546,7 +582,7 @@ int fused_forward_impl(const char *fn, const void *value, int value_dtype, const
     FusedArgs a{};
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
     a.ref_levels = (int)ref_levels, a.rq = msda_ref_rows_per_image(ref_batch, N, Lq);
-    a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P, a.out = out;
+    a.N = N, a.S = S, a.M = M, a.D = D, a.L = L, a.Lq = Lq, a.P = P, a.out = out;
     a.os = offsets_stride, a.ls = logits_stride;
     if (offsets_stride < 0 || logits_stride < 0 || ((offsets_stride * msda_dtype_bytes(param_dtype)) % 8))
         return fail(VAH_E_ALIGN, "%s: bad strides", fn);
@@ -569,6 +605,9 @@ int fused_backward_impl(const char *fn, const void *value, int value_dtype, cons
                         int64_t Lq, int64_t P, float *grad_value, void *d_offsets, void *d_logits, void *stream) {
     clear_error();
     if (int rc = check_common(fn, N, S, M, D, L, Lq, P, ref_levels, ref_batch)) return rc;
+    if (D != kD)
+        return fail(VAH_E_UNSUPPORTED, "%s: the atomic backward serves D == 32 only; D == 64 has the tiled backward "
+                                       "(vah_msda_fused_backward_tiled)", fn);
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !grad_out || !grad_value || !d_offsets || !d_logits)
         return fail(VAH_E_NULL, "%s: null pointer", fn);
@@ -593,7 +632,7 @@ int fused_backward_impl(const char *fn, const void *value, int value_dtype, cons
 extern "C" {
 
 int vah_msda_fused_supported(int64_t D, int64_t L, int64_t P) {
-    return D == 32 && P == 4 && (L == 1 || L == 3 || L == 4);
+    return (D == 32 || D == 64) && P == 4 && (L == 1 || L == 3 || L == 4);
 }
 
 int vah_msda_fused_forward(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,

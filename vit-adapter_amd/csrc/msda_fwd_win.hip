@@ -14,6 +14,10 @@
 //     reduction).  The 8-lane kernel spends ~20 wave-instructions per sample, this one ~3.
 // Corners outside the window (offsets beyond `halo`) are read from global memory by the lane that needs them,
 // so any offsets give the same result; they only cost time.
+//
+// D == 64 (HSH = 1): a (N,S,M,64) tensor is a (N,S,2M,32) one, so the kernel runs the 2M half-heads as heads of their
+// own - a lane per (query, head, half) over the half-head's window, the LDS of a D == 32 call - and a half-head row
+// reads the offsets and logits of parameter row `row >> 1`: the tap arithmetic of a row is done twice.
 #include <type_traits>
 
 #include "elem16.h"
@@ -25,7 +29,7 @@ namespace {
 
 using namespace vah::msda;
 
-constexpr int kD = 32;
+constexpr int kD = 32;                // channels of a (half-)head row
 constexpr int kP = 4;
 constexpr int kWinThreads = 128;
 
@@ -210,8 +214,9 @@ __global__ __launch_bounds__(kSchedThreads) void msda_win_schedule(const float *
 }
 
 // os / ls: elements between the offsets / logits of consecutive (n, q, m) rows (contiguous tensors: 8 and 4; the module's
-// interleaved fp32 [offsets | logits] rows: 12 and 12)
-template <typename VT, typename PT>
+// interleaved fp32 [offsets | logits] rows: 12 and 12).  M: 32-channel head slices (heads << HSH); out / value rows by
+// slice, parameter rows by head.
+template <typename VT, typename PT, int HSH>
 __global__ __launch_bounds__(kWinThreads) void msda_fused_fwd_win(
     const VT *__restrict__ value, const PT *__restrict__ off, const PT *__restrict__ logit, int64_t os, int64_t ls,
     const float *__restrict__ ref, const unsigned char *__restrict__ ws, int Gmax, int halo, int64_t S, int M, int N, int64_t Lq,
@@ -261,23 +266,24 @@ __global__ __launch_bounds__(kWinThreads) void msda_fused_fwd_win(
         for (int idx = beg + threadIdx.x; idx < end; idx += kWinThreads) {
             const int64_t q = perm[idx];
             const int64_t row = (n * Lq + q) * M + m;
+            const int64_t prow = row >> HSH;              // M is even when HSH is 1
             // ---- the row's operands: 4 offsets (x, y), 4 logits, the reference point
             uint32_t ow[kP * 2 * sizeof(PT) / 4], lw[kP * sizeof(PT) / 4];
             {
                 if constexpr (std::is_same<PT, _Float16>::value) {
                     // fp16 rows are 8-byte aligned only (one fp16 [offsets | logits | gap] matrix: rows of 3 P + 8 halves)
-                    const uint2 *op = reinterpret_cast<const uint2 *>(off + row * os);
+                    const uint2 *op = reinterpret_cast<const uint2 *>(off + prow * os);
                     const uint2 v0 = op[0], v1 = op[1];
                     ow[0] = v0.x, ow[1] = v0.y, ow[2] = v1.x, ow[3] = v1.y;
                 } else {
-                    const uint4 *op = reinterpret_cast<const uint4 *>(off + row * os);
+                    const uint4 *op = reinterpret_cast<const uint4 *>(off + prow * os);
 #pragma unroll
                     for (int i = 0; i < (int)(kP * 2 * sizeof(PT) / 16); ++i) {
                         const uint4 v = op[i];
                         ow[4 * i] = v.x, ow[4 * i + 1] = v.y, ow[4 * i + 2] = v.z, ow[4 * i + 3] = v.w;
                     }
                 }
-                const uint2 *lp = reinterpret_cast<const uint2 *>(logit + row * ls);
+                const uint2 *lp = reinterpret_cast<const uint2 *>(logit + prow * ls);
 #pragma unroll
                 for (int i = 0; i < (int)(kP * sizeof(PT) / 8); ++i) {
                     const uint2 v = lp[i];
@@ -358,7 +364,7 @@ __global__ __launch_bounds__(kWinThreads) void msda_fused_fwd_win(
 
 int64_t win_gmax(int64_t S) { return S / 8 + 2; }        // groups of 8 x 8 pixels of an H x W map with H * W <= S: at W = 1, H / 8 + 1
 
-template <typename VT, typename PT>
+template <typename VT, typename PT, int HSH>
 int launch(const void *value, const void *off, const void *logit, int64_t os, int64_t ls, const float *ref, const int64_t *shapes,
            const int64_t *lsi, int64_t N, int64_t S, int64_t M, int64_t Lq, int halo, void *ws, bool ws_ready, void *out,
            hipStream_t st) {
@@ -373,12 +379,12 @@ int launch(const void *value, const void *off, const void *logit, int64_t os, in
     const int side = kTile + 2 * (halo + 1);
     const int smem = side * side * kD * (int)sizeof(VT);
     if (smem > 64 * 1024) return fail(VAH_E_SHAPE, "msda fused forward (windows): a halo of %d pixels needs too much LDS", halo);
-    if (int rc = allow_dynamic_lds((const void *)msda_fused_fwd_win<VT, PT>, smem, "msda fused forward (windows)")) return rc;
+    if (int rc = allow_dynamic_lds((const void *)msda_fused_fwd_win<VT, PT, HSH>, smem, "msda fused forward (windows)")) return rc;
     // as many workgroups as there can be items, up to a few per CU slot: the kernel loops over the actual items
     int64_t grid = N * M * Gmax;
     if (grid > 16384) grid = 16384;
     grid = (grid + 7) / 8 * 8;
-    hipLaunchKernelGGL((msda_fused_fwd_win<VT, PT>), dim3((unsigned)grid), dim3(kWinThreads), smem, st, (const VT *)value,
+    hipLaunchKernelGGL((msda_fused_fwd_win<VT, PT, HSH>), dim3((unsigned)grid), dim3(kWinThreads), smem, st, (const VT *)value,
                        (const PT *)off, (const PT *)logit, os, ls, ref, (const unsigned char *)ws, Gmax, halo, S, (int)M, (int)N, Lq,
                        (VT *)out);
     return check_launch("msda fused forward (windows) launch");
@@ -407,7 +413,7 @@ int vah_msda_fused_forward_win(const void *value, int value_dtype, const int64_t
     clear_error();
     const char *fn = "vah_msda_fused_forward_win";
     if (N < 0 || S < 1 || M < 1 || Lq < 0 || halo < 0 || halo > 32 || M * D >= (1LL << 31)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (D != kD || P != kP) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32, P == 4 (one level)", fn);
+    if ((D != kD && D != 2 * kD) || P != kP) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32 or D == 64, P == 4 (one level)", fn);
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !ws || !out) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (int rc = msda_check_dtypes(fn, value_dtype, param_dtype, true)) return rc;
@@ -425,7 +431,8 @@ int vah_msda_fused_forward_win(const void *value, int value_dtype, const int64_t
                       4 * (N * S * M * D + 3 * N * Lq * M * P + N * Lq * M * D));
 #define VAH_CASE(VT, VC, PT, PC)                                                                                     \
     if (value_dtype == VC && param_dtype == PC)                                                                      \
-        return launch<VT, PT>(value, offsets, logits, os, ls, ref, shapes, lsi, N, S, M, Lq, (int)halo, ws, ws_holds_schedule != 0, out, st)
+        return D == kD ? launch<VT, PT, 0>(value, offsets, logits, os, ls, ref, shapes, lsi, N, S, M, Lq, (int)halo, ws, ws_holds_schedule != 0, out, st) \
+                       : launch<VT, PT, 1>(value, offsets, logits, os, ls, ref, shapes, lsi, N, S, 2 * M, Lq, (int)halo, ws, ws_holds_schedule != 0, out, st)
     VAH_CASE(float, 0, float, 0);
     VAH_CASE(__bf16, 1, __bf16, 1);
     VAH_CASE(__bf16, 1, float, 0);

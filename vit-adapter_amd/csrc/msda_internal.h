@@ -15,11 +15,11 @@ int msda_grad_taps_f32(const float *value, const int64_t *shapes, const int64_t 
 int64_t msda_ref_rows_per_image(int64_t ref_batch, int64_t N, int64_t Lq);
 
 // d(offsets), d(logits) of the fused core, nothing scattered (msda_fused.hip: msda_fused_bwd_vec4 / msda_fused_bwd).
-// rq: msda_ref_rows_per_image.
+// rq: msda_ref_rows_per_image.  D: 32, or 64 with fp32 values.
 int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi, const void *offsets,
                          const void *logits, int param_dtype, const float *ref, int64_t ref_levels, int64_t rq,
-                         const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t L, int64_t Lq, int64_t P, void *d_offsets,
-                         void *d_logits, hipStream_t st);
+                         const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
+                         void *d_offsets, void *d_logits, hipStream_t st);
 
 // Dtype codes of the fused core: 0 = fp32, 1 = bf16, 2 = fp16.  fp32 and bf16 mix freely between values and
 // parameters; fp16 comes in one form (values, offsets, logits - and every gradient - fp16) and only where f16_ok:

@@ -40,6 +40,14 @@
 //                      d(out)/d(attention) (round 2 formed them as 16 x 16 packed dot products per entry on the VALU:
 //                      a quarter of the kernel).
 //   3. msda_grad_finish (fused core only): per-sample gradient records -> d_offsets; softmax backward -> d_logits.
+//
+// Heads of 64 channels (fused core, D == 64): the matrix-core tile stays 32 channels x 32 pixels.  A (N,S,M,64) tensor
+// is bit for bit a (N,S,2M,32) one, so every pass runs on the 2M 32-channel HALF-HEADS as heads of their own (`M` in the
+// kernels and in the workspace bounds is that number) and a half-head row reads the offsets / logits of parameter row
+// `row >> HSH`.  The two halves of a head have identical lists; each owner tile computes the corner dot products over
+// ITS 32 channels, so a sample has two partial {d(offset x), d(offset y), d(out)/d(p)}: they are kept as fp32 records
+// per half-head row and msda_grad_finish adds them - half 0 + half 1 - and rounds once.  HSH is a template parameter:
+// the D == 32 instantiations are the code they were.
 #include <cstdlib>
 #include <type_traits>
 
@@ -72,7 +80,7 @@ constexpr int kTShY = 2, kTShX = 3;
 constexpr int kTilePx = kTW * kTH;
 constexpr int kP = 4;              // points per level on this path
 constexpr int kMaxL = 4;
-constexpr int kD = 32;
+constexpr int kD = 32;             // channels of a tile row: a head, or half of a 64-channel head
 constexpr int kCtrStride = 32;     // ints between two list counters (one 128-byte line each)
 constexpr int kBinTable = 2048;    // tiles of one level the LDS tables of the binning pass cover (more: global atomics)
 constexpr int kChunksPerWg = 8;    // a list longer than this many 64-entry chunks (by its even load) is shared
@@ -378,7 +386,8 @@ struct PlainSrc {
 // PT: type of offsets / logits; GPT: type their gradients are written in (the module's Linear layers take bf16
 // gradients under autocast also when their outputs are kept in fp32).  fp16: PT = GPT = _Float16 only; its rows need
 // 8-byte, not 16-byte, alignment (an fp16 [offsets | logits | gap] matrix has rows of 3 L P + 8 halves).
-template <typename PT, typename GPT, int L>
+// HSH: 1 when a head is two half-head rows (D == 64): `row` counts half-heads, parameters are read at row >> 1.
+template <typename PT, typename GPT, int L, int HSH>
 struct FusedSrc {
     const PT *off, *logit;
     const float *ref;
@@ -394,7 +403,9 @@ struct FusedSrc {
     // row's samples, and every partial store instruction costs a wave 64 cache-line visits whatever its width - one
     // 8-byte store per owned sample instead of a 4-byte d(offset) and a 4-byte d(p) store.  msda_grad_finish turns
     // the records into d_offsets and (softmax backward) d_logits.
-    static constexpr int RW = sizeof(GPT) == 2 ? 2 : 4;          // 32-bit words per record
+    // Half-heads (HSH): a sample has two owners, one per half; their partial sums stay fp32 (16-byte records, one per
+    // half-head row and sample) and msda_grad_finish adds them before the one rounding.
+    static constexpr int RW = (sizeof(GPT) == 2 && !HSH) ? 2 : 4;          // 32-bit words per record
     uint32_t *rec;
     __device__ __forceinline__ void pack(float gx, float gy, float ga_, uint32_t (&w)[RW]) const {
         if constexpr (RW == 2) {
@@ -440,11 +451,11 @@ struct FusedSrc {
     __device__ __forceinline__ Raw load(int row, int rr, int l) const {
         Raw r;
         if constexpr (std::is_same<PT, _Float16>::value) {
-            const uint2 *op = reinterpret_cast<const uint2 *>(off + row * os + l * kP * 2);       // 8-byte aligned
+            const uint2 *op = reinterpret_cast<const uint2 *>(off + (row >> HSH) * os + l * kP * 2);       // 8-byte aligned
             const uint2 v0 = op[0], v1 = op[1];
             r.o[0] = v0.x, r.o[1] = v0.y, r.o[2] = v1.x, r.o[3] = v1.y;
         } else {
-            const uint4 *op = reinterpret_cast<const uint4 *>(off + row * os + l * kP * 2);       // 16-byte aligned
+            const uint4 *op = reinterpret_cast<const uint4 *>(off + (row >> HSH) * os + l * kP * 2);       // 16-byte aligned
 #pragma unroll
             for (int i = 0; i < OW / 4; ++i) {
                 const uint4 v = op[i];
@@ -452,7 +463,7 @@ struct FusedSrc {
             }
         }
         r.rp = *reinterpret_cast<const float2 *>(ref + (rr * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
-        const uint2 *lp = reinterpret_cast<const uint2 *>(logit + row * ls);                       // 8-byte aligned
+        const uint2 *lp = reinterpret_cast<const uint2 *>(logit + (row >> HSH) * ls);              // 8-byte aligned
 #pragma unroll
         for (int i = 0; i < LW / 2; ++i) {
             const uint2 v = WEIGHTS ? lp[i] : make_uint2(0, 0);
@@ -1161,13 +1172,14 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
 // ---- fused core only: records -> d_offsets, d_logits ------------------------------------------------------------
 // d_logit[s] = p_s * (ga_s - sum_t p_t ga_t), p = softmax(logits of the (n, q, m) row), ga = d(out)/d(p) as the
 // tile pass (and, for gated samples, the binning pass) left it in the records; d_offset = the records' first two
-// numbers.  One thread per row.
-template <typename PT, typename GPT, int L>
+// numbers.  One thread per (n, q, head) row.  HSH: the row's samples have one fp32 record per half-head (rows 2 row and
+// 2 row + 1 of the scratch): added here, half 0 first, and rounded once.
+template <typename PT, typename GPT, int L, int HSH>
 __global__ __launch_bounds__(256) void msda_grad_finish(const PT *__restrict__ logit, int64_t ls, const uint32_t *__restrict__ rec,
                                                         int64_t rows, GPT *__restrict__ d_off, GPT *__restrict__ d_logit, int64_t dos,
                                                         int64_t dls) {
     constexpr int LP = L * kP;
-    constexpr int RW = sizeof(GPT) == 2 ? 2 : 4;
+    constexpr int RW = (sizeof(GPT) == 2 && !HSH) ? 2 : 4;
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
     float p[LP], g[LP];
@@ -1177,8 +1189,24 @@ __global__ __launch_bounds__(256) void msda_grad_finish(const PT *__restrict__ l
         p[s] = (float)logit[row * ls + s];
         mx = fmaxf(mx, p[s]);
     }
-    const uint4 *rp = reinterpret_cast<const uint4 *>(rec + row * LP * RW);
-    if constexpr (RW == 2) {
+    const uint4 *rp = reinterpret_cast<const uint4 *>(rec + (row << HSH) * LP * RW);
+    if constexpr (HSH) {
+        const uint4 *rp1 = rp + LP;          // the second half-head's records
+        auto f = [](uint32_t w) { return __builtin_bit_cast(float, w); };
+#pragma unroll
+        for (int s = 0; s < LP; s += 2) {
+            const uint4 a0 = rp[s], a1 = rp[s + 1], b0 = rp1[s], b1 = rp1[s + 1];
+            const float x0 = f(a0.x) + f(b0.x), y0 = f(a0.y) + f(b0.y), x1 = f(a1.x) + f(b1.x), y1 = f(a1.y) + f(b1.y);
+            g[s] = f(a0.z) + f(b0.z), g[s + 1] = f(a1.z) + f(b1.z);
+            if constexpr (sizeof(GPT) == 2) {          // 8-byte stores, see below
+                typename Half<GPT>::x4 o;
+                o[0] = (GPT)x0, o[1] = (GPT)y0, o[2] = (GPT)x1, o[3] = (GPT)y1;
+                *reinterpret_cast<typename Half<GPT>::x4 *>(d_off + row * dos + 2 * s) = o;
+            } else {
+                *reinterpret_cast<float4 *>(reinterpret_cast<float *>(d_off + row * dos) + 2 * s) = make_float4(x0, y0, x1, y1);
+            }
+        }
+    } else if constexpr (RW == 2) {
         uint32_t *dp = reinterpret_cast<uint32_t *>(d_off + row * dos);
 #pragma unroll
         for (int s = 0; s < LP; s += 4) {
@@ -1266,31 +1294,34 @@ int run_tiled(const char *fn, const Src &src, const Bounds &bd, const int64_t *s
 template <typename VT>
 constexpr bool kTapsInTile = std::is_same<VT, __bf16>::value || std::is_same<VT, _Float16>::value;
 
-template <typename VT, typename PT, typename GPT, int L>
+// M: heads; the passes run on M << HSH half-heads (bd is sized for them)
+template <typename VT, typename PT, typename GPT, int L, int HSH>
 int fused_tiled(const char *fn, const Bounds &bd, const void *value, const int64_t *shapes, const int64_t *lsi, const void *off,
                 const void *logit, int64_t os, int64_t ls, const float *ref, int ref_levels, int rq, int64_t N, int64_t M, int64_t Lq, int64_t S,
                 const void *grad_out, void *grad_value, int gv_16, void *d_off, void *d_logit, int64_t dos, int64_t dls, void *ws,
                 hipStream_t st) {
     constexpr bool TAPS = kTapsInTile<VT>;
     uint32_t *rec = (uint32_t *)((char *)ws + bd.off_ga);
-    FusedSrc<PT, GPT, L> src{(const PT *)off, (const PT *)logit, ref, ref_levels, rq, (int)os, (int)ls, rec};
+    typedef FusedSrc<PT, GPT, L, HSH> Src;
+    const int64_t Mh = M << HSH;
+    Src src{(const PT *)off, (const PT *)logit, ref, ref_levels, rq, (int)os, (int)ls, rec};
     int rc;
     if constexpr (std::is_same<VT, _Float16>::value) {          // fp16: one form, grad_value in fp16
-        rc = run_tiled<VT, VT, FusedSrc<PT, GPT, L>, TAPS>(fn, src, bd, shapes, lsi, N, M, L, Lq, S, (const VT *)value,
+        rc = run_tiled<VT, VT, Src, TAPS>(fn, src, bd, shapes, lsi, N, Mh, L, Lq, S, (const VT *)value,
                                                            (const VT *)grad_out, (VT *)grad_value, ws, st);
     } else if (gv_16) {
         if constexpr (std::is_same<VT, __bf16>::value)
-            rc = run_tiled<VT, __bf16, FusedSrc<PT, GPT, L>, TAPS>(fn, src, bd, shapes, lsi, N, M, L, Lq, S, (const VT *)value,
+            rc = run_tiled<VT, __bf16, Src, TAPS>(fn, src, bd, shapes, lsi, N, Mh, L, Lq, S, (const VT *)value,
                                                                  (const VT *)grad_out, (__bf16 *)grad_value, ws, st);
         else
             return fail(VAH_E_UNSUPPORTED, "%s: a bf16 grad_value needs bf16 values", fn);
     } else {
-        rc = run_tiled<VT, float, FusedSrc<PT, GPT, L>, TAPS>(fn, src, bd, shapes, lsi, N, M, L, Lq, S, (const VT *)value,
+        rc = run_tiled<VT, float, Src, TAPS>(fn, src, bd, shapes, lsi, N, Mh, L, Lq, S, (const VT *)value,
                                                             (const VT *)grad_out, (float *)grad_value, ws, st);
     }
     if (rc || !TAPS) return rc;
     const int64_t rows = N * Lq * M;
-    hipLaunchKernelGGL((msda_grad_finish<PT, GPT, L>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, (const PT *)logit, ls,
+    hipLaunchKernelGGL((msda_grad_finish<PT, GPT, L, HSH>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, (const PT *)logit, ls,
                        (const uint32_t *)rec, rows, (GPT *)d_off, (GPT *)d_logit, dos, dls);
     return check_launch(fn);
 }
@@ -1303,7 +1334,7 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
                               int64_t d_offsets_stride, int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
     clear_error();
     if (N < 0 || S < 1 || M < 1 || Lq < 0 || M * D >= (1LL << 31)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
-    if (D != kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32", fn);
+    if (D != kD && D != 2 * kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32 or D == 64", fn);
     if (ref_levels != 1 && ref_levels != L) return fail(VAH_E_SHAPE, "%s: ref_levels must be 1 or L", fn);
     if (ref_batch != 1 && ref_batch != N)
         return fail(VAH_E_SHAPE, "%s: ref_batch must be 1 or N (%lld), got %lld", fn, (long long)N, (long long)ref_batch);
@@ -1329,8 +1360,9 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
     // the passes index ref in int: N * Lq * ref_levels * 2 <= N * Lq * 2 * L < N * Lq * M * os < 2^31 by the check above
     // (os >= 2 * L * P)
     const int64_t rq = msda_ref_rows_per_image(ref_batch, N, Lq);
+    // everything in the workspace is per 32-channel head slice: M * (D / 32) of them (what vah_msda_tile_ws_bytes is asked with)
     Bounds bd;
-    if (int rc = make_bounds(fn, N, S, M, L, Lq, P, &bd)) return rc;
+    if (int rc = make_bounds(fn, N, S, M * (D / kD), L, Lq, P, &bd)) return rc;
     if (ws_bytes < bd.total) return fail(VAH_E_SHAPE, "%s: workspace too small (%lld < %lld)", fn, (long long)ws_bytes, (long long)bd.total);
     hipStream_t st = (hipStream_t)stream;
     LaunchScope scope(f16 ? "msda_fused_bwd_f16" : "msda_fused_bwd", vs * (N * S * M * D + N * Lq * M * D) + gs * N * S * M * D + (ps + gps) * 3 * N * Lq * M * L * P, st,
@@ -1341,13 +1373,15 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
         if (grad_param_dtype != param_dtype || strided)
             return fail(VAH_E_UNSUPPORTED, "%s: fp32 values write gradients in the parameter dtype, contiguous tensors only", fn);
         if (int rc = msda_fused_grad_taps(value, value_dtype, shapes, lsi, offsets, logits, param_dtype, ref, ref_levels, rq, grad_out,
-                                          N, S, M, L, Lq, P, d_offsets, d_logits, st))
+                                          N, S, M, D, L, Lq, P, d_offsets, d_logits, st))
             return rc;
     }
 #define VAH_CASE(VT, VC, PT, PC, GPT, GC, LL)                                                                              \
     if (value_dtype == VC && param_dtype == PC && grad_param_dtype == GC && L == LL)                                      \
-        return fused_tiled<VT, PT, GPT, LL>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, (int)rq, N, M, Lq, S, \
-                                            grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)
+        return D == kD ? fused_tiled<VT, PT, GPT, LL, 0>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, (int)rq, N, M, Lq, S, \
+                                                         grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)                 \
+                       : fused_tiled<VT, PT, GPT, LL, 1>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, (int)rq, N, M, Lq, S, \
+                                                         grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)
 #define VAH_CASES(LL)                                  \
     VAH_CASE(float, 0, float, 0, float, 0, LL);        \
     VAH_CASE(__bf16, 1, __bf16, 1, __bf16, 1, LL);     \

@@ -27,15 +27,24 @@ def _fp16_enabled():
     return fused.ENABLED['fp16_msda']
 
 
+def tile_ws_bytes(N, S, M, D, L, Lq, P):
+    """vah_msda_tile_ws_bytes for heads of D channels: the workspace is sized per 32-channel head slice (< 0: the tile
+    pass does not take the problem)."""
+    return _vah.lib.vah_msda_tile_ws_bytes(N, S, M * (D // 32), L, Lq, P)
+
+
+def _tile_pass_serves(value, offsets, n_levels, n_points):
+    N, S, M, D = value.shape
+    return tiled_backward(n_levels, n_points) and tile_ws_bytes(N, S, M, D, n_levels, offsets.shape[1], n_points) >= 0
+
+
 def _dtypes_ok(value, offsets, logits, n_levels, n_points):
     """fp32 and bf16 mix between the values and the parameters; fp16 comes in one form - value, offsets and logits all
     fp16 - and has no atomic backward, so only where the tile pass serves (L, P) and the problem's size."""
     if logits.dtype != offsets.dtype or value.dtype not in _DT or offsets.dtype not in _DT:
         return False
     if torch.float16 in (value.dtype, offsets.dtype):
-        return (value.dtype == offsets.dtype and tiled_backward(n_levels, n_points) and _fp16_enabled()
-                and _vah.lib.vah_msda_tile_ws_bytes(value.shape[0], value.shape[1], value.shape[2], n_levels,
-                                                    offsets.shape[1], n_points) >= 0)
+        return value.dtype == offsets.dtype and _fp16_enabled() and _tile_pass_serves(value, offsets, n_levels, n_points)
     return True
 
 
@@ -58,6 +67,8 @@ def fused_supported(value, offsets, logits, reference_points, n_levels, n_points
     return (value.is_cuda and value.dim() == 4 and _dtypes_ok(value, offsets, logits, n_levels, n_points)
             and ref_points_ok(reference_points, value.shape[0], n_levels)
             and bool(_vah.lib.vah_msda_fused_supported(value.shape[-1], n_levels, n_points))
+            # 64-channel heads, like fp16, have no atomic backward: only where the tile pass serves
+            and (value.shape[-1] != 64 or _tile_pass_serves(value, offsets, n_levels, n_points))
             and value.numel() > 0 and offsets.numel() > 0)
 
 
@@ -168,8 +179,8 @@ def fused_forward(value, spatial_shapes, level_start_index, offsets, logits, o_s
 
 
 class MSDeformAttnFusedFunction(Function):
-    """apply(value (N,S,M,32), spatial_shapes, level_start_index, offsets (N,Lq,M,L,P,2),
-    logits (N,Lq,M,L*P), reference_points (1|N,Lq,1|L,2)) -> (N, Lq, M*32) in value's dtype.
+    """apply(value (N,S,M,D), D in (32, 64), spatial_shapes, level_start_index, offsets (N,Lq,M,L,P,2),
+    logits (N,Lq,M,L*P), reference_points (1|N,Lq,1|L,2)) -> (N, Lq, M*D) in value's dtype.
     Gradients: grad_value in value's dtype, d_offsets / d_logits in the offsets' (fp16 for fp16 operands).
     reference_points with shape[0] == N are one grid per image (the Mask2Former pixel decoder's grid times valid ratios,
     padded batches through the drop-in MSDeformAttn): the same kernels with a batch term in the reference read.  They
@@ -198,9 +209,10 @@ class MSDeformAttnFusedFunction(Function):
         if ctx.tiled:
             # atomic-free tile pass (csrc/msda_tile.hip): grad_value is STORED, in the value's dtype.  Nothing about the
             # level geometry is read back to the host: grid and workspace follow from the tensor shapes.
-            ws_bytes = _vah.lib.vah_msda_tile_ws_bytes(N, S, M, L, Lq, P)
-            if ws_bytes < 0 and value.dtype == torch.float16:
-                raise RuntimeError('fused MSDeformAttn: no fp16 backward for this problem size (%s)' % _vah.lib.vah_last_error().decode())
+            ws_bytes = tile_ws_bytes(N, S, M, D, L, Lq, P)
+            if ws_bytes < 0 and (value.dtype == torch.float16 or D == 64):
+                raise RuntimeError('fused MSDeformAttn: no %s backward for this problem size (%s)'
+                                   % ('fp16' if value.dtype == torch.float16 else '64-channel', _vah.lib.vah_last_error().decode()))
             if ws_bytes >= 0:
                 gdt = offsets.dtype
                 d_off = torch.empty(offsets.shape, dtype=gdt, device=offsets.device)

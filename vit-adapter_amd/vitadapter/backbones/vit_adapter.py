@@ -194,6 +194,18 @@ PRESETS = {
                      deform_num_heads=6, cffn_ratio=0.25, deform_ratio=1.0,
                      interaction_indexes=[[0, 2], [3, 5], [6, 8], [9, 11]],
                      window_attn=[False] * 12, window_size=[None] * 12),
+    # seg/configs/ade20k/upernet_deit_adapter_small_512_160k_ade20k.py:10-26 (deformable heads of 384 / 6 = 64 channels)
+    'small_seg': dict(flavour='seg', patch_size=16, embed_dim=384, depth=12, num_heads=6,
+                      mlp_ratio=4, drop_path_rate=0.2, conv_inplane=64, n_points=4,
+                      deform_num_heads=6, cffn_ratio=0.25, deform_ratio=1.0,
+                      interaction_indexes=[[0, 2], [3, 5], [6, 8], [9, 11]],
+                      window_attn=[False] * 12, window_size=[None] * 12),
+    # det/configs/mask_rcnn/mask_rcnn_deit_adapter_small_fpn_3x_coco.py:11-29
+    'small_det': dict(flavour='det', patch_size=16, embed_dim=384, depth=12, num_heads=6,
+                      mlp_ratio=4, drop_path_rate=0.2, conv_inplane=64, n_points=4,
+                      deform_num_heads=6, cffn_ratio=0.25, deform_ratio=1.0,
+                      interaction_indexes=[[0, 2], [3, 5], [6, 8], [9, 11]],
+                      window_attn=[True, True, False] * 4, window_size=[14, 14, None] * 4),
     # det/configs/mask_rcnn/mask_rcnn_deit_adapter_base_fpn_3x_coco.py:10-29
     'base_det': dict(flavour='det', patch_size=16, embed_dim=768, depth=12, num_heads=12,
                      mlp_ratio=4, drop_path_rate=0.3, conv_inplane=64, n_points=4,

@@ -883,7 +883,7 @@ class _MSDAPairCore(torch.autograd.Function):
         gout = gout.contiguous().to(value.dtype)
         g = torch.empty((R, M * PS), dtype=torch.bfloat16, device=x2.device)
         grad_value = torch.empty_like(value)
-        ws_bytes = _vah.lib.vah_msda_tile_ws_bytes(N, S, M, L, Lq, P)
+        ws_bytes = _vah.lib.vah_msda_tile_ws_bytes(N, S, M * (D // 32), L, Lq, P)      # per 32-channel head slice
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device)
         with _vah.on(value.device):
             rc = _vah.lib.vah_msda_fused_backward_tiled_nref(
@@ -906,21 +906,22 @@ class _MSDAPairCore(torch.autograd.Function):
 
 def msda_pair_core_ok(mod, query, value, reference_points):
     """The one-node form of MSDeformAttn's offsets / weights pair + core: bf16 autocast on the GPU with bf16 values, the
-    tile-pass backward and shapes the fused kernels cover (D == 32, P == 4, L in {1, 3, 4}), reference points shared by
+    tile-pass backward and shapes the fused kernels cover (D in {32, 64}, P == 4, L in {1, 3, 4}), reference points shared by
     the batch or one grid per image (not learned ones: ops.functions.ms_deform_attn_fused.ref_points_ok)."""
     import os
     from ops.functions.ms_deform_attn_fused import ref_points_ok
     a, b = mod.sampling_offsets, mod.attention_weights
     M, L, P = mod.n_heads, mod.n_levels, mod.n_points
     return (ENABLED['linear'] and ENABLED['linear_pair'] and ENABLED['pair_core'] and query.is_cuda and _bf16_autocast()
-            and value.dtype == torch.bfloat16 and value.dim() == 4 and value.shape[-1] == 32 and P == 4 and L in (1, 3, 4)
+            and value.dtype == torch.bfloat16 and value.dim() == 4 and value.shape[-1] in (32, 64) and P == 4 and L in (1, 3, 4)
             and (M * 3 * L * P) % 8 == 0            # rows of the pair GEMM / its column sums: 16-byte multiples
             and type(a) is torch.nn.Linear and type(b) is torch.nn.Linear and a.bias is not None and b.bias is not None
             and a.weight.dtype == torch.float32 and b.weight.dtype == torch.float32 and a.weight.shape[1] % 8 == 0
             and ref_points_ok(reference_points, value.shape[0], L)
             and query.numel() > 0 and value.numel() > 0 and query.dtype in (torch.bfloat16, torch.float32)
             and os.environ.get('VAH_MSDA_FUSED', '1') != '0' and os.environ.get('VAH_MSDA_TILED', '1') != '0'
-            and _vah.lib.vah_msda_tile_ws_bytes(value.shape[0], value.shape[1], M, L, query.shape[1], P) >= 0)
+            and _vah.lib.vah_msda_tile_ws_bytes(value.shape[0], value.shape[1], M * (value.shape[-1] // 32), L,
+                                                query.shape[1], P) >= 0)
 
 
 def msda_pair_core(mod, query, value, shapes, lsi, reference_points):
