@@ -169,6 +169,19 @@ for _name in EXPORTS:
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = SIGNATURES[_PARENT.get(_name, _name)]        # a twin: its parent's signature
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_msda_box.h declares (the fused MSDeformAttn core
+# with reference boxes): the *_nref signatures with one int64 ref_comps directly after ref_batch.  The dtype is an
+# argument, so there are no fp16 twins.  tests/test_msda_box_abi_cpu.py holds each entry to its prototype.
+BOX_SIGNATURES = {
+    'vah_msda_fused_forward_box': (_int, [_p, _int, _p, _p, _p, _p, _int, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                          _i64, _p, _p]),
+    'vah_msda_fused_backward_tiled_box': (_int, [_p, _int, _p, _p, _p, _p, _int, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64,
+                                                 _i64, _i64, _p, _int, _p, _p, _int, _i64, _i64, _p, _i64, _p]),
+}
+for _name, (_res, _args) in BOX_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

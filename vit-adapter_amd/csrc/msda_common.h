@@ -51,6 +51,27 @@ __device__ __forceinline__ Tap<T> make_tap(T lx, T ly, int H, int W) {
     return t;
 }
 
+// Reference of one (image, query, level) as the fused core reads it: a point (x, y), or - BOX - a box (cx, cy, w, h).
+// The reference module forms the sampling location of offset `off` as (detection/ops/modules/ms_deform_attn.py:117-122)
+//     point  loc = ref + off / (W, H)
+//     box    loc = ref[:2] + off / P * ref[2:] * 0.5
+// box_loc is the one spelling of the second line that the forward, the binning pass, the tile pass and the gather
+// kernels share (the tile pass owns a sample by its location: they have to agree to the bit); box_grad_scale is
+// d(off) / d(pixel coordinate), the factor that turns the pixel-space gradient the kernels accumulate into d(offsets):
+// d off.x = d out / d loc.x * w * 0.5 / P = gx * W * w * 0.5 / P (point form: gx, the level size cancels).
+template <bool BOX> struct RefRaw { typedef float2 type; };
+template <> struct RefRaw<true> { typedef float4 type; };
+
+template <int P>
+__device__ __forceinline__ float2 box_loc(const float4 &b, float ox, float oy) {
+    // an explicit fma: what -ffp-contract=fast makes of c + (o * 0.5 / P) * wh where it can, spelled so that it does everywhere
+    return make_float2(__builtin_fmaf(ox * (0.5f / P), b.z, b.x), __builtin_fmaf(oy * (0.5f / P), b.w, b.y));
+}
+template <int P>
+__device__ __forceinline__ float2 box_grad_scale(const float4 &b, int H, int W) {
+    return make_float2((float)W * ((0.5f / P) * b.z), (float)H * ((0.5f / P) * b.w));
+}
+
 struct Level {
     int H, W;
     int64_t start;

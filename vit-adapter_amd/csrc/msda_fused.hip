@@ -25,11 +25,18 @@
 // parameter row `row >> 1`.  The atomic backward (vah_msda_fused_backward[_nref]) stays at D == 32: like fp16, D == 64
 // exists only where the tile pass serves.
 //
-// Restrictions of this path: D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, reference points with last dim 2,
+// Restrictions of this path: D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, reference points with last dim 2 or 4,
 // shared by the batch (the adapter's) or one grid per image (the Mask2Former pixel decoder's grid times
 // valid ratios, segmentation/mmseg_custom/models/plugins/msdeformattn_pixel_decoder.py:224-240): `rq`, the
 // rows of ref between consecutive images, is a run-time kernel argument, 0 for a shared grid.
 // Everything else uses the unfused Function.
+//
+// Reference BOXES (last dim 4: (cx, cy, w, h), what the iterative-refinement decoders pass,
+// segmentation/mmseg_custom/models/utils/transformer.py:595-615): loc = c + off / P * (w, h) * 0.5
+// (detection/ops/modules/ms_deform_attn.py:120-122) and d(offsets) = d(out)/d(loc) * (w, h) * 0.5 / P.  BOX is a template
+// parameter of the forward and of the two gather kernels (msda_common.h: box_loc, box_grad_scale); the point-form
+// instantiations are the code they were.  Boxes exist where the tile pass serves, like fp16 and D == 64: the atomic
+// backward (vah_msda_fused_backward[_nref]) and the window forward have no box form.
 #include <cstdlib>
 #include <type_traits>
 
@@ -116,7 +123,7 @@ struct TapF {           // one sampling tap as the channel lanes of a row read i
     float w[4];         // bilinear weight of the corner (0 for an invalid corner)
 };
 
-template <typename VT, typename PT, int L, int P, int D>
+template <typename VT, typename PT, int L, int P, int D, bool BOX>
 __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const PT *__restrict__ off, const PT *__restrict__ logit, int64_t os, int64_t ls, const float *__restrict__ ref,
@@ -142,8 +149,15 @@ __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
             const int64_t q = w % Lq, n = w / Lq / M;
             const int64_t rw = (n * Lq + q) * M + (w / Lq) % M;
             const float2 o = load2(off + rw * os + sidx * 2);
-            const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
-            const Tap<float> t = make_tap<float>(rp.x + o.x / (float)lv.W, rp.y + o.y / (float)lv.H, lv.H, lv.W);
+            Tap<float> t;
+            if constexpr (BOX) {
+                const float4 rb = *reinterpret_cast<const float4 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 4);
+                const float2 xy = box_loc<P>(rb, o.x, o.y);
+                t = make_tap<float>(xy.x, xy.y, lv.H, lv.W);
+            } else {
+                const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+                t = make_tap<float>(rp.x + o.x / (float)lv.W, rp.y + o.y / (float)lv.H, lv.H, lv.W);
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 tl.row[k] = t.row[k];
@@ -205,8 +219,8 @@ __global__ __launch_bounds__(kBlock) void msda_fused_fwd(
 // global_atomic_add_f32 on whole 128-byte rows; d(offsets), d(logits) written in PT
 // ---------------------------------------------------------------------------------------
 // near_radius == kNoScatter: grad_value is left to the tile pass (msda_tile.hip) and nothing is scattered here;
-// otherwise every sample's four corners are scattered with float atomics.
-template <typename VT, typename PT, int L, int P>
+// otherwise every sample's four corners are scattered with float atomics.  BOX: the gather mode only (nothing scatters).
+template <typename VT, typename PT, int L, int P, bool BOX>
 __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const PT *__restrict__ off, const PT *__restrict__ logit, const float *__restrict__ ref,
@@ -234,20 +248,32 @@ __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
 #pragma unroll
     for (int l = 0; l < L; ++l) {
         const Level lv = read_level(shapes, lsi, l, S);
-        const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+        constexpr int RC = BOX ? 4 : 2;
+        const typename RefRaw<BOX>::type rp =
+            *reinterpret_cast<const typename RefRaw<BOX>::type *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * RC);
         const int64_t lstart = lv.valid ? lv.start : 0;      // the gathers below are unconditional: stay in bounds
         const VT *vl = value + head_off + lstart * stride;
         float *gvl = grad_value + head_off + lstart * stride;
         Tap<float> t[P];
         float v[P][4];
         bool scatter[P];
+        float2 gsc = make_float2(1.f, 1.f);      // d(off) / d(pixel coordinate); an invalid level's samples give nothing
+        if constexpr (BOX) {
+            gsc = box_grad_scale<P>(rp, lv.H, lv.W);
+            gsc = make_float2(lv.valid ? gsc.x : 0.f, lv.valid ? gsc.y : 0.f);
+        }
 #pragma unroll
         for (int u = 0; u < P; ++u) {
             const float2 o = load2(op + 2 * (l * P + u));
-            scatter[u] = near_radius != kNoScatter;
+            scatter[u] = !BOX && near_radius != kNoScatter;
             // an invalid level gates every sample off (W = H = 0 would not): use a location that fails
-            t[u] = make_tap<float>(lv.valid ? rp.x + o.x / (float)lv.W : -8.f,
-                                   lv.valid ? rp.y + o.y / (float)lv.H : -8.f, max(lv.H, 1), max(lv.W, 1));
+            if constexpr (BOX) {
+                const float2 xy = box_loc<P>(rp, o.x, o.y);
+                t[u] = make_tap<float>(lv.valid ? xy.x : -8.f, lv.valid ? xy.y : -8.f, max(lv.H, 1), max(lv.W, 1));
+            } else {
+                t[u] = make_tap<float>(lv.valid ? rp.x + o.x / (float)lv.W : -8.f,
+                                       lv.valid ? rp.y + o.y / (float)lv.H : -8.f, max(lv.H, 1), max(lv.W, 1));
+            }
         }
 #pragma unroll
         for (int u = 0; u < P; ++u)
@@ -270,9 +296,10 @@ __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
             const float val = t[u].cw[0] * v[u][0] + t[u].cw[1] * v[u][1] + t[u].cw[2] * v[u][2] +
                               t[u].cw[3] * v[u][3];
             ga[s] = dpp_sum32_hi(g * val);          // valid on lanes 16..31 of the row
-            // d loc = W * gw * tv  and  d off = d loc / W: the level size cancels
+            // d loc = W * gw * tv  and  d off = d loc / W: the level size cancels (a box: d off = d loc * w * 0.5 / P)
             gx[s] = dpp_sum32_hi(gw * tv);
             gy[s] = dpp_sum32_hi(gh * tv);
+            if constexpr (BOX) gx[s] *= gsc.x, gy[s] *= gsc.y;
         }
     }
     // softmax backward + stores: lane 16 + s of the row handles sample s (LP <= 16)
@@ -296,7 +323,7 @@ __global__ __launch_bounds__(kBlock) void msda_fused_bwd(
 struct TapL {
     int row[4];        // token index of the corner inside its level, -1 = invalid corner
     float lh, lw;
-    int pad[2];
+    int pad[2];        // BOX: the bits of d(off) / d(pixel coordinate), x and y (box_grad_scale)
 };
 
 #ifndef VAH_BWDA_WAVES1
@@ -305,7 +332,7 @@ struct TapL {
 #ifndef VAH_BWDA_WAVESN
 #define VAH_BWDA_WAVESN 3
 #endif
-template <typename VT, typename PT, int L, int P, int D>
+template <typename VT, typename PT, int L, int P, int D, bool BOX>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(VT) == 2 ? (L == 1 ? VAH_BWDA_WAVES1 : VAH_BWDA_WAVESN) : 1)))   // fp32 values would spill
 void msda_fused_bwd_vec4(
     const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
@@ -334,9 +361,18 @@ void msda_fused_bwd_vec4(
             const int64_t rw = (n * Lq + q) * M + (w / Lq) % M;
             const Level lv = read_level(shapes, lsi, l, S);
             const float2 o = load2(off + (rw * LP + sidx) * 2);
-            const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
-            const Tap<float> t = make_tap<float>(lv.valid ? rp.x + o.x / (float)lv.W : -8.f,
-                                                 lv.valid ? rp.y + o.y / (float)lv.H : -8.f, max(lv.H, 1), max(lv.W, 1));
+            Tap<float> t;
+            if constexpr (BOX) {
+                const float4 rb = *reinterpret_cast<const float4 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 4);
+                const float2 xy = box_loc<P>(rb, o.x, o.y), gsc = box_grad_scale<P>(rb, lv.H, lv.W);
+                t = make_tap<float>(lv.valid ? xy.x : -8.f, lv.valid ? xy.y : -8.f, max(lv.H, 1), max(lv.W, 1));
+                tl.pad[0] = __builtin_bit_cast(int, lv.valid ? gsc.x : 0.f);      // an invalid level's samples give nothing
+                tl.pad[1] = __builtin_bit_cast(int, lv.valid ? gsc.y : 0.f);
+            } else {
+                const float2 rp = *reinterpret_cast<const float2 *>(ref + ((n * rq + q) * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+                t = make_tap<float>(lv.valid ? rp.x + o.x / (float)lv.W : -8.f,
+                                    lv.valid ? rp.y + o.y / (float)lv.H : -8.f, max(lv.H, 1), max(lv.W, 1));
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) tl.row[k] = (lv.valid && t.ok[k]) ? t.row[k] : -1;
             tl.lh = t.lh;
@@ -418,6 +454,10 @@ void msda_fused_bwd_vec4(
         const int s = i * LANES + sub;
         if (s < LP) {
             d_logit[row * LP + s] = (PT)(p_m[i] * (ga_m[i] - dot));
+            if constexpr (BOX) {        // pixel-space gradient -> d(offsets), in fp32 ahead of store2's rounding
+                const TapL *ts = s_tap + rl * LP + s;
+                gx_m[i] *= __builtin_bit_cast(float, ts->pad[0]), gy_m[i] *= __builtin_bit_cast(float, ts->pad[1]);
+            }
             store2(d_off + (row * LP + s) * 2, gx_m[i], gy_m[i]);
         }
     }
@@ -429,6 +469,7 @@ struct FusedArgs {
     const float *ref;
     int ref_levels;
     int64_t rq = 0;                  // rows of ref between consecutive images: Lq for a per-image grid, 0 for a shared one
+    bool box = false;                // ref holds boxes (cx, cy, w, h), not points
     int64_t N, S, M, L, Lq, P;
     int64_t D = kD;                  // channels per head: 32 or 64
     void *out;
@@ -439,22 +480,23 @@ struct FusedArgs {
     hipStream_t st;
 };
 
-template <typename VT, typename PT, int L, int P, int D>
+template <typename VT, typename PT, int L, int P, int D, bool BOX>
 int launch_fwd(const FusedArgs &a) {
     constexpr int RPB = kBlock / (D / 4);          // rows per block
     const int64_t rows = a.N * a.Lq * a.M;
     const int64_t nblocks = (rows + RPB - 1) / RPB;
     const int64_t grid = (nblocks + 7) / 8 * 8;
     if (grid >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "msda fused forward: grid too large");
-    hipLaunchKernelGGL((msda_fused_fwd<VT, PT, L, P, D>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
+    hipLaunchKernelGGL((msda_fused_fwd<VT, PT, L, P, D, BOX>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
                        (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.os ? a.os : L * P * 2,
                        a.ls ? a.ls : L * P, a.ref, a.ref_levels, a.rq, a.S, (int)a.M, a.Lq, rows, nblocks, (VT *)a.out);
     return check_launch("msda fused forward launch");
 }
 
-template <typename VT, typename PT, int L, int P, int D>
+template <typename VT, typename PT, int L, int P, int D, bool BOX>
 int launch_bwd(const FusedArgs &a) {
     const int64_t rows = a.N * a.Lq * a.M;
+    if (BOX && !a.taps_only) return fail(VAH_E_UNSUPPORTED, "msda fused backward: the atomic backward has no box form");
     if constexpr (D != kD) {
         // D == 64: the gradients of the parameters for the tile pass, fp32 values (see msda_fused_bwd_vec4)
         if constexpr (std::is_same<VT, float>::value) {
@@ -463,7 +505,7 @@ int launch_bwd(const FusedArgs &a) {
             const int64_t nb = (rows + RPB - 1) / RPB;
             const int64_t gridd = (nb + 7) / 8 * 8;
             if (gridd >= ((int64_t)1 << 31)) return fail(VAH_E_SHAPE, "msda fused backward: grid too large");
-            hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P, D>), dim3((unsigned)gridd), dim3(kBlock), 0, a.st,
+            hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P, D, BOX>), dim3((unsigned)gridd), dim3(kBlock), 0, a.st,
                                (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.ref,
                                a.ref_levels, a.rq, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nb, kNoScatter,
                                a.grad_value, (PT *)a.d_off, (PT *)a.d_logit);
@@ -478,7 +520,7 @@ int launch_bwd(const FusedArgs &a) {
     const bool wide = a.N * a.S * a.M * kD * (int64_t)sizeof(VT) >= ((int64_t)1 << 32);   // vec4 kernel: 32-bit offsets
     if (!a.taps_only || wide) {
         // one lane per channel; scatters grad_value with atomics unless the tile pass owns it (taps_only)
-        hipLaunchKernelGGL((msda_fused_bwd<VT, PT, L, P>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
+        hipLaunchKernelGGL((msda_fused_bwd<VT, PT, L, P, BOX>), dim3((unsigned)grid), dim3(kBlock), 0, a.st,
                            (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.ref,
                            a.ref_levels, a.rq, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nblocks,
                            a.taps_only ? kNoScatter : -1.f, a.grad_value, (PT *)a.d_off, (PT *)a.d_logit);
@@ -486,7 +528,7 @@ int launch_bwd(const FusedArgs &a) {
     }
     const int64_t nb8 = (rows + (kBlock / 8) - 1) / (kBlock / 8);
     const int64_t grid8 = (nb8 + 7) / 8 * 8;
-    hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P, kD>), dim3((unsigned)grid8), dim3(kBlock), 0, a.st,
+    hipLaunchKernelGGL((msda_fused_bwd_vec4<VT, PT, L, P, kD, BOX>), dim3((unsigned)grid8), dim3(kBlock), 0, a.st,
                        (const VT *)a.value, a.shapes, a.lsi, (const PT *)a.off, (const PT *)a.logit, a.ref,
                        a.ref_levels, a.rq, (const VT *)a.grad_out, a.S, (int)a.M, a.Lq, rows, nb8, kNoScatter,
                        a.grad_value, (PT *)a.d_off, (PT *)a.d_logit);
@@ -494,18 +536,23 @@ int launch_bwd(const FusedArgs &a) {
     }
 }
 
-template <bool BWD, typename VT, typename PT, int D>
-int dispatch_lpd(const FusedArgs &a) {
+template <bool BWD, typename VT, typename PT, int D, bool BOX>
+int dispatch_lpdb(const FusedArgs &a) {
 #define VAH_CASE(LL, PP)                                                        \
     if (a.L == LL && a.P == PP) {                                               \
-        if constexpr (BWD) return launch_bwd<VT, PT, LL, PP, D>(a);             \
-        else return launch_fwd<VT, PT, LL, PP, D>(a);    /* (fp16 has no backward instantiation here) */ \
+        if constexpr (BWD) return launch_bwd<VT, PT, LL, PP, D, BOX>(a);        \
+        else return launch_fwd<VT, PT, LL, PP, D, BOX>(a);    /* (fp16 has no backward instantiation here) */ \
     }
     VAH_CASE(1, 4);
     VAH_CASE(3, 4);
     VAH_CASE(4, 4);
 #undef VAH_CASE
     return fail(VAH_E_UNSUPPORTED, "msda fused: (L, P) = (%lld, %lld) not instantiated", (long long)a.L, (long long)a.P);
+}
+
+template <bool BWD, typename VT, typename PT, int D>
+int dispatch_lpd(const FusedArgs &a) {
+    return a.box ? dispatch_lpdb<BWD, VT, PT, D, true>(a) : dispatch_lpdb<BWD, VT, PT, D, false>(a);
 }
 
 template <bool BWD, typename VT, typename PT>
@@ -542,6 +589,11 @@ int check_common(const char *fn, int64_t N, int64_t S, int64_t M, int64_t D, int
 // (ref_batch == N == 1 is the shared form).  ((N - 1) * Lq + q) * ref_levels * 2 is formed in int64_t in this file.
 int64_t msda_ref_rows_per_image(int64_t ref_batch, int64_t N, int64_t Lq) { return ref_batch == N && N > 1 ? Lq : 0; }
 
+int msda_check_ref_comps(const char *fn, int64_t ref_comps) {
+    if (ref_comps == 2 || ref_comps == 4) return VAH_OK;
+    return fail(VAH_E_SHAPE, "%s: ref_comps must be 2 (points) or 4 (boxes), got %lld", fn, (long long)ref_comps);
+}
+
 int msda_check_dtypes(const char *fn, int value_dtype, int param_dtype, bool f16_ok) {
     const bool wide = (value_dtype | param_dtype) & ~1;          // a code other than 0 / 1 somewhere
     if (!wide || (f16_ok && value_dtype == 2 && param_dtype == 2)) return VAH_OK;
@@ -553,12 +605,12 @@ int msda_check_dtypes(const char *fn, int value_dtype, int param_dtype, bool f16
 
 int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi, const void *offsets,
                          const void *logits, int param_dtype, const float *ref, int64_t ref_levels, int64_t rq,
-                         const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
-                         void *d_offsets, void *d_logits, hipStream_t st) {
+                         int64_t ref_comps, const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L,
+                         int64_t Lq, int64_t P, void *d_offsets, void *d_logits, hipStream_t st) {
     FusedArgs a{};
     a.D = D;
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
-    a.ref_levels = (int)ref_levels, a.rq = rq, a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P;
+    a.ref_levels = (int)ref_levels, a.rq = rq, a.box = ref_comps == 4, a.N = N, a.S = S, a.M = M, a.L = L, a.Lq = Lq, a.P = P;
     a.grad_out = grad_out, a.d_off = d_offsets, a.d_logit = d_logits;
     a.grad_value = nullptr;          // never dereferenced: nothing scatters in this mode
     a.taps_only = true;
@@ -568,20 +620,23 @@ int msda_fused_grad_taps(const void *value, int value_dtype, const int64_t *shap
 
 namespace {
 
-// The C entry points below with and without ref_batch are calls of these two.
+// The C entry points below with and without ref_batch / ref_comps are calls of these two (the forward; the atomic backward,
+// which has no box form).  ref_comps: 2 = points, 4 = boxes (16-byte aligned).
 int fused_forward_impl(const char *fn, const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
                        const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
-                       int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch, int64_t N, int64_t S,
-                       int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, void *out, void *stream) {
+                       int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch, int64_t ref_comps,
+                       int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, void *out, void *stream) {
     clear_error();
+    if (int rc = msda_check_ref_comps(fn, ref_comps)) return rc;
     if (int rc = check_common(fn, N, S, M, D, L, Lq, P, ref_levels, ref_batch)) return rc;
     if (N * Lq * M == 0) return VAH_OK;
     if (!value || !shapes || !lsi || !offsets || !logits || !ref || !out) return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (int rc = msda_check_dtypes(fn, value_dtype, param_dtype, true)) return rc;
     if (((uintptr_t)value | (uintptr_t)out | (uintptr_t)offsets | (uintptr_t)ref) % 8) return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    if (ref_comps == 4 && (uintptr_t)ref % 16) return fail(VAH_E_ALIGN, "%s: misaligned (reference boxes are read 16 bytes at a time)", fn);
     FusedArgs a{};
     a.value = value, a.off = offsets, a.logit = logits, a.shapes = shapes, a.lsi = lsi, a.ref = ref;
-    a.ref_levels = (int)ref_levels, a.rq = msda_ref_rows_per_image(ref_batch, N, Lq);
+    a.ref_levels = (int)ref_levels, a.rq = msda_ref_rows_per_image(ref_batch, N, Lq), a.box = ref_comps == 4;
     a.N = N, a.S = S, a.M = M, a.D = D, a.L = L, a.Lq = Lq, a.P = P, a.out = out;
     a.os = offsets_stride, a.ls = logits_stride;
     if (offsets_stride < 0 || logits_stride < 0 || ((offsets_stride * msda_dtype_bytes(param_dtype)) % 8))
@@ -641,7 +696,7 @@ int vah_msda_fused_forward(const void *value, int value_dtype, const int64_t *sh
                            int64_t ref_levels, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L,
                            int64_t Lq, int64_t P, void *out, void *stream) {
     return vah::fused_forward_impl("vah_msda_fused_forward", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
-                                   offsets_stride, logits_stride, ref, ref_levels, 1, N, S, M, D, L, Lq, P, out, stream);
+                                   offsets_stride, logits_stride, ref, ref_levels, 1, 2, N, S, M, D, L, Lq, P, out, stream);
 }
 
 int vah_msda_fused_forward_nref(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
@@ -650,7 +705,17 @@ int vah_msda_fused_forward_nref(const void *value, int value_dtype, const int64_
                                 int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, void *out,
                                 void *stream) {
     return vah::fused_forward_impl("vah_msda_fused_forward_nref", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
-                                   offsets_stride, logits_stride, ref, ref_levels, ref_batch, N, S, M, D, L, Lq, P, out, stream);
+                                   offsets_stride, logits_stride, ref, ref_levels, ref_batch, 2, N, S, M, D, L, Lq, P, out, stream);
+}
+
+int vah_msda_fused_forward_box(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                               const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
+                               int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch,
+                               int64_t ref_comps, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
+                               void *out, void *stream) {
+    return vah::fused_forward_impl("vah_msda_fused_forward_box", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
+                                   offsets_stride, logits_stride, ref, ref_levels, ref_batch, ref_comps, N, S, M, D, L, Lq, P, out,
+                                   stream);
 }
 
 int vah_msda_fused_backward(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,

@@ -335,6 +335,7 @@ __device__ __forceinline__ void write_item(const PlanDev &g, const Bounds &bd, I
 // Plain: sampling_locations (N,Lq,M,L,P,2) and attention_weights (N,Lq,M,L,P), fp32 (the reference API).
 struct PlainSrc {
     static constexpr int kLevels = 0;       // run-time
+    static constexpr bool kBox = false;     // locations come as they are
     const float *loc, *attn;
     int LP;
     float *grad_loc, *grad_attn;           // outputs of the tile pass (spec cuh:156-158)
@@ -387,7 +388,10 @@ struct PlainSrc {
 // gradients under autocast also when their outputs are kept in fp32).  fp16: PT = GPT = _Float16 only; its rows need
 // 8-byte, not 16-byte, alignment (an fp16 [offsets | logits | gap] matrix has rows of 3 L P + 8 halves).
 // HSH: 1 when a head is two half-head rows (D == 64): `row` counts half-heads, parameters are read at row >> 1.
-template <typename PT, typename GPT, int L, int HSH>
+// BOX: ref holds boxes (cx, cy, w, h), loc = c + off / P * (w, h) * 0.5 (msda_common.h::box_loc), and the owner tile
+// scales a sample's pixel-space gradient to d(offset) (grad_scale) in fp32, before pack() rounds the record.  A
+// compile-time switch: the tile pass is bound by registers and instruction issue, and the point form is the code it was.
+template <typename PT, typename GPT, int L, int HSH, bool BOX>
 struct FusedSrc {
     const PT *off, *logit;
     const float *ref;
@@ -395,6 +399,7 @@ struct FusedSrc {
     int rq;                                // rows of ref between consecutive images: Lq (one grid per image) or 0 (shared)
     int os, ls;                            // elements between the offsets / logits of consecutive (n, q, m) rows
     static constexpr int kLevels = L;
+    static constexpr bool kBox = BOX;
     static constexpr int LP = L * kP;
     static constexpr int OW = kP * 2 * (int)sizeof(PT) / 4;      // words of one level's offsets (4 or 8)
     static constexpr int LW = LP * (int)sizeof(PT) / 4;          // words of the row's logits (even)
@@ -443,7 +448,7 @@ struct FusedSrc {
     struct Raw {
         uint32_t o[OW];
         uint32_t lg[LW];
-        float2 rp;
+        typename RefRaw<BOX>::type rp;
     };
     // row of ref that query q of image n reads (n is uniform over a workgroup of either pass)
     __device__ __forceinline__ int ref_row(int n, int q) const { return n * rq + q; }
@@ -462,7 +467,8 @@ struct FusedSrc {
                 r.o[4 * i] = v.x, r.o[4 * i + 1] = v.y, r.o[4 * i + 2] = v.z, r.o[4 * i + 3] = v.w;
             }
         }
-        r.rp = *reinterpret_cast<const float2 *>(ref + (rr * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
+        if constexpr (BOX) r.rp = *reinterpret_cast<const float4 *>(ref + (rr * ref_levels + (ref_levels > 1 ? l : 0)) * 4);
+        else r.rp = *reinterpret_cast<const float2 *>(ref + (rr * ref_levels + (ref_levels > 1 ? l : 0)) * 2);
         const uint2 *lp = reinterpret_cast<const uint2 *>(logit + (row >> HSH) * ls);              // 8-byte aligned
 #pragma unroll
         for (int i = 0; i < LW / 2; ++i) {
@@ -486,8 +492,17 @@ struct FusedSrc {
     }
     __device__ __forceinline__ float2 xy(const Raw &r, int p, const LevelConst &c) const {
         const float ox = word_elem<PT>(r.o, 2 * p), oy = word_elem<PT>(r.o, 2 * p + 1);
-        if (c.pow2) return make_float2(r.rp.x + ox * c.rW, r.rp.y + oy * c.rH);
-        return make_float2(r.rp.x + ox / c.Wf, r.rp.y + oy / c.Hf);
+        if constexpr (BOX) {
+            return box_loc<kP>(r.rp, ox, oy);
+        } else {
+            if (c.pow2) return make_float2(r.rp.x + ox * c.rW, r.rp.y + oy * c.rH);
+            return make_float2(r.rp.x + ox / c.Wf, r.rp.y + oy / c.Hf);
+        }
+    }
+    // BOX: d(offset) / d(pixel coordinate) of the samples of r's (row, level): (W, H) * (w, h) * 0.5 / P
+    __device__ __forceinline__ float2 grad_scale(const Raw &r, int H, int W) const {
+        if constexpr (BOX) return box_grad_scale<kP>(r.rp, H, W);
+        else return make_float2(1.f, 1.f);
     }
     __device__ __forceinline__ void weights(const Raw &r, int l, float (&a)[kP]) const {
         float pr[LP];
@@ -931,6 +946,11 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                     lh[p] = b.lh, lw[p] = b.lw;
                     on[p] = live && b.inside;
                 }
+                // reference boxes: the factor from the pixel-space gradient to d(offset), kept from the decode (the raw
+                // words are the next chunk's by the time the gradients are stored).  Parking it in LDS through the dot
+                // products changed no instantiation's registers or scratch.
+                float2 gsc = make_float2(1.f, 1.f);
+                if constexpr (TAPS && Src::kBox) gsc = src.grad_scale(raw, cur.H, cur.W);
                 const int row_c = row;
                 auto issue_next = [&]() __attribute__((always_inline)) {
                     const int idx2 = min((ch + 2 * STEP) * 64 + lane, last_i);
@@ -1001,6 +1021,10 @@ __global__ __launch_bounds__(64, WPS) void msda_tile(Src src, const PlanDev *__r
                         const int fy = y0 >= 0 ? ry[p] : ry[p] + 1, fx = x0 >= 0 ? rx[p] : rx[p] + 1;
                         const bool owned = on[p] && (unsigned)fy < (unsigned)kTH && (unsigned)fx < (unsigned)kTW;
                         own |= owned ? 1u << p : 0u;
+                    }
+                    if constexpr (Src::kBox) {          // in fp32, ahead of the one rounding in pack()
+#pragma unroll
+                        for (int p = 0; p < kP; ++p) gx_[p] *= gsc.x, gy_[p] *= gsc.y;
                     }
                     if (!(ablate & 16) && own) src.store_grads(row_c, cur.l, own, gx_, gy_, gav, cur.H, cur.W);
                     }
@@ -1295,14 +1319,14 @@ template <typename VT>
 constexpr bool kTapsInTile = std::is_same<VT, __bf16>::value || std::is_same<VT, _Float16>::value;
 
 // M: heads; the passes run on M << HSH half-heads (bd is sized for them)
-template <typename VT, typename PT, typename GPT, int L, int HSH>
+template <typename VT, typename PT, typename GPT, int L, int HSH, bool BOX>
 int fused_tiled(const char *fn, const Bounds &bd, const void *value, const int64_t *shapes, const int64_t *lsi, const void *off,
                 const void *logit, int64_t os, int64_t ls, const float *ref, int ref_levels, int rq, int64_t N, int64_t M, int64_t Lq, int64_t S,
                 const void *grad_out, void *grad_value, int gv_16, void *d_off, void *d_logit, int64_t dos, int64_t dls, void *ws,
                 hipStream_t st) {
     constexpr bool TAPS = kTapsInTile<VT>;
     uint32_t *rec = (uint32_t *)((char *)ws + bd.off_ga);
-    typedef FusedSrc<PT, GPT, L, HSH> Src;
+    typedef FusedSrc<PT, GPT, L, HSH, BOX> Src;
     const int64_t Mh = M << HSH;
     Src src{(const PT *)off, (const PT *)logit, ref, ref_levels, rq, (int)os, (int)ls, rec};
     int rc;
@@ -1328,11 +1352,12 @@ int fused_tiled(const char *fn, const Bounds &bd, const void *value, const int64
 
 int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
                               const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
-                              int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch, const void *grad_out,
-                              int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P, void *grad_value,
-                              int grad_value_dtype, void *d_offsets, void *d_logits, int grad_param_dtype,
+                              int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch, int64_t ref_comps,
+                              const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
+                              void *grad_value, int grad_value_dtype, void *d_offsets, void *d_logits, int grad_param_dtype,
                               int64_t d_offsets_stride, int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
     clear_error();
+    if (int rc = msda_check_ref_comps(fn, ref_comps)) return rc;
     if (N < 0 || S < 1 || M < 1 || Lq < 0 || M * D >= (1LL << 31)) return fail(VAH_E_SHAPE, "%s: bad dims", fn);
     if (D != kD && D != 2 * kD) return fail(VAH_E_UNSUPPORTED, "%s: needs D == 32 or D == 64", fn);
     if (ref_levels != 1 && ref_levels != L) return fail(VAH_E_SHAPE, "%s: ref_levels must be 1 or L", fn);
@@ -1343,6 +1368,7 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
         return fail(VAH_E_NULL, "%s: null pointer", fn);
     if (((uintptr_t)grad_out | (uintptr_t)grad_value | (uintptr_t)ws | (uintptr_t)offsets) % 16 || ((uintptr_t)d_offsets | (uintptr_t)ref) % 8)
         return fail(VAH_E_ALIGN, "%s: misaligned", fn);
+    if (ref_comps == 4 && (uintptr_t)ref % 16) return fail(VAH_E_ALIGN, "%s: misaligned (reference boxes are read 16 bytes at a time)", fn);
     if (int rc = msda_check_dtypes(fn, value_dtype, param_dtype, true)) return rc;
     const bool f16 = value_dtype == 2;
     if (f16 ? (grad_value_dtype != 2 || grad_param_dtype != 2) : ((grad_value_dtype | grad_param_dtype) & ~1) != 0)
@@ -1357,8 +1383,8 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
     if (os < L * P * 2 || ls < L * P || dos < L * P * 2 || dls < L * P || (os * ps) % (f16 ? 8 : 16) || (ls * ps) % 8 || (dos * gps) % (gps == 4 ? 16 : 8) ||
         ((uintptr_t)logits) % 8 || (dls * gps) % gps || N * Lq * M * (os > ls ? os : ls) >= ((int64_t)1 << 31))
         return fail(VAH_E_ALIGN, "%s: bad strides", fn);
-    // the passes index ref in int: N * Lq * ref_levels * 2 <= N * Lq * 2 * L < N * Lq * M * os < 2^31 by the check above
-    // (os >= 2 * L * P)
+    // the passes index ref in int: N * Lq * ref_levels * ref_comps <= N * Lq * 4 * L < N * Lq * M * os < 2^31 by the check
+    // above (os >= 2 * L * P = 8 L)
     const int64_t rq = msda_ref_rows_per_image(ref_batch, N, Lq);
     // everything in the workspace is per 32-channel head slice: M * (D / 32) of them (what vah_msda_tile_ws_bytes is asked with)
     Bounds bd;
@@ -1372,16 +1398,18 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
     if (value_dtype == 0) {
         if (grad_param_dtype != param_dtype || strided)
             return fail(VAH_E_UNSUPPORTED, "%s: fp32 values write gradients in the parameter dtype, contiguous tensors only", fn);
-        if (int rc = msda_fused_grad_taps(value, value_dtype, shapes, lsi, offsets, logits, param_dtype, ref, ref_levels, rq, grad_out,
-                                          N, S, M, D, L, Lq, P, d_offsets, d_logits, st))
+        if (int rc = msda_fused_grad_taps(value, value_dtype, shapes, lsi, offsets, logits, param_dtype, ref, ref_levels, rq, ref_comps,
+                                          grad_out, N, S, M, D, L, Lq, P, d_offsets, d_logits, st))
             return rc;
     }
+    const bool box = ref_comps == 4;
+#define VAH_TILED(VT, PT, GPT, LL, HSH, BOX)                                                                                                  \
+    fused_tiled<VT, PT, GPT, LL, HSH, BOX>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, (int)rq, N, M, Lq, S, \
+                                           grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)
 #define VAH_CASE(VT, VC, PT, PC, GPT, GC, LL)                                                                              \
     if (value_dtype == VC && param_dtype == PC && grad_param_dtype == GC && L == LL)                                      \
-        return D == kD ? fused_tiled<VT, PT, GPT, LL, 0>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, (int)rq, N, M, Lq, S, \
-                                                         grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)                 \
-                       : fused_tiled<VT, PT, GPT, LL, 1>(fn, bd, value, shapes, lsi, offsets, logits, os, ls, ref, (int)ref_levels, (int)rq, N, M, Lq, S, \
-                                                         grad_out, grad_value, grad_value_dtype, d_offsets, d_logits, dos, dls, ws, st)
+        return D == kD ? (box ? VAH_TILED(VT, PT, GPT, LL, 0, true) : VAH_TILED(VT, PT, GPT, LL, 0, false))               \
+                       : (box ? VAH_TILED(VT, PT, GPT, LL, 1, true) : VAH_TILED(VT, PT, GPT, LL, 1, false))
 #define VAH_CASES(LL)                                  \
     VAH_CASE(float, 0, float, 0, float, 0, LL);        \
     VAH_CASE(__bf16, 1, __bf16, 1, __bf16, 1, LL);     \
@@ -1394,6 +1422,7 @@ int fused_backward_tiled_impl(const char *fn, const void *value, int value_dtype
     VAH_CASES(4);
 #undef VAH_CASES
 #undef VAH_CASE
+#undef VAH_TILED
     return fail(VAH_E_UNSUPPORTED, "%s: L = %lld not instantiated", fn, (long long)L);
 }
 
@@ -1444,7 +1473,7 @@ int vah_msda_fused_backward_tiled(const void *value, int value_dtype, const int6
                                   void *d_offsets, void *d_logits, int grad_param_dtype, int64_t d_offsets_stride,
                                   int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
     return vah::fused_backward_tiled_impl("vah_msda_fused_backward_tiled", value, value_dtype, shapes, lsi, offsets, logits, param_dtype,
-                                          offsets_stride, logits_stride, ref, ref_levels, 1, grad_out, N, S, M, D, L, Lq, P,
+                                          offsets_stride, logits_stride, ref, ref_levels, 1, 2, grad_out, N, S, M, D, L, Lq, P,
                                           grad_value, grad_value_dtype, d_offsets, d_logits, grad_param_dtype, d_offsets_stride,
                                           d_logits_stride, ws, ws_bytes, stream);
 }
@@ -1457,9 +1486,22 @@ int vah_msda_fused_backward_tiled_nref(const void *value, int value_dtype, const
                                        void *d_logits, int grad_param_dtype, int64_t d_offsets_stride,
                                        int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
     return vah::fused_backward_tiled_impl("vah_msda_fused_backward_tiled_nref", value, value_dtype, shapes, lsi, offsets, logits,
-                                          param_dtype, offsets_stride, logits_stride, ref, ref_levels, ref_batch, grad_out, N, S, M,
+                                          param_dtype, offsets_stride, logits_stride, ref, ref_levels, ref_batch, 2, grad_out, N, S, M,
                                           D, L, Lq, P, grad_value, grad_value_dtype, d_offsets, d_logits, grad_param_dtype,
                                           d_offsets_stride, d_logits_stride, ws, ws_bytes, stream);
+}
+
+int vah_msda_fused_backward_tiled_box(const void *value, int value_dtype, const int64_t *shapes, const int64_t *lsi,
+                                      const void *offsets, const void *logits, int param_dtype, int64_t offsets_stride,
+                                      int64_t logits_stride, const float *ref, int64_t ref_levels, int64_t ref_batch,
+                                      int64_t ref_comps, const void *grad_out, int64_t N, int64_t S, int64_t M, int64_t D,
+                                      int64_t L, int64_t Lq, int64_t P, void *grad_value, int grad_value_dtype, void *d_offsets,
+                                      void *d_logits, int grad_param_dtype, int64_t d_offsets_stride,
+                                      int64_t d_logits_stride, void *ws, int64_t ws_bytes, void *stream) {
+    return vah::fused_backward_tiled_impl("vah_msda_fused_backward_tiled_box", value, value_dtype, shapes, lsi, offsets, logits,
+                                          param_dtype, offsets_stride, logits_stride, ref, ref_levels, ref_batch, ref_comps, grad_out,
+                                          N, S, M, D, L, Lq, P, grad_value, grad_value_dtype, d_offsets, d_logits,
+                                          grad_param_dtype, d_offsets_stride, d_logits_stride, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

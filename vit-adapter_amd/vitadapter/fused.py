@@ -863,7 +863,7 @@ class _MSDAPairCore(torch.autograd.Function):
         offsets = yv[..., :2 * L * P].unflatten(-1, (L, P, 2))
         logits = yv[..., 2 * L * P:]
         value = value.contiguous()
-        refc = ref.detach().float().contiguous().view(ref.shape[0], Lq, -1, 2)
+        refc = ref.detach().float().contiguous().view(ref.shape[0], Lq, -1, ref.shape[-1])          # points, or boxes (cx, cy, w, h)
         # the window-forward schedule rides on a grid the batch shares; one grid per image has no such schedule
         out = mf.fused_forward(value, shapes, lsi, offsets, logits, PS, PS, refc, carrier=ref if refc.shape[0] == 1 else None,
                                token=BF16_COPIES.epoch)
@@ -885,12 +885,14 @@ class _MSDAPairCore(torch.autograd.Function):
         grad_value = torch.empty_like(value)
         ws_bytes = _vah.lib.vah_msda_tile_ws_bytes(N, S, M * (D // 32), L, Lq, P)      # per 32-channel head slice
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device)
+        from ops.functions.ms_deform_attn_fused import box_entry
+        name, comps = box_entry('vah_msda_fused_backward_tiled', refc.shape[3])          # boxes: the *_box entry point
         with _vah.on(value.device):
-            rc = _vah.lib.vah_msda_fused_backward_tiled_nref(
+            rc = getattr(_vah.lib, name)(
                 value.data_ptr(), 1, shapes.data_ptr(), lsi.data_ptr(), y.data_ptr(), y.data_ptr() + 2 * L * P * 4, 0, PS, PS,
-                refc.data_ptr(), refc.shape[2], refc.shape[0], gout.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(), 1,
+                refc.data_ptr(), refc.shape[2], refc.shape[0], *comps, gout.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(), 1,
                 g.data_ptr(), g.data_ptr() + 2 * L * P * 2, 1, PS, PS, ws.data_ptr(), ws_bytes, _stream(value))
-        _vah.check(rc, 'vah_msda_fused_backward_tiled_nref')
+        _vah.check(rc, name)
         gx = gw = gbias = None
         if ctx.needs_input_grad[0]:
             gx = gemm_16(g, w).view(ctx.in_shape)
@@ -907,7 +909,8 @@ class _MSDAPairCore(torch.autograd.Function):
 def msda_pair_core_ok(mod, query, value, reference_points):
     """The one-node form of MSDeformAttn's offsets / weights pair + core: bf16 autocast on the GPU with bf16 values, the
     tile-pass backward and shapes the fused kernels cover (D in {32, 64}, P == 4, L in {1, 3, 4}), reference points shared by
-    the batch or one grid per image (not learned ones: ops.functions.ms_deform_attn_fused.ref_points_ok)."""
+    the batch or one grid per image (not learned ones: ops.functions.ms_deform_attn_fused.ref_points_ok), points or boxes
+    (cx, cy, w, h): the tile pass, which every call here needs, is also all that serves boxes."""
     import os
     from ops.functions.ms_deform_attn_fused import ref_points_ok
     a, b = mod.sampling_offsets, mod.attention_weights

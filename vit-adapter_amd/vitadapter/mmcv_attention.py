@@ -9,8 +9,9 @@ through mmcv's BaseTransformerLayer with ``query`` (Lq, N, E), ``query_pos``, ``
 ``reference_points`` (N, Lq, L, 2), ``spatial_shapes``, ``level_start_index``
 (msdeformattn_pixel_decoder.py:230-242); ``init_weights()`` is called explicitly (:154-158).  Those reference points are
 one grid per image (the pixel centres times each image's valid ratios, :224-240): with 32-channel heads the fused kernels
-take them as they are, at any batch size; 4-component points, and per-image points that require grad, keep the unfused
-sequence (ops/functions/ms_deform_attn_fused.py::ref_points_ok).
+take them as they are, at any batch size, and so they take the 4-component boxes (cx, cy, w, h) of the decoders that
+refine boxes layer by layer (mmseg_custom/models/utils/transformer.py:595-615); per-image points or boxes that require
+grad keep the unfused sequence (ops/functions/ms_deform_attn_fused.py::ref_points_ok).
 
 The class itself lives in mmcv (``mmcv.ops.multi_scale_deform_attn``), which is not part of the
 reference tree: its behaviour is restated here from the call sites above and mmcv 1.4's published
