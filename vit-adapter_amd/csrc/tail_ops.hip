@@ -23,6 +23,8 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 #include "../../include/vitadapter_hip.h"
 #include "common.h"
@@ -43,6 +45,7 @@ struct Operands {
     int relu, y_bf16, dy_bf16;          // ReLU fused behind the normalisation; dtypes of y and dy
     const float *shift;                 // optional per-channel constant added to the sum (conv biases)
     unsigned quad_magic;                // floor(2^32 / (W / 4)) + 1: item -> (row, quad) by one v_mul_hi (items < 2^16)
+    unsigned oct_magic, lo_magic;       // the same for W / 8 (8-pixel items) and for Wl (the adjoint's passes): fixed forms
 };
 
 struct Tap {
@@ -414,6 +417,357 @@ __global__ __launch_bounds__(256) void tail_bwd_apply_kernel(Operands o, const f
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Fixed forms.  The kernels above are the general form: every operand dtype, scale, b, shift, ReLU and output dtype is a
+// run-time (wave-uniform) choice inside the per-quad body, which is what bounds them (VALU, not HBM).  The backbone
+// runs three forms only -
+//     norm1: 16-bit a + fp32 x at scale 4 + shift;   norm2: fp32 a + fp32 x at scale 2;   norm3: fp32 a + fp32 x, scale 1
+// all without b, without ReLU and with fp32 y / dy - and for those the choices are template parameters <A16, S, SHIFT>.
+// In stats, bwd_stats and bwd_apply an item is 8 consecutive pixels (W % 8 == 0): 16-bit operands arrive as one 16-byte
+// load, fp32 operands as two, and the 8 pixels share the low-res columns of one row pair (4 columns at scale 4, 6 at
+// scale 2); apply keeps quads (see sum4_form).  Arithmetic per element is the general form's, expression for expression:
+// given the same mean / rstd / mdy / mdyx, y, da and dxlo carry the same bits; the channel sums associate differently
+// (another thread sums the quad).  VAH_TAIL_FORM=general (read per call) routes every call to the kernels above.
+// ---------------------------------------------------------------------------------------------------------------
+template <bool A16>
+__device__ __forceinline__ void load8(const void *p, int64_t idx, uint4 &lo, uint4 &hi) {
+    if constexpr (A16) {
+        lo = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(p) + idx);
+        hi = lo;
+    } else {
+        lo = *reinterpret_cast<const uint4 *>(reinterpret_cast<const float *>(p) + idx);
+        hi = *reinterpret_cast<const uint4 *>(reinterpret_cast<const float *>(p) + idx + 4);
+    }
+}
+
+template <typename T, bool A16>
+__device__ __forceinline__ void decode8(const uint4 &lo, const uint4 &hi, float (&v)[8]) {
+    if constexpr (A16) {
+        const float4 f0 = widen4<T>(lo.x, lo.y), f1 = widen4<T>(lo.z, lo.w);
+        v[0] = f0.x, v[1] = f0.y, v[2] = f0.z, v[3] = f0.w;
+        v[4] = f1.x, v[5] = f1.y, v[6] = f1.z, v[7] = f1.w;
+    } else {
+        v[0] = __uint_as_float(lo.x), v[1] = __uint_as_float(lo.y), v[2] = __uint_as_float(lo.z), v[3] = __uint_as_float(lo.w);
+        v[4] = __uint_as_float(hi.x), v[5] = __uint_as_float(hi.y), v[6] = __uint_as_float(hi.z), v[7] = __uint_as_float(hi.w);
+    }
+}
+
+// one pixel of the upsample: the column lerp on the two low-res rows, then the row lerp (sum4's expressions)
+__device__ __forceinline__ float lerp2(float p0, float p1, float q0, float q1, float wx, float wy) {
+    const float top = p0 + wx * (p1 - p0), bot = q0 + wx * (q1 - q0);
+    return top + wy * (bot - top);
+}
+
+// t[0..7] = a + (shift + 0) + up(x) for 8 consecutive pixels (row y, columns x8 .. x8 + 7, x8 % 8 == 0) of `plane`;
+// DY: g[0..7] = the fp32 dy of the same pixels.  `add` = shift[c] + 0.f (the general form's `sft + vb`, b absent).
+// All loads are requested before the first is decoded.
+template <typename T, bool A16, int S, bool DY>
+__device__ __forceinline__ void sum8(const Operands &o, int64_t plane, int y, int x8, float add, const float *dy, float (&t)[8],
+                                     float (&g)[8]) {
+    const int64_t idx = (plane * o.H + y) * o.W + x8;
+    uint4 alo, ahi, glo, ghi;
+    load8<A16>(o.a, idx, alo, ahi);
+    if constexpr (DY) load8<false>(dy, idx, glo, ghi);
+    const float *xp = o.x + plane * o.Hl * o.Wl;
+    constexpr int NC = S == 4 ? 4 : 6;                       // low-res columns under 8 pixels (scale 2: 6, scale 4: 4)
+    float c0[NC], c1[NC];
+    float4 xs0, xs1;
+    float wy = 0.f;
+    if constexpr (S == 1) {
+        xs0 = *reinterpret_cast<const float4 *>(xp + (int64_t)y * o.Wl + x8);
+        xs1 = *reinterpret_cast<const float4 *>(xp + (int64_t)y * o.Wl + x8 + 4);
+    } else {
+        const Tap ty = tap_of(y, o.Hl, S);
+        wy = ty.w1;
+        const float *r0 = xp + (int64_t)ty.i0 * o.Wl, *r1 = xp + (int64_t)ty.i1 * o.Wl;
+        // columns bc .. bc + NC - 1, bc = floor of the first pixel's source position (>= -1); the inner ones start at
+        // a multiple of NC - 2 floats, the two outer ones are clamped as the general form clamps them
+        const int bc = x8 / S - 1;
+        const int cl = max(bc, 0), cr = min(bc + NC - 1, o.Wl - 1);
+        c0[0] = r0[cl];
+        c1[0] = r1[cl];
+        c0[NC - 1] = r0[cr];
+        c1[NC - 1] = r1[cr];
+        if constexpr (S == 4) {
+            const float2 m0 = *reinterpret_cast<const float2 *>(r0 + bc + 1), m1 = *reinterpret_cast<const float2 *>(r1 + bc + 1);
+            c0[1] = m0.x, c0[2] = m0.y;
+            c1[1] = m1.x, c1[2] = m1.y;
+        } else {
+            const float4 m0 = *reinterpret_cast<const float4 *>(r0 + bc + 1), m1 = *reinterpret_cast<const float4 *>(r1 + bc + 1);
+            c0[1] = m0.x, c0[2] = m0.y, c0[3] = m0.z, c0[4] = m0.w;
+            c1[1] = m1.x, c1[2] = m1.y, c1[3] = m1.z, c1[4] = m1.w;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);                       // loads above, arithmetic below
+    decode8<T, A16>(alo, ahi, t);
+    if constexpr (DY) decode8<T, false>(glo, ghi, g);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t[k] += add;
+    if constexpr (S == 1) {
+        t[0] += xs0.x, t[1] += xs0.y, t[2] += xs0.z, t[3] += xs0.w;
+        t[4] += xs1.x, t[5] += xs1.y, t[6] += xs1.z, t[7] += xs1.w;
+    } else if constexpr (S == 4) {                           // pixel k: columns (k + 2) / 4 and the next; 5/8, 7/8, 1/8, 3/8
+        constexpr float w[4] = {0.625f, 0.875f, 0.125f, 0.375f};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int j = (k + 2) >> 2;
+            t[k] += lerp2(c0[j], c0[j + 1], c1[j], c1[j + 1], w[k & 3], wy);
+        }
+    } else {                                                 // pixel k: columns (k + 1) / 2 and the next; 3/4, 1/4
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int j = (k + 1) >> 1;
+            t[k] += lerp2(c0[j], c0[j + 1], c1[j], c1[j + 1], (k & 1) ? 0.25f : 0.75f, wy);
+        }
+    }
+}
+
+// item -> (row, first column) of an 8-pixel item; o.oct_magic as o.quad_magic, for W / 8
+__device__ __forceinline__ void item8(const Operands &o, int i, int wv8, int r0, int &y, int &x8) {
+    const int iy = wv8 == 1 ? i : (int)__umulhi((unsigned)i, o.oct_magic);
+    y = r0 + iy;
+    x8 = (i - iy * wv8) * 8;
+}
+
+template <typename T, bool A16, int S, bool SHIFT>
+__global__ __launch_bounds__(256) void tail_stats_form_kernel(Operands o, float *__restrict__ part) {
+    __shared__ float s_red[4];
+    const int64_t plane = blockIdx.x / o.chunks;
+    const int chunk = blockIdx.x % o.chunks;
+    const int c = (int)(plane % o.C);
+    const int64_t n = plane / o.C;
+    const int r0 = chunk * o.rows_per_block, r1 = min(o.H, r0 + o.rows_per_block);
+    const int wv8 = o.W >> 3;
+    const float add = (SHIFT ? o.shift[c] : 0.f) + 0.f;
+    float s1 = 0.f, s2 = 0.f;
+    for (int i = threadIdx.x; i < (r1 - r0) * wv8; i += 256) {
+        int y, x8;
+        item8(o, i, wv8, r0, y, x8);
+        float t[8], g[8];
+        sum8<T, A16, S, false>(o, plane, y, x8, add, nullptr, t, g);
+        s1 += (t[0] + t[1]) + (t[2] + t[3]);
+        s2 += (t[0] * t[0] + t[1] * t[1]) + (t[2] * t[2] + t[3] * t[3]);
+        s1 += (t[4] + t[5]) + (t[6] + t[7]);
+        s2 += (t[4] * t[4] + t[5] * t[5]) + (t[6] * t[6] + t[7] * t[7]);
+    }
+    s1 = block_sum(s1, s_red);
+    s2 = block_sum(s2, s_red);
+    if (threadIdx.x == 0) {
+        float *row = part + (n * o.chunks + chunk) * 2 * o.C;
+        row[c] = s1;
+        row[o.C + c] = s2;
+    }
+}
+
+// The same sum for one quad (row y, columns x4 .. x4 + 3): sum4 with its run-time choices resolved.  The normalise pass
+// keeps quad items: it is the one pass that streams a full-size fp32 output, and with 8-pixel items a wave's store
+// instruction covers every second 16 bytes of 2 KB (measured at stride 4: 130 us against the general form's 111 us),
+// with quads it covers 1 KB of whole lines.
+template <typename T, bool A16, int S>
+__device__ __forceinline__ float4 sum4_form(const Operands &o, int64_t plane, int y, int x4, float add) {
+    const int64_t idx = (plane * o.H + y) * o.W + x4;
+    uint2 a2 = make_uint2(0u, 0u);
+    uint4 a4 = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (A16) a2 = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(o.a) + idx);
+    else a4 = *reinterpret_cast<const uint4 *>(reinterpret_cast<const float *>(o.a) + idx);
+    const float *xp = o.x + plane * o.Hl * o.Wl;
+    constexpr int NC = S == 4 ? 3 : 4;                       // low-res columns under 4 pixels
+    float c0[NC], c1[NC];
+    float4 xs = make_float4(0.f, 0.f, 0.f, 0.f);
+    float wy = 0.f;
+    if constexpr (S == 1) {
+        xs = *reinterpret_cast<const float4 *>(xp + (int64_t)y * o.Wl + x4);
+    } else {
+        const Tap ty = tap_of(y, o.Hl, S);
+        wy = ty.w1;
+        const float *r0 = xp + (int64_t)ty.i0 * o.Wl, *r1 = xp + (int64_t)ty.i1 * o.Wl;
+        const int bc = x4 / S - 1;                           // floor((2 x4 + 1 - S) / 2S), x4 % 4 == 0
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const int cj = min(max(bc + j, 0), o.Wl - 1);
+            c0[j] = r0[cj];
+            c1[j] = r1[cj];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);                       // loads above, arithmetic below
+    float4 t;
+    if constexpr (A16) t = widen4<T>(a2.x, a2.y);
+    else t = make_float4(__uint_as_float(a4.x), __uint_as_float(a4.y), __uint_as_float(a4.z), __uint_as_float(a4.w));
+    t.x += add;
+    t.y += add;
+    t.z += add;
+    t.w += add;
+    if constexpr (S == 1) {
+        t.x += xs.x;
+        t.y += xs.y;
+        t.z += xs.z;
+        t.w += xs.w;
+    } else if constexpr (S == 4) {                           // columns b, b, b + 1, b + 1; weights 5/8, 7/8, 1/8, 3/8
+        t.x += lerp2(c0[0], c0[1], c1[0], c1[1], 0.625f, wy);
+        t.y += lerp2(c0[0], c0[1], c1[0], c1[1], 0.875f, wy);
+        t.z += lerp2(c0[1], c0[2], c1[1], c1[2], 0.125f, wy);
+        t.w += lerp2(c0[1], c0[2], c1[1], c1[2], 0.375f, wy);
+    } else {                                                 // columns b, b + 1, b + 1, b + 2; weights 3/4, 1/4, 3/4, 1/4
+        t.x += lerp2(c0[0], c0[1], c1[0], c1[1], 0.75f, wy);
+        t.y += lerp2(c0[1], c0[2], c1[1], c1[2], 0.25f, wy);
+        t.z += lerp2(c0[1], c0[2], c1[1], c1[2], 0.75f, wy);
+        t.w += lerp2(c0[2], c0[3], c1[2], c1[3], 0.25f, wy);
+    }
+    return t;
+}
+
+template <typename T, bool A16, int S, bool SHIFT>
+__global__ __launch_bounds__(256) void tail_apply_form_kernel(Operands o, const float *__restrict__ mean,
+                                                              const float *__restrict__ rstd,
+                                                              const float *__restrict__ gamma,
+                                                              const float *__restrict__ beta, float *__restrict__ y) {
+    const int64_t plane = blockIdx.x / o.chunks;
+    const int chunk = blockIdx.x % o.chunks;
+    const int c = (int)(plane % o.C);
+    const int r0 = chunk * o.rows_per_block, r1 = min(o.H, r0 + o.rows_per_block);
+    const int wv4 = o.W >> 2;                                // >= 2: W % 8 == 0
+    const float add = (SHIFT ? o.shift[c] : 0.f) + 0.f;
+    const float sc = rstd[c] * (gamma ? gamma[c] : 1.f);
+    const float sh = (beta ? beta[c] : 0.f) - mean[c] * sc;
+    for (int i = threadIdx.x; i < (r1 - r0) * wv4; i += 256) {
+        const int iy = (int)__umulhi((unsigned)i, o.quad_magic), yy = r0 + iy, x4 = (i - iy * wv4) * 4;
+        const float4 t = sum4_form<T, A16, S>(o, plane, yy, x4, add);
+        // no ReLU: the general form's nanmax(v, -inf) is v
+        *reinterpret_cast<float4 *>(y + (plane * o.H + yy) * o.W + x4) =
+            make_float4(t.x * sc + sh, t.y * sc + sh, t.z * sc + sh, t.w * sc + sh);
+    }
+}
+
+template <typename T, bool A16, int S, bool SHIFT>
+__global__ __launch_bounds__(256) void tail_bwd_stats_form_kernel(Operands o, const float *__restrict__ mean,
+                                                                  const float *__restrict__ rstd,
+                                                                  const float *__restrict__ dy, float *__restrict__ part) {
+    __shared__ float s_red[4];
+    const int64_t plane = blockIdx.x / o.chunks;
+    const int chunk = blockIdx.x % o.chunks;
+    const int c = (int)(plane % o.C);
+    const int64_t n = plane / o.C;
+    const int r0 = chunk * o.rows_per_block, r1 = min(o.H, r0 + o.rows_per_block);
+    const int wv8 = o.W >> 3;
+    const float add = (SHIFT ? o.shift[c] : 0.f) + 0.f;
+    const float mu = mean[c], rs = rstd[c];
+    float s1 = 0.f, s2 = 0.f;
+    for (int i = threadIdx.x; i < (r1 - r0) * wv8; i += 256) {
+        int yy, x8;
+        item8(o, i, wv8, r0, yy, x8);
+        float t[8], g[8];
+        sum8<T, A16, S, true>(o, plane, yy, x8, add, dy, t, g);
+        s1 += (g[0] + g[1]) + (g[2] + g[3]);
+        s2 += (g[0] * (t[0] - mu) + g[1] * (t[1] - mu)) + (g[2] * (t[2] - mu) + g[3] * (t[3] - mu));
+        s1 += (g[4] + g[5]) + (g[6] + g[7]);
+        s2 += (g[4] * (t[4] - mu) + g[5] * (t[5] - mu)) + (g[6] * (t[6] - mu) + g[7] * (t[7] - mu));
+    }
+    s1 = block_sum(s1, s_red);
+    s2 = block_sum(s2, s_red) * rs;
+    if (threadIdx.x == 0) {
+        float *row = part + (n * o.chunks + chunk) * 2 * o.C;
+        row[c] = s1;
+        row[o.C + c] = s2;
+    }
+}
+
+// The adjoint of the upsample with the weights of the scale as constants.  Low-res index j collects the 2S high-res
+// positions S j - S / 2 + u, u = 0 .. 2S - 1, with weights (2u + 1) / 2S rising, then falling: 1/8 3/8 5/8 7/8 | 7/8 5/8 3/8
+// 1/8 at S = 4, 1/4 3/4 | 3/4 1/4 at S = 2; every other position of the general form's loop has weight exactly 0.  At the
+// two borders the clamped source positions fold both taps onto the border index: the S / 2 positions next to the border
+// weigh (1 - w) + w = 1 and the S / 2 beyond it do not exist.  A term that does not exist (or, in the row pass, lies in
+// another tile) leaves the sum as it is.  Terms are added in ascending position, as the general form adds them.
+// TILE: positions lo .. hi - 1 only are present (the rows of this tile); otherwise the whole axis 0 .. S n_lo - 1 is.
+template <int S, bool TILE>
+__device__ __forceinline__ float adjoint_taps(const float *p, int stride, int j, int n_lo, int lo, int hi) {
+    float acc = 0.f;
+#pragma unroll
+    for (int u = 0; u < 2 * S; ++u) {
+        const float wc = (float)(u < S ? 2 * u + 1 : 4 * S - 2 * u - 1) * (0.5f / (float)S);
+        const int pos = S * j - S / 2 + u;
+        const bool inner = u >= S / 2 && u < S + S / 2;
+        const bool at_border = u < S ? j == 0 : j == n_lo - 1;
+        const float w = inner && at_border ? 1.f : wc;
+        // fmaf, spelled out: the general form's `acc += w * row[x]` contracts to one fma, and so must every term here
+        // (left to the compiler, a term under a select became a multiply and an add: two roundings)
+        if (!TILE && inner) {                                           // always there: S j <= pos < S (j + 1)
+            acc = __builtin_fmaf(w, p[pos * stride], acc);
+        } else {
+            const bool there = (inner || !at_border) && (!TILE || (pos >= lo && pos < hi));
+            const int at = TILE ? min(max(pos, lo), hi - 1) - lo : (u < S ? max(pos, 0) : min(pos, S * n_lo - 1));
+            const float sum = __builtin_fmaf(w, p[at * stride], acc);
+            acc = there ? sum : acc;
+        }
+    }
+    return acc;
+}
+
+// dt, da and dxlo as tail_bwd_apply_kernel; b absent, da and dxlo present, dy fp32
+template <typename T, bool A16, int S, bool SHIFT>
+__global__ __launch_bounds__(256) void tail_bwd_apply_form_kernel(Operands o, const float *__restrict__ mean,
+                                                                  const float *__restrict__ rstd,
+                                                                  const float *__restrict__ gamma,
+                                                                  const float *__restrict__ dy,
+                                                                  const float *__restrict__ mdy,
+                                                                  const float *__restrict__ mdyx, void *__restrict__ da,
+                                                                  float *__restrict__ dxlo) {
+    extern __shared__ __attribute__((aligned(16))) float s_tile[];     // [rows][W] dt, then [rows][Wl] column sums
+    const int64_t plane = blockIdx.x / o.chunks;
+    const int chunk = blockIdx.x % o.chunks;
+    const int c = (int)(plane % o.C);
+    const int r0 = chunk * o.rows_per_block, r1 = min(o.H, r0 + o.rows_per_block);
+    const int rows = r1 - r0;
+    const int wv8 = o.W >> 3;
+    const float add = (SHIFT ? o.shift[c] : 0.f) + 0.f;
+    const float mu = mean[c], rs = rstd[c];
+    const float k = rs * (gamma ? gamma[c] : 1.f), m1 = mdy[c], m2 = mdyx[c];
+    for (int i = threadIdx.x; i < rows * wv8; i += 256) {
+        int yy, x8;
+        item8(o, i, wv8, r0, yy, x8);
+        const int64_t idx = (plane * o.H + yy) * o.W + x8;
+        float t[8], g[8], d[8];
+        sum8<T, A16, S, true>(o, plane, yy, x8, add, dy, t, g);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d[e] = k * (g[e] - m1 - (t[e] - mu) * rs * m2);
+        const float4 d0 = make_float4(d[0], d[1], d[2], d[3]), d1 = make_float4(d[4], d[5], d[6], d[7]);
+        if constexpr (A16) {
+            vec8<T> v;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (T)d[e];
+            *reinterpret_cast<vec8<T> *>(reinterpret_cast<T *>(da) + idx) = v;
+        } else {
+            *reinterpret_cast<float4 *>(reinterpret_cast<float *>(da) + idx) = d0;
+            *reinterpret_cast<float4 *>(reinterpret_cast<float *>(da) + idx + 4) = d1;
+        }
+        float *lo = S == 1 ? dxlo + idx : s_tile + (yy - r0) * o.W + x8;         // scale 1: same grid, plain store
+        *reinterpret_cast<float4 *>(lo) = d0;
+        *reinterpret_cast<float4 *>(lo + 4) = d1;
+    }
+    if constexpr (S > 1) {
+        __syncthreads();
+        float *s_col = s_tile + rows * o.W;                              // [rows][Wl]
+        const int Wl = o.Wl;
+        for (int i = threadIdx.x; i < rows * Wl; i += 256) {
+            const int ry = (int)__umulhi((unsigned)i, o.lo_magic), j = i - ry * Wl;
+            s_col[i] = adjoint_taps<S, false>(s_tile + ry * o.W, 1, j, Wl, 0, o.W);
+        }
+        __syncthreads();
+        const int i_lo = tap_of(r0, o.Hl, S).i0, i_hi = tap_of(r1 - 1, o.Hl, S).i1;
+        float *out = dxlo + plane * o.Hl * Wl;
+        for (int i = threadIdx.x; i < (i_hi - i_lo + 1) * Wl; i += 256) {
+            const int ly = (int)__umulhi((unsigned)i, o.lo_magic), li = i_lo + ly, j = i - ly * Wl;
+            const float acc = adjoint_taps<S, true>(s_col + j, Wl, li, o.Hl, r0, r1);
+            // rows whose footprint lies wholly inside this tile are owned by it; the others are shared
+            const bool owned = S * (li - 1) >= r0 && S * (li + 2) - 1 <= r1 - 1;
+            if (owned || (li == 0 && r0 == 0 && S * (li + 2) - 1 <= r1 - 1) ||
+                (li == o.Hl - 1 && r1 == o.H && S * (li - 1) >= r0))
+                out[(int64_t)li * Wl + j] += acc;                       // no other workgroup touches this row
+            else
+                atomicAdd(out + (int64_t)li * Wl + j, acc);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void tail_finalize(const float *__restrict__ part, int nparts, int K,
                                                      float *__restrict__ out) {
     __shared__ float s_acc[8][32];
@@ -645,8 +999,34 @@ int plan_tail(const char *fn, Operands &o, int has_x, int scale, int64_t N, int6
         return fail(VAH_E_SHAPE, "%s: a tile of %d rows x (%d + %d) floats does not fit %d KB of LDS (batch too large for "
                     "this map, or rows too wide)", fn, o.rows_per_block, o.W, o.Wl, (int)(kTailLdsMax / 1024));
     o.quad_magic = W / 4 > 1 ? (unsigned)(((uint64_t)1 << 32) / (uint64_t)(W / 4)) + 1u : 0u;      // one quad per row: no division
+    // fixed forms: fewer items than quads, and rows_per_block * Wl <= rows_per_block * W / 2 < 2^16 as well (the LDS
+    // limit above holds rows_per_block * W below 38400 where there is an x at scale > 1)
+    o.oct_magic = W / 8 > 1 ? (unsigned)(((uint64_t)1 << 32) / (uint64_t)(W / 8)) + 1u : 0u;
+    o.lo_magic = o.Wl > 1 ? (unsigned)(((uint64_t)1 << 32) / (uint64_t)o.Wl) + 1u : 0u;
     return VAH_OK;
 }
+
+// Which fixed form a call takes (0: the general form).  VAH_TAIL_FORM=general, read per call, sends every call to the
+// general form: the A/B handle of tests/test_tail_forms_gpu.py and of the measurements in DESIGN 4.7.
+enum TailForm { kFormGeneral = 0, kFormNorm1, kFormNorm2, kFormNorm3 };
+
+TailForm tail_form(const Operands &o, int relu, int out_16) {
+    if (o.b || !o.x || relu || out_16 || o.W % 8 || (uintptr_t)o.a % 16) return kFormGeneral;      // 16-byte loads
+    const char *e = getenv("VAH_TAIL_FORM");
+    if (e && !strcmp(e, "general")) return kFormGeneral;
+    if (o.a_bf16 && o.scale == 4 && o.shift) return kFormNorm1;
+    if (!o.a_bf16 && o.scale == 2 && !o.shift) return kFormNorm2;
+    if (!o.a_bf16 && o.scale == 1 && !o.shift) return kFormNorm3;
+    return kFormGeneral;
+}
+
+// KERNEL<T, A16, S, SHIFT> of `form` (not kFormGeneral)
+#define VAH_TAIL_FORM_LAUNCH(form, KERNEL, grid, smem, st, ...)                                                   \
+    do {                                                                                                          \
+        if ((form) == kFormNorm1) hipLaunchKernelGGL((KERNEL<T, true, 4, true>), grid, dim3(256), smem, st, __VA_ARGS__);        \
+        else if ((form) == kFormNorm2) hipLaunchKernelGGL((KERNEL<T, false, 2, false>), grid, dim3(256), smem, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERNEL<T, false, 1, false>), grid, dim3(256), smem, st, __VA_ARGS__);            \
+    } while (0)
 
 int fill_operands(const char *fn, Operands &o, const void *a, int a_bf16, const void *b, int b_bf16, const float *x,
                   int scale, int64_t N, int64_t C, int64_t H, int64_t W) {
@@ -732,7 +1112,9 @@ int tail_stats_launch(const char *fn, const void *a, int a_bf16, const void *b, 
     const int nparts = (int)N * o.chunks;
     LaunchScope scope(tname<T>("bn_tail_stats", "bn_tail_stats_f16"),
                       N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0)), st);
-    hipLaunchKernelGGL(tail_stats_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, ws);
+    const dim3 grid((unsigned)(N * C * o.chunks));
+    if (const TailForm form = tail_form(o, 0, 0)) VAH_TAIL_FORM_LAUNCH(form, tail_stats_form_kernel, grid, 0, st, o, ws);
+    else hipLaunchKernelGGL(tail_stats_kernel<T>, grid, dim3(256), 0, st, o, ws);
     hipLaunchKernelGGL(tail_finalize, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, ws, nparts, (int)(2 * C), sums);
     return check_launch(fn);
 }
@@ -752,7 +1134,11 @@ int tail_apply_launch(const char *fn, const void *a, int a_bf16, const void *b, 
     hipStream_t st = (hipStream_t)stream;
     LaunchScope scope(tname<T>("bn_tail_apply", "bn_tail_apply_f16"),
                       N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0) + 4), st);
-    hipLaunchKernelGGL(tail_apply_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, mean, rstd, gamma, beta, y);
+    const dim3 grid((unsigned)(N * C * o.chunks));
+    if (const TailForm form = tail_form(o, o.relu, o.y_bf16))
+        VAH_TAIL_FORM_LAUNCH(form, tail_apply_form_kernel, grid, 0, st, o, mean, rstd, gamma, beta, (float *)y);
+    else
+        hipLaunchKernelGGL(tail_apply_kernel<T>, grid, dim3(256), 0, st, o, mean, rstd, gamma, beta, y);
     return check_launch(fn);
 }
 
@@ -773,8 +1159,11 @@ int tail_bwd_stats_launch(const char *fn, const void *a, int a_bf16, const void 
     const int nparts = (int)N * o.chunks;
     LaunchScope scope(tname<T>("bn_tail_bwd_stats", "bn_tail_bwd_stats_f16"),
                       N * C * H * W * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0) + 4), st);
-    hipLaunchKernelGGL(tail_bwd_stats_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), 0, st, o, mean, rstd, gamma, beta,
-                       dy, ws);
+    const dim3 grid((unsigned)(N * C * o.chunks));
+    if (const TailForm form = tail_form(o, o.relu, o.dy_bf16))
+        VAH_TAIL_FORM_LAUNCH(form, tail_bwd_stats_form_kernel, grid, 0, st, o, mean, rstd, (const float *)dy, ws);
+    else
+        hipLaunchKernelGGL(tail_bwd_stats_kernel<T>, grid, dim3(256), 0, st, o, mean, rstd, gamma, beta, dy, ws);
     hipLaunchKernelGGL(tail_finalize, dim3((unsigned)((2 * C + 31) / 32)), dim3(256), 0, st, ws, nparts, (int)(2 * C), sums);
     return check_launch(fn);
 }
@@ -798,10 +1187,19 @@ int tail_bwd_apply_launch(const char *fn, const void *a, int a_bf16, const void 
     if (dxlo && x && scale > 1) smem = (size_t)o.rows_per_block * (o.W + o.Wl) * sizeof(float);
     LaunchScope scope(tname<T>("bn_tail_bwd_apply", "bn_tail_bwd_apply_f16"),
                       N * C * H * W * (2 * ((a_bf16 ? 2 : 4) + (b ? (b_bf16 ? 2 : 4) : 0)) + 4), st);
-    if (smem > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)tail_bwd_apply_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(tail_bwd_apply_kernel<T>, dim3((unsigned)(N * C * o.chunks)), dim3(256), smem, st, o, mean, rstd, gamma,
-                       beta, dy, mdy, mdyx, da, db, dxlo);
+    const dim3 grid((unsigned)(N * C * o.chunks));
+    const TailForm form = da && (uintptr_t)da % 16 == 0 && !db && dxlo ? tail_form(o, o.relu, o.dy_bf16) : kFormGeneral;
+    if (smem > 64 * 1024) {
+        const void *fnp = (const void *)tail_bwd_apply_kernel<T>;
+        if (form == kFormNorm1) fnp = (const void *)tail_bwd_apply_form_kernel<T, true, 4, true>;
+        else if (form == kFormNorm2) fnp = (const void *)tail_bwd_apply_form_kernel<T, false, 2, false>;
+        (void)hipFuncSetAttribute(fnp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    }
+    if (form)
+        VAH_TAIL_FORM_LAUNCH(form, tail_bwd_apply_form_kernel, grid, smem, st, o, mean, rstd, gamma, (const float *)dy, mdy, mdyx, da,
+                             dxlo);
+    else
+        hipLaunchKernelGGL(tail_bwd_apply_kernel<T>, grid, dim3(256), smem, st, o, mean, rstd, gamma, beta, dy, mdy, mdyx, da, db, dxlo);
     return check_launch(fn);
 }
 
