@@ -182,6 +182,22 @@ for _name, (_res, _args) in BOX_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_group_norm.h declares (GroupNorm on channels-last
+# rows, csrc/group_norm.hip).  A tensor operand is (pointer, dtype code, row stride, image stride); the dtype is an
+# argument, so there are no fp16 twins.  tests/test_group_norm_abi_cpu.py holds each entry to its prototype.
+_t = [_p, _int, _i64, _i64]
+GN_SIGNATURES = {
+    'vah_group_norm_supported': (_int, [_i64, _i64]),
+    'vah_group_norm_ws_floats': (_i64, [_i64, _i64, _i64, _i64]),
+    'vah_group_norm_stats': (_int, _t + [_i64, _i64, _i64, _i64, _f, _p, _p, _p, _i64, _p]),
+    'vah_group_norm_apply': (_int, _t + [_i64, _i64, _i64, _i64, _p, _p, _p, _p, _int, _p] + _t + [_p]),
+    'vah_group_norm_bwd_stats': (_int, _t + _t + [_i64, _i64, _i64, _i64, _p, _p, _p, _p, _int, _p, _p, _p, _p, _i64, _p]),
+    'vah_group_norm_bwd_apply': (_int, _t + _t + [_i64, _i64, _i64, _i64, _p, _p, _p, _p, _int, _p] + _t + [_p]),
+}
+for _name, (_res, _args) in GN_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

@@ -10,7 +10,8 @@ from .backbones import (BEiTAdapter, ViTAdapter, ViTAdapterDet, ViTAdapterSeg, r
                         register_beit_adapter)
 
 from .mmcv_attention import MultiScaleDeformableAttention, register_attention
+from .pixel_decoder import MSDeformAttnPixelDecoder, register_pixel_decoder
 
 __all__ = ['ViTAdapter', 'ViTAdapterSeg', 'ViTAdapterDet', 'register_backbones', 'BEiTAdapter',
            'register_beit_adapter',
-           'MultiScaleDeformableAttention', 'register_attention']
+           'MultiScaleDeformableAttention', 'register_attention', 'MSDeformAttnPixelDecoder', 'register_pixel_decoder']

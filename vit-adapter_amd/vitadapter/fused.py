@@ -18,6 +18,9 @@ fp32 straight from the accumulators (torch rounds dW to fp16 first), the same si
 partials as for bf16.  conv1x1, patch embedding and the MSDA pair core stay bf16-only; under fp16 autocast they are
 torch's - the deformable attention itself is not: MSDeformAttn's fp16 value / offsets / logits go to the fp16
 instantiation of the fused MSDA kernels (ops/functions/ms_deform_attn_fused.py; ENABLED['fp16_msda']).
+
+group_norm (csrc/group_norm.hip, ENABLED['group_norm']) is the GroupNorm of the pixel decoder's ConvModules on
+channels-last rows: fp32 without autocast, bf16 / fp16 (fp16 under ENABLED['fp16_rows']) maps with fp32 statistics under it.
 """
 import os
 
@@ -30,7 +33,8 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'bn_relu': True, 'bias_fold': True, 'keep_feat': True, 'maps': True, 'maps_in': True, 'linear_pair': True, 'maxpool': True, 'conv1x1': True, 'ln_dual': True, 'wgrad_fin': True, 'spm_nhwc': True, 'up_gemm': True, 'patch_gemm': True, 'wgrad_overlap': True, 'drop_pool': True,
            'fp16_rows': True, 'fp16_spm': True, 'fp16_tail': True, 'bias_partials': True,
            'fp16_linear': True,
-           'fp16_msda': True}        # fp16_msda: read by ops.functions.ms_deform_attn_fused.fused_supported
+           'fp16_msda': True,        # fp16_msda: read by ops.functions.ms_deform_attn_fused.fused_supported
+           'group_norm': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -1658,3 +1662,116 @@ def max_pool(pool, x):
         return _MaxPool3s2.apply(x)
     return pool(x)
 
+
+
+_GN_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+def _gn_rows_ok(t):
+    """Is ``t`` (N, T, C) a channels-last rows tensor the GroupNorm kernels address directly: contiguous channels,
+    16-byte aligned, strides in multiples of 8 elements?  A contiguous tensor is, and so is a level's row range of an
+    (Lq, N, C) buffer seen as (N, T, C)."""
+    N, T, C = t.shape
+    return (t.stride(2) == 1 and t.data_ptr() % 16 == 0 and (N == 1 or t.stride(0) % 8 == 0)
+            and (T == 1 or (t.stride(1) % 8 == 0 and t.stride(1) >= C)))
+
+
+def _gn_arg(t):
+    """(pointer, dtype code, row stride, image stride) of a rows tensor"""
+    N, T, C = t.shape
+    return t.data_ptr(), _GN_CODES[t.dtype], (t.stride(1) if T > 1 else C), (t.stride(0) if N > 1 else 0)
+
+
+class _GroupNorm(torch.autograd.Function):
+    """GroupNorm (+ ReLU, + addend) over channels-last rows (N, T, C) on csrc/group_norm.hip: fp32 statistics per (image,
+    group), one rounding at the store.  ``out``: a rows view to write into (modified in place: it is the first argument,
+    as autograd's bookkeeping of an in-place change to a view asks) or None.  The backward recomputes the ReLU mask from
+    x; it returns fp32 dgamma / dbeta and dx in x's dtype; the gradient of the addend is dy itself."""
+
+    @staticmethod
+    def forward(ctx, out, x, weight, bias, G, eps, relu, add, ydt):
+        N, T, C = x.shape
+        dev, st, lib = x.device, _stream(x), _vah.lib
+        w = weight.detach().float().contiguous() if weight is not None else None
+        b = bias.detach().float().contiguous() if bias is not None else None
+        mean = torch.empty(N * G, dtype=torch.float32, device=dev)
+        rstd = torch.empty(N * G, dtype=torch.float32, device=dev)
+        nws = lib.vah_group_norm_ws_floats(N, T, C, G)
+        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+        y = out if out is not None else torch.empty((N, T, C), dtype=ydt, device=dev)
+        with _vah.on(dev):
+            _vah.check(lib.vah_group_norm_stats(*_gn_arg(x), N, T, C, G, eps, mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), nws, st),
+                       'vah_group_norm_stats')
+            _vah.check(lib.vah_group_norm_apply(*_gn_arg(x), N, T, C, G, mean.data_ptr(), rstd.data_ptr(),
+                                                w.data_ptr() if w is not None else None, b.data_ptr() if b is not None else None,
+                                                int(relu), add.data_ptr() if add is not None else None, *_gn_arg(y), st),
+                       'vah_group_norm_apply')
+        ctx.save_for_backward(x, mean, rstd, w, b)
+        ctx.meta = (G, relu, weight is not None, bias is not None, out is not None, add is not None)
+        if out is not None:
+            ctx.mark_dirty(out)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd, w, b = ctx.saved_tensors
+        G, relu, has_w, has_b, has_out, has_add = ctx.meta
+        N, T, C = x.shape
+        dev, st, lib = x.device, _stream(x), _vah.lib
+        if dy.dtype not in _GN_CODES or (dy.dtype != torch.float32 and x.dtype != torch.float32 and dy.dtype != x.dtype):
+            dy = dy.to(x.dtype)
+        if not _gn_rows_ok(dy):
+            dy = dy.contiguous()
+        wp = w.data_ptr() if w is not None else None
+        bp = b.data_ptr() if b is not None else None
+        gsums = torch.empty(2 * N * G, dtype=torch.float32, device=dev)
+        dgamma = torch.empty(C, dtype=torch.float32, device=dev) if has_w else None
+        dbeta = torch.empty(C, dtype=torch.float32, device=dev) if has_b else None
+        nws = lib.vah_group_norm_ws_floats(N, T, C, G)
+        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+        dx = None
+        with _vah.on(dev):
+            _vah.check(lib.vah_group_norm_bwd_stats(*_gn_arg(x), *_gn_arg(dy), N, T, C, G, mean.data_ptr(), rstd.data_ptr(), wp, bp,
+                                                    int(relu), gsums.data_ptr(), dgamma.data_ptr() if has_w else None,
+                                                    dbeta.data_ptr() if has_b else None, ws.data_ptr(), nws, st),
+                       'vah_group_norm_bwd_stats')
+            if ctx.needs_input_grad[1]:
+                dx = torch.empty((N, T, C), dtype=x.dtype, device=dev)
+                _vah.check(lib.vah_group_norm_bwd_apply(*_gn_arg(x), *_gn_arg(dy), N, T, C, G, mean.data_ptr(), rstd.data_ptr(), wp, bp,
+                                                        int(relu), gsums.data_ptr(), *_gn_arg(dx), st), 'vah_group_norm_bwd_apply')
+        # `out` was overwritten: its old contents have gradient zero.  Autograd wants a tensor here, not None, to keep the
+        # chain through the buffer the view belongs to: one zero, expanded - nothing of dy's size is allocated or filled
+        return (dy.new_zeros(()).expand_as(dy) if has_out else None, dx, dgamma, dbeta, None, None, None,
+                dy if has_add and ctx.needs_input_grad[7] else None, None)
+
+
+def group_norm(norm, x, relu=False, add=None, out=None, out_dtype=None):
+    """``[relu](norm(x)) [+ add]`` for an nn.GroupNorm on channels-last rows: x (N, T, C) with contiguous channels - an
+    NHWC map with its pixels flattened, or a level's rows of an (Lq, N, C) buffer seen as (N, T, C).  ``add``: (N, T, C)
+    in the result's dtype.  ``out``: a rows view the result is written into and that is returned; else the result is a
+    new (N, T, C) tensor of ``out_dtype`` (default: x's dtype).  The reference's ConvModule (conv -> GN -> ReLU) in the
+    pixel decoder, msdeformattn_pixel_decoder.py:84-124.
+    On the GPU, for the shapes vah_group_norm_supported serves and with ENABLED['group_norm'], this is csrc/group_norm.hip
+    (fp32, bf16, and fp16 under ENABLED['fp16_rows']); otherwise F.group_norm on the (N, C, T) view."""
+    N, T, C = x.shape
+    G = norm.num_groups
+    ydt = out.dtype if out is not None else (out_dtype or x.dtype)
+    ok16 = [d == torch.float32 or takes_16(d, 'fp16_rows') for d in (x.dtype, ydt)]
+    if (ENABLED['group_norm'] and x.is_cuda and x.numel() > 0 and all(ok16)
+            and not (x.dtype != ydt and torch.float32 not in (x.dtype, ydt))
+            and _vah.lib.vah_group_norm_supported(C, G) and (out is None or (out.shape == x.shape and _gn_rows_ok(out)))
+            and (add is None or add.shape == x.shape)):
+        if not _gn_rows_ok(x):
+            x = x.contiguous()
+        if add is not None:
+            add = add.to(ydt).contiguous()
+        return _GroupNorm.apply(out, x, norm.weight, norm.bias, G, float(norm.eps), bool(relu), add, ydt)
+    y = F.group_norm(x.transpose(1, 2), G, norm.weight, norm.bias, norm.eps).transpose(1, 2)
+    if relu:
+        y = torch.relu(y)
+    if add is not None:
+        y = y + add
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y.to(out_dtype or x.dtype)           # under autocast F.group_norm answers in fp32
