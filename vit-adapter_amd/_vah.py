@@ -198,6 +198,18 @@ for _name, (_res, _args) in GN_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_resize.h declares (bilinear resize on channels-last
+# rows and its adjoint, csrc/resize_rows.hip), tensor operands as above.  tests/test_resize_rows_abi_cpu.py holds each entry
+# to its prototype.
+RESIZE_SIGNATURES = {
+    'vah_resize_rows_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'vah_resize_rows_forward': (_int, _t + [_i64, _i64, _i64, _i64, _i64, _i64, _int] + _t + [_p, _i64, _p]),
+    'vah_resize_rows_backward': (_int, _t + [_i64, _i64, _i64, _i64, _i64, _i64, _int] + _t + [_p, _i64, _p]),
+}
+for _name, (_res, _args) in RESIZE_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

@@ -41,6 +41,24 @@ template <typename T> constexpr const char *tname(const char *bf16_name, const c
 template <> constexpr const char *tname<__bf16>(const char *bf16_name, const char *) { return bf16_name; }
 template <> constexpr const char *tname<_Float16>(const char *, const char *f16_name) { return f16_name; }
 
+// The dtype codes of the entry points whose element types are arguments (0 fp32, 1 bf16, 2 fp16): element size in bytes,
+// f(Tag<element type>) for a code, and "a bf16 operand beside an fp16 one" (never instantiated)
+inline int64_t esize(int dt) { return dt == 0 ? 4 : 2; }
+
+template <typename T> struct Tag { typedef T type; };
+
+template <typename F>
+int with_type(int dt, F &&f) {
+    switch (dt) {
+        case 0: return f(Tag<float>{});
+        case 1: return f(Tag<__bf16>{});
+        default: return f(Tag<_Float16>{});
+    }
+}
+
+template <typename A, typename B>
+constexpr bool mixed16() { return sizeof(A) == 2 && sizeof(B) == 2 && !std::is_same<A, B>::value; }
+
 #if defined(__HIPCC__)
 __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -77,6 +95,34 @@ __device__ __forceinline__ float word_elem(const uint32_t *w, int i) {
     else if constexpr (std::is_same<T, _Float16>::value)                      // v_cvt_f32_f16: exact, subnormals kept
         return (float)__builtin_bit_cast(_Float16, (unsigned short)((i & 1) ? w[i >> 1] >> 16 : w[i >> 1] & 0xFFFFu));
     else return __builtin_bit_cast(float, (i & 1) ? (w[i >> 1] & 0xFFFF0000u) : (w[i >> 1] << 16));
+}
+
+// 8 consecutive elements of T (float, _Float16 or __bf16) at a 16-byte aligned address, as fp32: one 16-byte load of
+// 16-bit data, two of fp32 (the channels-last row kernels: group_norm.hip, resize_rows.hip)
+template <typename T>
+__device__ __forceinline__ void load8_f32(const T *p, float (&v)[8]) {
+    if constexpr (sizeof(T) == 4) {
+        const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
+        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+    } else {
+        const vec8<T> t = *reinterpret_cast<const vec8<T> *>(p);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (float)t[j];
+    }
+}
+
+// the store to match: each element rounded once, to nearest even (fp16 overflows to inf and keeps subnormals)
+template <typename T>
+__device__ __forceinline__ void store8_f32(T *p, const float (&v)[8]) {
+    if constexpr (sizeof(T) == 4) {
+        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4 *>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+        vec8<T> t;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] = (T)v[j];
+        *reinterpret_cast<vec8<T> *>(p) = t;
+    }
 }
 #endif
 

@@ -35,31 +35,6 @@ struct GnParams {
     int G, shift;                       // shift = log2(C / G)
 };
 
-template <typename T>
-__device__ __forceinline__ void load8(const T *p, float (&v)[8]) {
-    if constexpr (sizeof(T) == 4) {
-        const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
-    } else {
-        const vec8<T> t = *reinterpret_cast<const vec8<T> *>(p);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)t[j];
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void store8(T *p, const float (&v)[8]) {
-    if constexpr (sizeof(T) == 4) {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4 *>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-        vec8<T> t;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = (T)v[j];
-        *reinterpret_cast<vec8<T> *>(p) = t;
-    }
-}
-
 // the constants of this thread's 8 channels in image n: pre-activation = fma(x, sc, sh), xhat = (x - mu) * rs
 __device__ __forceinline__ void load_consts(const GnParams &p, int n, int c0, float (&sc)[8], float (&sh)[8], float (&mu)[8],
                                             float (&rs)[8], float (&w)[8]) {
@@ -107,16 +82,16 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const TX *__restrict__ x,
         float xv[4][8], gv[4][8];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            load8(xp + (r + u * RL) * xrs, xv[u]);
-            if (MODE == 1) load8(dp + (r + u * RL) * drs, gv[u]);
+            load8_f32(xp + (r + u * RL) * xrs, xv[u]);
+            if (MODE == 1) load8_f32(dp + (r + u * RL) * drs, gv[u]);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) add(xv[u], MODE == 1 ? gv[u] : xv[u]);
     }
     for (; r < r1; r += RL) {
         float xv[8], gv[8];
-        load8(xp + r * xrs, xv);
-        if (MODE == 1) load8(dp + r * drs, gv);
+        load8_f32(xp + r * xrs, xv);
+        if (MODE == 1) load8_f32(dp + r * drs, gv);
         add(xv, MODE == 1 ? gv : xv);
     }
 #pragma unroll
@@ -227,23 +202,23 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const TX *__restrict__ x,
             v[j] = relu ? __builtin_elementwise_maximum(u, 0.f) : u;
             if (ap) v[j] += av[j];
         }
-        store8(yp + t * yrs, v);
+        store8_f32(yp + t * yrs, v);
     };
     int64_t t = (int64_t)blockIdx.x * RL + rl;
     for (; t + (kGnApplyRows - 1) * step < T; t += kGnApplyRows * step) {
         float v[kGnApplyRows][8], av[kGnApplyRows][8];
 #pragma unroll
         for (int u = 0; u < kGnApplyRows; ++u) {
-            load8(xp + (t + u * step) * xrs, v[u]);
-            if (ap) load8(ap + (t + u * step) * C, av[u]);
+            load8_f32(xp + (t + u * step) * xrs, v[u]);
+            if (ap) load8_f32(ap + (t + u * step) * C, av[u]);
         }
 #pragma unroll
         for (int u = 0; u < kGnApplyRows; ++u) finish(t + u * step, v[u], ap ? av[u] : v[u]);
     }
     for (; t < T; t += step) {
         float v[8], av[8];
-        load8(xp + t * xrs, v);
-        if (ap) load8(ap + t * C, av);
+        load8_f32(xp + t * xrs, v);
+        if (ap) load8_f32(ap + t * C, av);
         finish(t, v, ap ? av : v);
     }
 }
@@ -274,23 +249,23 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const TX *__restrict_
             const float g = (!relu || fmaf(v[j], sc[j], sh[j]) > 0.f) ? gv[j] : 0.f;
             v[j] = rs[j] * (g * w[j] - m1[j] - (v[j] - mu[j]) * rs[j] * m2[j]);
         }
-        store8(gp + t * grs, v);
+        store8_f32(gp + t * grs, v);
     };
     int64_t t = (int64_t)blockIdx.x * RL + rl;
     for (; t + (kGnApplyRows - 1) * step < T; t += kGnApplyRows * step) {
         float v[kGnApplyRows][8], gv[kGnApplyRows][8];
 #pragma unroll
         for (int u = 0; u < kGnApplyRows; ++u) {
-            load8(xp + (t + u * step) * xrs, v[u]);
-            load8(dp + (t + u * step) * drs, gv[u]);
+            load8_f32(xp + (t + u * step) * xrs, v[u]);
+            load8_f32(dp + (t + u * step) * drs, gv[u]);
         }
 #pragma unroll
         for (int u = 0; u < kGnApplyRows; ++u) finish(t + u * step, v[u], gv[u]);
     }
     for (; t < T; t += step) {
         float v[8], gv[8];
-        load8(xp + t * xrs, v);
-        load8(dp + t * drs, gv);
+        load8_f32(xp + t * xrs, v);
+        load8_f32(dp + t * drs, gv);
         finish(t, v, gv);
     }
 }
@@ -358,23 +333,6 @@ int gn_check_ws(const char *fn, const float *ws, int64_t ws_floats, int64_t N, i
     if (ws_floats < (int64_t)N * gn_parts(N, T) * 2 * C) return fail(VAH_E_SHAPE, "%s: workspace too small", fn);
     return 0;
 }
-
-int64_t esize(int dt) { return dt == 0 ? 4 : 2; }
-
-template <typename T> struct Tag { typedef T type; };
-
-// f(Tag<element type>) for a dtype code
-template <typename F>
-int with_type(int dt, F &&f) {
-    switch (dt) {
-        case 0: return f(Tag<float>{});
-        case 1: return f(Tag<__bf16>{});
-        default: return f(Tag<_Float16>{});
-    }
-}
-
-template <typename A, typename B>
-constexpr bool mixed16() { return sizeof(A) == 2 && sizeof(B) == 2 && !std::is_same<A, B>::value; }
 
 const char *gn_name(bool f16, const char *a, const char *b) { return f16 ? b : a; }
 

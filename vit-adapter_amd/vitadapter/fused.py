@@ -21,6 +21,8 @@ instantiation of the fused MSDA kernels (ops/functions/ms_deform_attn_fused.py; 
 
 group_norm (csrc/group_norm.hip, ENABLED['group_norm']) is the GroupNorm of the pixel decoder's ConvModules on
 channels-last rows: fp32 without autocast, bf16 / fp16 (fp16 under ENABLED['fp16_rows']) maps with fp32 statistics under it.
+resize_bilinear_rows (csrc/resize_rows.hip, ENABLED['bilinear_rows']) is F.interpolate(mode='bilinear', size=...) on the same
+rows, with a gather-form adjoint that has no atomics: the upsample of the pixel decoder's FPN tail.
 """
 import os
 
@@ -34,7 +36,8 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'fp16_rows': True, 'fp16_spm': True, 'fp16_tail': True, 'bias_partials': True,
            'fp16_linear': True,
            'fp16_msda': True,        # fp16_msda: read by ops.functions.ms_deform_attn_fused.fused_supported
-           'group_norm': True}
+           'group_norm': True,
+           'bilinear_rows': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -1775,3 +1778,62 @@ def group_norm(norm, x, relu=False, add=None, out=None, out_dtype=None):
         out.copy_(y)
         return out
     return y.to(out_dtype or x.dtype)           # under autocast F.group_norm answers in fp32
+
+
+class _ResizeBilinearRows(torch.autograd.Function):
+    """Bilinear resize of channels-last rows (N, Hi * Wi, C) -> (N, Ho * Wo, C) on csrc/resize_rows.hip: fp32 arithmetic,
+    one rounding at the store.  The backward is the exact transpose in gather form - a fixed order of additions, no
+    atomics - and returns dx in x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, hw_in, hw_out, align_corners, ydt):
+        N, _, C = x.shape
+        (Hi, Wi), (Ho, Wo) = hw_in, hw_out
+        dev, st, lib = x.device, _stream(x), _vah.lib
+        nws = lib.vah_resize_rows_ws_bytes(Hi, Wi, Ho, Wo)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        y = torch.empty((N, Ho * Wo, C), dtype=ydt, device=dev)
+        with _vah.on(dev):
+            _vah.check(lib.vah_resize_rows_forward(*_gn_arg(x), N, C, Hi, Wi, Ho, Wo, int(align_corners), *_gn_arg(y),
+                                                   ws.data_ptr(), nws, st), 'vah_resize_rows_forward')
+        ctx.meta = (hw_in, hw_out, align_corners, x.dtype, C)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (Hi, Wi), (Ho, Wo), align_corners, xdt, C = ctx.meta
+        N = dy.shape[0]
+        dev, st, lib = dy.device, _stream(dy), _vah.lib
+        if dy.dtype not in _GN_CODES or (dy.dtype != torch.float32 and xdt != torch.float32 and dy.dtype != xdt):
+            dy = dy.to(xdt)
+        if not _gn_rows_ok(dy):
+            dy = dy.contiguous()
+        nws = lib.vah_resize_rows_ws_bytes(Hi, Wi, Ho, Wo)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        dx = torch.empty((N, Hi * Wi, C), dtype=xdt, device=dev)
+        with _vah.on(dev):
+            _vah.check(lib.vah_resize_rows_backward(*_gn_arg(dy), N, C, Hi, Wi, Ho, Wo, int(align_corners), *_gn_arg(dx),
+                                                    ws.data_ptr(), nws, st), 'vah_resize_rows_backward')
+        return dx, None, None, None, None
+
+
+def resize_bilinear_rows(x, hw_in, hw_out, align_corners=False, out_dtype=None):
+    """``F.interpolate(x as (N, C, Hi, Wi), size=hw_out, mode='bilinear', align_corners=align_corners)`` on channels-last
+    rows: x (N, Hi * Wi, C) with contiguous channels - an NHWC map with its pixels flattened, or a level's rows of an
+    (Lq, N, C) buffer seen as (N, T, C), read in place.  Returns a new contiguous (N, Ho * Wo, C) tensor of ``out_dtype``
+    (default: x's dtype).  The reference's upsample of the FPN tail, msdeformattn_pixel_decoder.py:258-262.
+    On the GPU, for C a multiple of 8 and with ENABLED['bilinear_rows'], this is csrc/resize_rows.hip (fp32, bf16, and fp16
+    under ENABLED['fp16_rows']; not a change from one 16-bit type to the other), whose backward is deterministic;
+    otherwise F.interpolate on the NCHW-shaped view, then ``.to(out_dtype)``."""
+    N, T, C = x.shape
+    (Hi, Wi), (Ho, Wo) = hw_in, hw_out
+    assert T == Hi * Wi, (tuple(x.shape), hw_in)
+    ydt = out_dtype or x.dtype
+    ok16 = [d == torch.float32 or takes_16(d, 'fp16_rows') for d in (x.dtype, ydt)]
+    if (ENABLED['bilinear_rows'] and x.is_cuda and x.numel() > 0 and Ho * Wo > 0 and C % 8 == 0 and all(ok16)
+            and not (x.dtype != ydt and torch.float32 not in (x.dtype, ydt))):
+        if not _gn_rows_ok(x):
+            x = x.contiguous()
+        return _ResizeBilinearRows.apply(x, (int(Hi), int(Wi)), (int(Ho), int(Wo)), bool(align_corners), ydt)
+    y = F.interpolate(x.permute(0, 2, 1).reshape(N, C, Hi, Wi), size=(Ho, Wo), mode='bilinear', align_corners=align_corners)
+    return y.permute(0, 2, 3, 1).reshape(N, Ho * Wo, C).to(ydt).contiguous()

@@ -205,7 +205,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
     all-valid mask + level embedding), the pixel-centre reference points - one (1, Lq, L, 2) grid shared by the batch,
     valid ratios being one - and the level geometry are constants of (h, w, device) and cached; the reference's all-False
     padding mask is not built.  After the encoder the stride-4 tail runs lateral 1 x 1 -> GroupNorm + bilinear upsample of
-    the finest encoder level (torch's interpolate, summed in by the GroupNorm kernel) -> 3 x 3 conv (vitadapter.conv on
+    the finest encoder level (fused.resize_bilinear_rows, summed in by the GroupNorm kernel) -> 3 x 3 conv (vitadapter.conv on
     NHWC under 16-bit autocast) -> GroupNorm + ReLU -> ``mask_feature`` as a product on the rows.  Under 16-bit autocast
     the intermediate maps are 16-bit, the query buffer and the statistics fp32; without autocast everything is fp32; on
     the CPU the torch expressions run throughout.
@@ -353,6 +353,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
                               spatial_shapes=ss, reference_points=ref, level_start_index=lsi)
         outs, start = [], 0
         for h, w in shapes:                             # (h * w, N, C) rows of the buffer -> NCHW-shaped views
+            top, top_hw = memory[start:start + h * w].permute(1, 0, 2), (h, w)      # the same rows as (N, h * w, C), in place
             outs.append(memory[start:start + h * w].permute(1, 2, 0).reshape(N, -1, h, w))
             start += h * w
         t16 = fused.autocast_16('fp16_rows') if feats[0].is_cuda else None
@@ -361,10 +362,12 @@ class MSDeformAttnPixelDecoder(nn.Module):
             x = feats[i]
             hw = tuple(x.shape[-2:])
             lat = _conv1x1_rows(self.lateral_convs[i].conv, _rows(x))
-            up = _rows(F.interpolate(outs[-1], size=hw, mode='bilinear', align_corners=False))
-            rows = fused.group_norm(self.lateral_convs[i].gn, lat, add=up if t16 is None else up.to(t16), out_dtype=t16)
+            # the finest map so far, resized to this level: 16-bit rows straight from the encoder's buffer
+            up = fused.resize_bilinear_rows(top, top_hw, hw, align_corners=False, out_dtype=t16 or torch.float32)
+            rows = fused.group_norm(self.lateral_convs[i].gn, lat, add=up, out_dtype=t16)
             rows = _conv3x3_rows(self.output_convs[i].conv, rows, hw)
             rows = fused.group_norm(self.output_convs[i].gn, rows, relu=self.output_convs[i].with_relu, out_dtype=t16)
+            top, top_hw = rows, hw
             outs.append(_maps(rows, hw))
         last = rows if rows is not None else _rows(outs[-1])
         hw = tuple(outs[-1].shape[-2:])
