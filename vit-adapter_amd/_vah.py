@@ -210,6 +210,21 @@ for _name, (_res, _args) in RESIZE_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_masked_attn.h declares (masked cross-attention of
+# Mask2Former's query decoder, csrc/masked_attn.hip), tensor operands as above with (token stride, image stride).
+# tests/test_masked_attn_abi_cpu.py holds each entry to its prototype.
+_mca_dims = [_i64, _i64, _i64, _i64, _i64, _f]              # N, H, Lq, Lk, head_dim, scale
+MCA_SIGNATURES = {
+    'vah_mca_splits': (_i64, [_i64]),
+    'vah_mca_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'vah_mca_pack_mask': (_int, _t + [_i64, _i64, _i64, _p, _p]),
+    'vah_mca_forward': (_int, _t + _t + _t + [_p] + _mca_dims + _t + [_p, _p, _i64, _p]),
+    'vah_mca_backward': (_int, _t + _t + _t + [_p] + _t + _t + [_p] + _mca_dims + _t + _t + _t + [_p, _i64, _p]),
+}
+for _name, (_res, _args) in MCA_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

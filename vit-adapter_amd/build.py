@@ -26,7 +26,8 @@ FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-Wall', '-Wno-u
 # compiler's default the accumulators live in AGPRs and every such step pays a v_accvgpr_read/write pair per register
 # (190 of 930 instructions in the forward's key loop) and the kernels need 212 - 288 registers (1 - 2 waves per SIMD).
 # Forcing the VGPR form of MFMA removes the copies and brings them to 146 - 202 registers.
-PER_FILE_FLAGS = {f: ['-mllvm', '-amdgpu-mfma-vgpr-form'] for f in ('attn_fwd.hip', 'attn_bwd.hip', 'attn_win.hip', 'attn_flash.hip')}
+PER_FILE_FLAGS = {f: ['-mllvm', '-amdgpu-mfma-vgpr-form'] for f in ('attn_fwd.hip', 'attn_bwd.hip', 'attn_win.hip', 'attn_flash.hip',
+                                                                    'masked_attn.hip')}
 
 
 def _newer(target, deps):

@@ -23,7 +23,10 @@ group_norm (csrc/group_norm.hip, ENABLED['group_norm']) is the GroupNorm of the 
 channels-last rows: fp32 without autocast, bf16 / fp16 (fp16 under ENABLED['fp16_rows']) maps with fp32 statistics under it.
 resize_bilinear_rows (csrc/resize_rows.hip, ENABLED['bilinear_rows']) is F.interpolate(mode='bilinear', size=...) on the same
 rows, with a gather-form adjoint that has no atomics: the upsample of the pixel decoder's FPN tail.
+masked_cross_attention (csrc/masked_attn.hip, ENABLED['masked_attn']) is the cross-attention of Mask2Former's query decoder:
+the mask packed to one bit per (image, query, key) by a sign test, heads of 32 channels, bf16 or fp16 autocast.
 """
+import math
 import os
 
 import torch
@@ -37,7 +40,8 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'fp16_linear': True,
            'fp16_msda': True,        # fp16_msda: read by ops.functions.ms_deform_attn_fused.fused_supported
            'group_norm': True,
-           'bilinear_rows': True}
+           'bilinear_rows': True,
+           'masked_attn': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -1837,3 +1841,100 @@ def resize_bilinear_rows(x, hw_in, hw_out, align_corners=False, out_dtype=None):
         return _ResizeBilinearRows.apply(x, (int(Hi), int(Wi)), (int(Ho), int(Wo)), bool(align_corners), ydt)
     y = F.interpolate(x.permute(0, 2, 1).reshape(N, C, Hi, Wi), size=(Ho, Wo), mode='bilinear', align_corners=align_corners)
     return y.permute(0, 2, 3, 1).reshape(N, Ho * Wo, C).to(ydt).contiguous()
+
+
+def mca_pack_mask(mask_logits):
+    """(N, Q, Lk) mask logits (fp32, bf16 or fp16, contiguous keys) -> (N, Q, ceil(Lk / 32)) keep-bits as int32 words on
+    csrc/masked_attn.hip: key j is kept iff not (x < 0), a row that keeps nothing keeps everything
+    (include/vitadapter_hip_masked_attn.h).  No gradient, nothing read back to the host."""
+    x = mask_logits.detach()
+    if x.dtype not in _GN_CODES:
+        x = x.float()
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    N, Q, Lk = x.shape
+    bits = torch.empty((N, Q, (Lk + 31) // 32), dtype=torch.int32, device=x.device)
+    with _vah.on(x.device):
+        _vah.check(_vah.lib.vah_mca_pack_mask(x.data_ptr(), _GN_CODES[x.dtype], x.stride(1), x.stride(0), N, Q, Lk, bits.data_ptr(),
+                                              _stream(x)), 'vah_mca_pack_mask')
+    return bits
+
+
+def _mca_rows_ok(t):
+    """(L, N, E) with contiguous channels, 16-byte aligned, strides in multiples of 8 elements"""
+    return t.stride(2) == 1 and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
+
+
+def _mca_arg(t):
+    """(pointer, dtype code, token stride, image stride) of an (L, N, E) tensor"""
+    return t.data_ptr(), _GN_CODES[t.dtype], t.stride(0), t.stride(1)
+
+
+class _MaskedCrossAttention(torch.autograd.Function):
+    """softmax(scale q k^T + (-inf where excluded)) v on csrc/masked_attn.hip: q (Lq, N, H * 32), k and v (Lk, N, H * 32) in
+    one 16-bit type (strided forms are read in place), ``bits`` from mca_pack_mask.  Deterministic in both directions; no
+    gradient for the mask."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bits, H, scale):
+        q, k, v = (t if _mca_rows_ok(t) else t.contiguous() for t in (q, k, v))
+        Lq, N, E = q.shape
+        Lk = k.shape[0]
+        dev, st, lib = q.device, _stream(q), _vah.lib
+        nws = lib.vah_mca_ws_bytes(N, H, Lq, Lk)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        out = torch.empty((Lq, N, E), dtype=q.dtype, device=dev)
+        lse = torch.empty((N, H, Lq), dtype=torch.float32, device=dev)
+        with _vah.on(dev):
+            _vah.check(lib.vah_mca_forward(*_mca_arg(q), *_mca_arg(k), *_mca_arg(v), bits.data_ptr(), N, H, Lq, Lk, E // H, scale,
+                                           *_mca_arg(out), lse.data_ptr(), ws.data_ptr(), nws, st), 'vah_mca_forward')
+        ctx.save_for_backward(q, k, v, bits, out, lse)
+        ctx.meta = (H, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        q, k, v, bits, out, lse = ctx.saved_tensors
+        H, scale = ctx.meta
+        Lq, N, E = q.shape
+        Lk = k.shape[0]
+        dev, st, lib = q.device, _stream(q), _vah.lib
+        if d_out.dtype != q.dtype:
+            d_out = d_out.to(q.dtype)
+        if not _mca_rows_ok(d_out):
+            d_out = d_out.contiguous()
+        nws = lib.vah_mca_ws_bytes(N, H, Lq, Lk)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        dq = torch.empty((Lq, N, E), dtype=q.dtype, device=dev)
+        dkv = torch.empty((2, Lk, N, E), dtype=q.dtype, device=dev)
+        with _vah.on(dev):
+            _vah.check(lib.vah_mca_backward(*_mca_arg(q), *_mca_arg(k), *_mca_arg(v), bits.data_ptr(), *_mca_arg(out), *_mca_arg(d_out),
+                                            lse.data_ptr(), N, H, Lq, Lk, E // H, scale, *_mca_arg(dq), *_mca_arg(dkv[0]),
+                                            *_mca_arg(dkv[1]), ws.data_ptr(), nws, st), 'vah_mca_backward')
+        return dq, dkv[0], dkv[1], None, None, None
+
+
+def masked_cross_attention(q, k, v, mask_logits, num_heads):
+    """Cross-attention of Mask2Former's query decoder (the reference's mask2former_head.py:404-525 around
+    nn.MultiheadAttention): q (Lq, N, E), k and v (Lk, N, E) - the projected rows, possibly column slices of a packed
+    projection - and mask_logits (N, Lq, Lk), the interpolated mask prediction of the previous layer.  Key j is excluded for
+    query i where mask_logits[n, i, j] < 0 (sigmoid < 0.5 in exact arithmetic); a row that excludes every key excludes
+    none.  The mask is shared by the heads and gets no gradient.  Returns (Lq, N, E).
+    On the GPU under bf16 or fp16 autocast, with ENABLED['masked_attn'], heads of 32 channels and Lq <= 128, this is
+    csrc/masked_attn.hip; otherwise the same expression in torch, which does not synchronise with the host either."""
+    Lq, N, E = q.shape
+    Lk = k.shape[0]
+    D = E // num_heads
+    scale = 1.0 / math.sqrt(D)
+    t16 = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled() else None
+    if (ENABLED['masked_attn'] and q.is_cuda and t16 in (torch.bfloat16, torch.float16) and D == 32 and E == 32 * num_heads
+            and 1 <= Lq <= 128 and Lk >= 1 and N >= 1):
+        return _MaskedCrossAttention.apply(q.to(t16), k.to(t16), v.to(t16), mca_pack_mask(mask_logits), num_heads, scale)
+    x = mask_logits.detach()
+    keep = ~(x < 0)
+    keep = keep | ~keep.any(-1, keepdim=True)
+    qh, kh, vh = (t.reshape(t.shape[0], N * num_heads, D).transpose(0, 1) for t in (q, k, v))
+    s = torch.bmm(qh, kh.transpose(1, 2)) * scale
+    s = s.view(N, num_heads, Lq, Lk).masked_fill(~keep[:, None], float('-inf'))
+    p = torch.softmax(s, -1).view(N * num_heads, Lq, Lk)
+    return torch.bmm(p.to(vh.dtype), vh).transpose(0, 1).reshape(Lq, N, E)

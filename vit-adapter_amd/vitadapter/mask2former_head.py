@@ -1,0 +1,250 @@
+"""Mask2Former's head up to its predictions: pixel decoder, query decoder on the masked cross-attention kernels, class and
+mask heads (BASELINE configs[4]).
+
+The reference is /root/reference/segmentation/mmseg_custom/models/decode_heads/mask2former_head.py (constructor :57-141,
+``init_weights`` :143-152, ``forward_head`` :404-444, ``forward`` :446-525) with the config
+configs/_base_/models/mask2former_beit.py:20-111.  ``Mask2FormerHead`` here takes its constructor arguments and defaults,
+keeps its state-dict layout, and returns what its ``forward`` returns: ``(cls_pred_list, mask_pred_list)``.  The losses, the
+assigner, the sampler and point sampling are not built: ``loss_*``, ``train_cfg`` and ``test_cfg`` are kept as attributes.
+
+The query decoder is mmcv's ``DetrTransformerDecoder`` of ``DetrTransformerDecoderLayer``s with
+``operation_order=('cross_attn', 'norm', 'self_attn', 'norm', 'ffn', 'norm')`` around ``MultiheadAttention`` (a wrapper of
+nn.MultiheadAttention that adds the position terms and its own identity) and ``FFN``.  mmcv is not part of the reference tree:
+those layer classes are restated from mmcv 1.4's published code with its parameter names, PARITY UNPINNED against mmcv; the
+head's own composition is pinned by tests/golden/mask2former_head.npz, which is computed by the reference's class.
+
+Differences from the reference's expression, none in the arithmetic it defines:
+  * the decoder inputs are the level rows of the pixel decoder's (Lq, N, C) buffer, read in place, plus the level embedding;
+    the key position term is the sine encoding of an all-valid mask, built once per (h, w, device) by the pixel decoder's
+    ``_sine`` and shared by the batch;
+  * ``forward_head`` returns the interpolated mask logits as (N, Q, h * w) in fp32 (also under autocast) instead of a
+    head-repeated bool tensor; the layer hands them to ``fused.masked_cross_attention``, which excludes key j where the logit
+    is < 0 and keeps every key of a row that would keep none - the reference's ``sigmoid() < 0.5`` and its
+    ``attn_mask[torch.where(...)] = False``, without the copy per head and without the host synchronisation.  The sign test
+    differs from torch's rounded sigmoid in a thin band below zero (include/vitadapter_hip_masked_attn.h).
+"""
+import copy
+import math
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import fused
+from .pixel_decoder import FFN, MSDeformAttnPixelDecoder, _conv1x1_rows, _ffn_settings, _get, sine_rows
+
+ORDER = ('cross_attn', 'norm', 'self_attn', 'norm', 'ffn', 'norm')
+
+
+def _linear_rows(w, b, x):
+    """``F.linear(x, w, b)`` for a weight that is a parameter or a row slice of one (the three parts of ``in_proj_weight``): the
+    GEMM dispatcher under 16-bit autocast (fused._LinearBF16, as fused.linear and pixel_decoder._conv1x1_rows), F.linear
+    otherwise.  A slice is no leaf, so its gradient goes back through autograd into the parameter's."""
+    t16 = fused.autocast_16('fp16_linear')
+    if (fused.ENABLED['linear'] and x.is_cuda and t16 is not None and w.dtype == torch.float32 and x.dtype in (t16, torch.float32)
+            and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0 and x.numel() > 0):
+        return fused._LinearBF16.apply(x, w, b, t16)
+    return F.linear(x, w, b)
+
+
+class MultiheadAttention(nn.Module):
+    """mmcv ``MultiheadAttention(embed_dims, num_heads, attn_drop=0, proj_drop=0, batch_first=False)``: the parameters live in
+    ``attn`` (an nn.MultiheadAttention, never called), the arithmetic is written out so that the cross-attention can take
+    the masked kernels.  ``forward`` returns ``identity + proj_drop(attention(query + query_pos, key + key_pos, value))``."""
+
+    def __init__(self, embed_dims, num_heads, attn_drop=0.0, proj_drop=0.0):
+        super().__init__()
+        if attn_drop:
+            raise ValueError('attn_drop must be 0 (the attention kernels have no dropout), got %r' % (attn_drop,))
+        self.embed_dims, self.num_heads = embed_dims, num_heads
+        self.attn = nn.MultiheadAttention(embed_dims, num_heads, dropout=0.0)
+        self.proj_drop = nn.Dropout(proj_drop)
+
+    def _project(self, x, part):
+        E = self.embed_dims
+        return _linear_rows(self.attn.in_proj_weight[part * E:(part + 1) * E], self.attn.in_proj_bias[part * E:(part + 1) * E], x)
+
+    def forward(self, query, key, value, query_pos=None, key_pos=None, mask_logits=None):
+        identity = query
+        q = self._project(query if query_pos is None else query + query_pos, 0)
+        k = self._project(key if key_pos is None else key + key_pos, 1)
+        v = self._project(value, 2)
+        Lq, N, E = q.shape
+        H = self.num_heads
+        if mask_logits is not None:
+            out = fused.masked_cross_attention(q, k, v, mask_logits, H)
+        else:
+            qh, kh, vh = (t.reshape(t.shape[0], N, H, E // H).permute(1, 2, 0, 3) for t in (q, k, v))
+            out = F.scaled_dot_product_attention(qh, kh, vh).permute(2, 0, 1, 3).reshape(Lq, N, E)
+        return identity + self.proj_drop(_linear_rows(self.attn.out_proj.weight, self.attn.out_proj.bias, out))
+
+
+class Mask2FormerDecoderLayer(nn.Module):
+    """One ``DetrTransformerDecoderLayer``: masked cross-attention to one level's rows, self-attention among the queries,
+    FFN; post-norm.  ``forward(query, memory_rows, query_pos, key_pos, mask_logits)``: query, query_pos (Q, N, E);
+    memory_rows (Lk, N, E) - keys and values; key_pos broadcastable to it; mask_logits (N, Q, Lk) - see the module docstring."""
+
+    def __init__(self, embed_dims=256, num_heads=8, feedforward_channels=2048, attn_drop=0.0, proj_drop=0.0, ffn_drop=0.0):
+        super().__init__()
+        self.attentions = nn.ModuleList([MultiheadAttention(embed_dims, num_heads, attn_drop, proj_drop) for _ in range(2)])
+        self.ffns = nn.ModuleList([FFN(embed_dims, feedforward_channels, ffn_drop)])
+        self.norms = nn.ModuleList([nn.LayerNorm(embed_dims) for _ in range(3)])
+
+    def forward(self, query, memory_rows, query_pos, key_pos, mask_logits):
+        query = self.attentions[0](query, memory_rows, memory_rows, query_pos, key_pos, mask_logits)
+        # post-norm: a norm's output is the fp32 residual stream itself, not only a GEMM operand, so it is not rounded to the
+        # autocast's type (fused.layer_norm would); torch's LayerNorm answers in fp32 under autocast
+        query = self.norms[0](query)
+        query = self.attentions[1](query, query, query, query_pos, query_pos)
+        query = self.norms[1](query)
+        query = self.ffns[0](query)
+        return self.norms[2](query)
+
+
+class Mask2FormerTransformerDecoder(nn.Module):
+    """``DetrTransformerDecoder(num_layers, transformerlayers, return_intermediate=True)``: the layers and ``post_norm``; the
+    head drives the layers one by one (mask2former_head.py:499-520)."""
+
+    def __init__(self, num_layers, embed_dims, num_heads, feedforward_channels, attn_drop=0.0, proj_drop=0.0, ffn_drop=0.0):
+        super().__init__()
+        self.layers = nn.ModuleList([Mask2FormerDecoderLayer(embed_dims, num_heads, feedforward_channels, attn_drop, proj_drop,
+                                                             ffn_drop) for _ in range(num_layers)])
+        self.post_norm = nn.LayerNorm(embed_dims)
+        self.embed_dims = embed_dims
+
+
+class Mask2FormerHead(nn.Module):
+    """The reference's ``Mask2FormerHead`` (see the module docstring).  ``forward(feats, img_metas=None)`` ->
+    ``(cls_pred_list, mask_pred_list)``: per decoder layer (and once before the first) class logits (N, Q, classes + 1) and mask
+    logits (N, Q, h, w) at the stride of ``mask_feature``, the latter in fp32.  ``decode`` is everything after the pixel
+    decoder."""
+
+    def __init__(self, in_channels, feat_channels, out_channels, num_things_classes=80, num_stuff_classes=53, num_queries=100,
+                 num_transformer_feat_level=3, pixel_decoder=None, enforce_decoder_input_project=False, transformer_decoder=None,
+                 positional_encoding=None, loss_cls=None, loss_mask=None, loss_dice=None, train_cfg=None, test_cfg=None,
+                 init_cfg=None, **kwargs):
+        super().__init__()
+        self.in_channels, self.channels = in_channels, feat_channels
+        self.num_things_classes, self.num_stuff_classes = num_things_classes, num_stuff_classes
+        self.num_classes = num_things_classes + num_stuff_classes
+        self.num_queries = num_queries
+        self.num_transformer_feat_level = num_transformer_feat_level
+        layer = _get(transformer_decoder, 'transformerlayers') or {}
+        attn = _get(layer, 'attn_cfgs') or {}
+        if isinstance(attn, (list, tuple)):
+            if any(a != attn[0] for a in attn):
+                raise ValueError('the two attentions of a layer must share one config')
+            attn = attn[0]
+        order = _get(layer, 'operation_order')
+        if order is None or tuple(order) != ORDER:
+            raise ValueError('operation_order must be %r, got %r' % (ORDER, order))
+        if attn.get('type', 'MultiheadAttention') != 'MultiheadAttention' or attn.get('batch_first', False):
+            raise ValueError('attn_cfgs must describe MultiheadAttention(batch_first=False), got %r' % (attn,))
+        if positional_encoding is None or positional_encoding.get('type') != 'SinePositionalEncoding':
+            raise ValueError('positional_encoding must be a SinePositionalEncoding config, got %r' % (positional_encoding,))
+        embed_dims = attn.get('embed_dims', 256)
+        if embed_dims != feat_channels and not enforce_decoder_input_project:
+            raise ValueError('embed_dims (%d) != feat_channels (%d) needs enforce_decoder_input_project' % (embed_dims, feat_channels))
+        if 2 * positional_encoding.get('num_feats', 128) != embed_dims:
+            raise ValueError('positional_encoding.num_feats must be embed_dims / 2')
+        ffn_width, ffn_drop = _ffn_settings(layer, embed_dims)          # ValueError for an FFN that is not (ReLU, 2 fcs, identity)
+        self.num_heads = attn.get('num_heads', 8)
+        self.num_transformer_decoder_layers = _get(transformer_decoder, 'num_layers', 9)
+        enc_attn = _get(_get(_get(pixel_decoder, 'encoder'), 'transformerlayers'), 'attn_cfgs') or {}
+        if isinstance(enc_attn, (list, tuple)):
+            enc_attn = enc_attn[0]
+        assert enc_attn.get('num_levels', 3) == num_transformer_feat_level
+        pd = {k: v for k, v in copy.deepcopy(dict(pixel_decoder)).items() if k != 'type'}
+        pd.update(in_channels=in_channels, feat_channels=feat_channels, out_channels=out_channels)
+        self.pixel_decoder = MSDeformAttnPixelDecoder(**pd)
+        self.transformer_decoder = Mask2FormerTransformerDecoder(
+            self.num_transformer_decoder_layers, embed_dims, self.num_heads, ffn_width, attn.get('attn_drop', 0.0),
+            attn.get('proj_drop', 0.0), ffn_drop)
+        self.decoder_embed_dims = embed_dims
+        self.decoder_input_projs = nn.ModuleList(
+            nn.Conv2d(feat_channels, embed_dims, kernel_size=1) if (embed_dims != feat_channels or enforce_decoder_input_project)
+            else nn.Identity() for _ in range(num_transformer_feat_level))
+        pe = positional_encoding
+        self.sine = dict(num_feats=pe.get('num_feats', 128), temperature=pe.get('temperature', 10000),
+                         normalize=pe.get('normalize', False), scale=pe.get('scale', 2 * math.pi), eps=pe.get('eps', 1e-6),
+                         offset=pe.get('offset', 0.))
+        self.query_embed = nn.Embedding(num_queries, feat_channels)
+        self.query_feat = nn.Embedding(num_queries, feat_channels)
+        self.level_embed = nn.Embedding(num_transformer_feat_level, feat_channels)
+        self.cls_embed = nn.Linear(feat_channels, self.num_classes + 1)
+        self.mask_embed = nn.Sequential(nn.Linear(feat_channels, feat_channels), nn.ReLU(inplace=True),
+                                        nn.Linear(feat_channels, feat_channels), nn.ReLU(inplace=True),
+                                        nn.Linear(feat_channels, out_channels))
+        self.conv_seg = None
+        self.loss_cls, self.loss_mask, self.loss_dice = loss_cls, loss_mask, loss_dice
+        self.train_cfg, self.test_cfg, self.init_cfg = train_cfg, test_cfg, init_cfg
+        self.class_weight = _get(loss_cls, 'class_weight')
+        self.extra_cfg = kwargs                       # BaseDecodeHead's arguments (in_index, ...): kept, not used
+        self._key_pos = {}
+
+    def init_weights(self):
+        """:143-152, with mmcv's caffe2_xavier_init restated (Kaiming uniform, a = 1, fan_in, leaky_relu)"""
+        for m in self.decoder_input_projs:
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_uniform_(m.weight, a=1, mode='fan_in', nonlinearity='leaky_relu')
+                nn.init.constant_(m.bias, 0)
+        self.pixel_decoder.init_weights()
+        for p in self.transformer_decoder.parameters():
+            if p.dim() > 1:
+                nn.init.xavier_normal_(p)
+
+    def key_pos(self, h, w, device):
+        """the decoder's key position term for an (h, w) level: (h * w, 1, E) fp32, cached"""
+        key = (h, w, str(device))
+        pos = self._key_pos.get(key)
+        if pos is None:
+            if len(self._key_pos) > 16:
+                self._key_pos.clear()
+            pos = self._key_pos[key] = sine_rows(self.sine, h, w, device)[:, None, :]     # the head's own settings
+        return pos
+
+    def forward_head(self, decoder_out, mask_feature, size):
+        """decoder_out (Q, N, C), mask_feature (N, C, h, w) -> cls_pred (N, Q, classes + 1), mask_pred (N, Q, h, w) fp32 and the
+        mask logits of the next cross-attention: mask_pred resized to ``size``, (N, Q, size[0] * size[1]) fp32, no gradient."""
+        x = fused.layer_norm(self.transformer_decoder.post_norm, decoder_out).transpose(0, 1)
+        cls_pred = self.cls_embed(x)
+        m = x
+        for part in self.mask_embed:
+            m = fused.linear(part, m) if isinstance(part, nn.Linear) else torch.relu(m)
+        N, C, h, w = mask_feature.shape
+        with torch.autocast(mask_feature.device.type, enabled=False):
+            mask_pred = torch.matmul(m.float(), mask_feature.float().flatten(2)).view(N, -1, h, w)
+            logits = F.interpolate(mask_pred, size, mode='bilinear', align_corners=False).flatten(2).detach()
+        return cls_pred, mask_pred, logits
+
+    def decode(self, mask_feature, multi_scale_memorys):
+        """everything after the pixel decoder: -> (cls_pred_list, mask_pred_list)"""
+        N = mask_feature.shape[0]
+        inputs, positions, sizes = [], [], []
+        for i in range(self.num_transformer_feat_level):
+            mem = multi_scale_memorys[i]
+            h, w = mem.shape[-2:]
+            rows = mem.flatten(2).permute(2, 0, 1)                # (h * w, N, C): the buffer's own rows when mem is a view of it
+            proj = self.decoder_input_projs[i]
+            if isinstance(proj, nn.Conv2d):
+                rows = _conv1x1_rows(proj, rows).float()
+            inputs.append(rows + self.level_embed.weight[i].view(1, 1, -1))
+            positions.append(self.key_pos(h, w, mem.device))
+            sizes.append((h, w))
+        query = self.query_feat.weight.unsqueeze(1).repeat(1, N, 1)
+        query_pos = self.query_embed.weight.unsqueeze(1).expand(-1, N, -1)
+        cls_preds, mask_preds = [], []
+        cls_pred, mask_pred, logits = self.forward_head(query, mask_feature, sizes[0])
+        cls_preds.append(cls_pred)
+        mask_preds.append(mask_pred)
+        L = self.num_transformer_feat_level
+        for i, layer in enumerate(self.transformer_decoder.layers):
+            query = layer(query, inputs[i % L], query_pos, positions[i % L], logits)
+            cls_pred, mask_pred, logits = self.forward_head(query, mask_feature, sizes[(i + 1) % L])
+            cls_preds.append(cls_pred)
+            mask_preds.append(mask_pred)
+        return cls_preds, mask_preds
+
+    def forward(self, feats, img_metas=None):
+        mask_feature, multi_scale_memorys = self.pixel_decoder(feats)
+        return self.decode(mask_feature, multi_scale_memorys)

@@ -194,6 +194,25 @@ def _conv3x3_rows(conv, rows, hw):
     return _rows(F.conv2d(_maps(rows, hw), w, conv.bias, padding=1))
 
 
+def sine_rows(s, h, w, device):
+    """positional_encoding.py:55-92 for an all-valid (h, w) mask, as rows: (h * w, 2 * num_feats) fp32.  ``s``: the settings
+    of a SinePositionalEncoding (num_feats, temperature, normalize, scale, eps, offset)"""
+    y = torch.arange(1, h + 1, dtype=torch.float32, device=device)
+    x = torch.arange(1, w + 1, dtype=torch.float32, device=device)
+    if s['normalize']:
+        y = (y + s['offset']) / (y[-1:] + s['eps']) * s['scale']
+        x = (x + s['offset']) / (x[-1:] + s['eps']) * s['scale']
+    k = torch.arange(s['num_feats'], dtype=torch.float32, device=device)
+    dim_t = s['temperature'] ** (2 * torch.div(k, 2, rounding_mode='floor') / s['num_feats'])
+
+    def enc(v):                                   # (len,) -> (len, num_feats): sin on even, cos on odd channels
+        p = v[:, None] / dim_t
+        return torch.stack((p[:, 0::2].sin(), p[:, 1::2].cos()), dim=2).flatten(1)
+    py = enc(y)[:, None, :].expand(h, w, -1)
+    px = enc(x)[None, :, :].expand(h, w, -1)
+    return torch.cat((py, px), dim=2).reshape(h * w, -1)
+
+
 class MSDeformAttnPixelDecoder(nn.Module):
     """Mask2Former's pixel decoder (/root/reference/segmentation/mmseg_custom/models/plugins/msdeformattn_pixel_decoder.py:
     16-268): the constructor arguments, defaults, state-dict layout, ``init_weights`` and ``forward(feats) ->
@@ -285,22 +304,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         self.encoder.init_weights()
 
     def _sine(self, h, w, device):
-        """positional_encoding.py:55-92 for an all-valid (h, w) mask, as rows: (h * w, 2 * num_feats) fp32"""
-        s = self.sine
-        y = torch.arange(1, h + 1, dtype=torch.float32, device=device)
-        x = torch.arange(1, w + 1, dtype=torch.float32, device=device)
-        if s['normalize']:
-            y = (y + s['offset']) / (y[-1:] + s['eps']) * s['scale']
-            x = (x + s['offset']) / (x[-1:] + s['eps']) * s['scale']
-        k = torch.arange(s['num_feats'], dtype=torch.float32, device=device)
-        dim_t = s['temperature'] ** (2 * torch.div(k, 2, rounding_mode='floor') / s['num_feats'])
-
-        def enc(v):                                   # (len,) -> (len, num_feats): sin on even, cos on odd channels
-            p = v[:, None] / dim_t
-            return torch.stack((p[:, 0::2].sin(), p[:, 1::2].cos()), dim=2).flatten(1)
-        py = enc(y)[:, None, :].expand(h, w, -1)
-        px = enc(x)[None, :, :].expand(h, w, -1)
-        return torch.cat((py, px), dim=2).reshape(h * w, -1)
+        return sine_rows(self.sine, h, w, device)
 
     def _constants(self, shapes, device):
         """per geometry: spatial_shapes, level_start_index, the (1, Lq, L, 2) reference grid, the sine rows (Lq, C)"""
