@@ -225,6 +225,17 @@ for _name, (_res, _args) in MCA_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_points.h declares (point sampling and the
+# matching cost of Mask2Former's training head, csrc/point_loss.hip).  A map operand is (pointer[, dtype code], map stride,
+# row stride, maps, height, width).  tests/test_points_abi_cpu.py holds each entry to its prototype.
+POINTS_SIGNATURES = {
+    'vah_pts_sample': (_int, [_p, _int, _i64, _i64, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p]),
+    'vah_pts_match_cost': (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _f, _f, _f, _f, _p, _p]),
+}
+for _name, (_res, _args) in POINTS_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

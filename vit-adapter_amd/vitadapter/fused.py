@@ -25,6 +25,8 @@ resize_bilinear_rows (csrc/resize_rows.hip, ENABLED['bilinear_rows']) is F.inter
 rows, with a gather-form adjoint that has no atomics: the upsample of the pixel decoder's FPN tail.
 masked_cross_attention (csrc/masked_attn.hip, ENABLED['masked_attn']) is the cross-attention of Mask2Former's query decoder:
 the mask packed to one bit per (image, query, key) by a sign test, heads of 32 channels, bf16 or fp16 autocast.
+point_sample and match_costs (csrc/point_loss.hip, ENABLED['point_loss']) are mmcv's point_sample without a gradient and the costs
+of MaskHungarianAssigner of Mask2Former's training head, in fp32; point_mask_losses, the sampled BCE / dice, is a torch expression.
 """
 import math
 import os
@@ -41,7 +43,8 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'fp16_msda': True,        # fp16_msda: read by ops.functions.ms_deform_attn_fused.fused_supported
            'group_norm': True,
            'bilinear_rows': True,
-           'masked_attn': True}
+           'masked_attn': True,
+           'point_loss': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -1938,3 +1941,127 @@ def masked_cross_attention(q, k, v, mask_logits, num_heads):
     s = s.view(N, num_heads, Lq, Lk).masked_fill(~keep[:, None], float('-inf'))
     p = torch.softmax(s, -1).view(N * num_heads, Lq, Lk)
     return torch.bmm(p.to(vh.dtype), vh).transpose(0, 1).reshape(Lq, N, E)
+
+
+_PTS_CODES = {torch.float32: 0, torch.uint8: 3, torch.bool: 3}
+
+
+def _pts_maps(maps):
+    """(M, h, w) maps as the point kernels read them: fp32 or uint8 (bool is read as its bytes), contiguous columns"""
+    if maps.dtype not in _PTS_CODES:
+        maps = maps.float()
+    if maps.dtype == torch.bool:
+        maps = maps.view(torch.uint8)
+    if maps.stride(2) != 1 or maps.stride(0) < 0 or maps.stride(1) < maps.shape[2]:
+        maps = maps.contiguous()
+    return maps
+
+
+def _pts_idx(idx, device):
+    if idx is None:
+        return None
+    return torch.as_tensor(idx, device=device).to(torch.int32).contiguous()
+
+
+def _pts_on(t):
+    return ENABLED['point_loss'] and t.is_cuda
+
+
+def _grid_sample_points(maps, points):
+    """mmcv ``point_sample(maps[:, None], points, align_corners=False)[:, 0]``: maps (R, h, w), points (R, P, 2) -> (R, P)"""
+    if maps.shape[0] == 0:
+        return maps.new_zeros((0, points.shape[1])) + 0 * maps.sum()
+    return F.grid_sample(maps[:, None], 2.0 * points[:, None] - 1.0, mode='bilinear', padding_mode='zeros', align_corners=False)[:, 0, 0]
+
+
+def point_sample(maps, points, map_idx=None, set_idx=None):
+    """Row r of the result samples ``maps[map_idx[r]]`` at the points ``points[set_idx[r]]``: maps (M, h, w) fp32, uint8 or
+    bool (ground-truth masks as stored), points (S, P, 2) fp32 in mmcv's convention ((x, y), the unit square is the map), an
+    index of None is the identity.  -> (R, P) fp32, no gradient.  mmcv's ``point_sample(input, points, align_corners=False)``
+    of the reference's mask2former_head.py:237-243, :338-342 and point_sample.py:63.  On the GPU with ENABLED['point_loss']
+    this is vah_pts_sample (csrc/point_loss.hip); otherwise F.grid_sample."""
+    maps, points = maps.detach(), points.detach().float()
+    dev = maps.device
+    if _pts_on(maps) and maps.dim() == 3 and maps.numel() > 0 and points.shape[1] > 0:
+        maps, points = _pts_maps(maps), points.contiguous()
+        mi, si = _pts_idx(map_idx, dev), _pts_idx(set_idx, dev)
+        M, h, w = maps.shape
+        S, P, _ = points.shape
+        R = mi.numel() if mi is not None else (si.numel() if si is not None else M)
+        out = torch.empty((R, P), dtype=torch.float32, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_pts_sample(maps.data_ptr(), _PTS_CODES[maps.dtype], maps.stride(0), maps.stride(1), M, h, w,
+                                               points.data_ptr(), S, P, mi.data_ptr() if mi is not None else None,
+                                               si.data_ptr() if si is not None else None, R, out.data_ptr(), _stream(maps)),
+                       'vah_pts_sample')
+        return out
+    m = maps if map_idx is None else maps[torch.as_tensor(map_idx, device=dev).long()]
+    p = points if set_idx is None else points[torch.as_tensor(set_idx, device=dev).long()]
+    return _grid_sample_points(m.float(), p)
+
+
+def match_costs(xs, ts, cls_scores, labels, gt_counts, weights, eps=1.0, gt_offsets=None):
+    """The cost matrices of the reference's MaskHungarianAssigner (models/utils/assigner.py:126-145 with ClassificationCost,
+    CrossEntropyLossCost(use_sigmoid=True) and DiceCost(pred_act=True) of models/losses/match_costs.py) for one decoder output:
+    xs (N * Q, P) sampled mask logits, ts (G_total, P) sampled ground truth of all images (image n owns ``gt_counts[n]`` rows,
+    in order), cls_scores (N, Q, classes + 1), labels (G_total,), weights = (w_cls, w_mask, w_dice), eps the dice cost's.
+    -> (N, Q, max(gt_counts)) fp32, columns past an image's own count +inf.  No gradient, nothing read back to the host.
+    ``gt_offsets``: the int32 (N + 1,) running sum of gt_counts on the device, if the caller keeps one.
+    On the GPU with ENABLED['point_loss'] this is vah_pts_match_cost; otherwise the reference's formulas."""
+    xs, ts, cls_scores = xs.detach().float(), ts.detach().float(), cls_scores.detach().float()
+    N, Q, C1 = cls_scores.shape
+    P = xs.shape[1]
+    gt_counts = [int(c) for c in gt_counts]
+    Gmax, G_total = max(gt_counts) if gt_counts else 0, sum(gt_counts)
+    dev = xs.device
+    w_cls, w_mask, w_dice = (float(v) for v in weights)
+    cost = torch.full((N, Q, Gmax), float('inf'), dtype=torch.float32, device=dev) if not _pts_on(xs) else None
+    if N * Q * Gmax == 0:
+        return torch.empty((N, Q, Gmax), dtype=torch.float32, device=dev)
+    if _pts_on(xs):
+        if gt_offsets is None:
+            gt_offsets = torch.tensor([sum(gt_counts[:i]) for i in range(N + 1)], dtype=torch.int32, device=dev)
+        xs, ts, cls_scores, labels = xs.contiguous(), ts.contiguous(), cls_scores.contiguous(), labels.long().contiguous()
+        cost = torch.empty((N, Q, Gmax), dtype=torch.float32, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_pts_match_cost(xs.data_ptr(), ts.data_ptr(), gt_offsets.data_ptr(), cls_scores.data_ptr(),
+                                                   labels.data_ptr(), N, Q, C1, G_total, Gmax, P, w_cls, w_mask, w_dice, float(eps),
+                                                   cost.data_ptr(), _stream(xs)), 'vah_pts_match_cost')
+        return cost
+    lo = 0
+    for n, G in enumerate(gt_counts):
+        if G == 0:
+            continue
+        x, t, lab = xs[n * Q:(n + 1) * Q], ts[lo:lo + G], labels[lo:lo + G].long()
+        lo += G
+        c_cls = -cls_scores[n].softmax(-1)[:, lab] * w_cls
+        pos = F.binary_cross_entropy_with_logits(x, torch.ones_like(x), reduction='none')
+        neg = F.binary_cross_entropy_with_logits(x, torch.zeros_like(x), reduction='none')
+        c_mask = (torch.einsum('nc,mc->nm', pos, t) + torch.einsum('nc,mc->nm', neg, 1 - t)) / P * w_mask
+        s = x.sigmoid()
+        c_dice = (1 - (2 * torch.einsum('nc,mc->nm', s, t) + eps) / (s.sum(-1)[:, None] + t.sum(-1)[None, :] + eps)) * w_dice
+        cost[n, :, :G] = c_cls + c_mask + c_dice
+    return cost
+
+
+def point_mask_losses(mask_pred, rows, targets, tgt_rows, points, eps=1.0):
+    """The mask losses of K matched queries before their reduction (the reference's mask2former_head.py:338-356 with
+    CrossEntropyLoss(use_sigmoid=True) and DiceLoss(naive_dice=True)): row k samples ``mask_pred.flatten(0, 1)[rows[k]]``
+    ((N, Q, h, w) logits, differentiable) and ``targets[tgt_rows[k]]`` ((Mt, H, W) masks, fp32 / uint8 / bool at their own
+    resolution) at ``points[k]`` ((K, P, 2), as in point_sample) and returns
+        bce_sum (K,) = sum_p binary_cross_entropy_with_logits(x, t),   dice (K,) = 1 - (2 sum s t + eps) / (sum s + sum t + eps)
+    with s = sigmoid(x).  The targets are sampled by point_sample (no gradient, no float copy of the masks on the kernel
+    path); the predictions, the two losses and their backward are torch's: F.grid_sample, whose backward into mask_pred
+    accumulates with float atomics.  There are no kernels for this part."""
+    dev = mask_pred.device
+    rows_l, tgt_l = torch.as_tensor(rows, device=dev).long(), torch.as_tensor(tgt_rows, device=dev).long()
+    points = points.detach().float()
+    if rows_l.numel() == 0:
+        z = mask_pred.flatten(0, 1)[:0].sum((1, 2)).float()
+        return z, z
+    x = _grid_sample_points(mask_pred.flatten(0, 1)[rows_l].float(), points)
+    t = point_sample(targets, points, map_idx=tgt_l)
+    bce = F.binary_cross_entropy_with_logits(x, t, reduction='none').sum(1)
+    s = x.sigmoid()
+    dice = 1 - (2 * (s * t).sum(1) + eps) / (s.sum(1) + t.sum(1) + eps)
+    return bce, dice

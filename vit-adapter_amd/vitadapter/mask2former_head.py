@@ -1,11 +1,15 @@
-"""Mask2Former's head up to its predictions: pixel decoder, query decoder on the masked cross-attention kernels, class and
-mask heads (BASELINE configs[4]).
+"""Mask2Former's head: pixel decoder, query decoder on the masked cross-attention kernels, class and mask heads, and the
+training losses with their matching on the point-sampling kernels (BASELINE configs[4]).
 
 The reference is /root/reference/segmentation/mmseg_custom/models/decode_heads/mask2former_head.py (constructor :57-141,
 ``init_weights`` :143-152, ``forward_head`` :404-444, ``forward`` :446-525) with the config
 configs/_base_/models/mask2former_beit.py:20-111.  ``Mask2FormerHead`` here takes its constructor arguments and defaults,
-keeps its state-dict layout, and returns what its ``forward`` returns: ``(cls_pred_list, mask_pred_list)``.  The losses, the
-assigner, the sampler and point sampling are not built: ``loss_*``, ``train_cfg`` and ``test_cfg`` are kept as attributes.
+keeps its state-dict layout, and returns what its ``forward`` returns: ``(cls_pred_list, mask_pred_list)``.  ``loss``
+(:154-402), ``forward_train`` and ``forward_test`` (:527-579) are the reference's too: signatures, dict keys and arithmetic.
+mmseg's builders are not here, so the losses, the assigner and the sampler are restated from their config dicts (which stay
+attributes: ``loss_*``, ``train_cfg``, ``test_cfg``): CrossEntropyLoss (softmax, class weights) for the classes,
+CrossEntropyLoss(use_sigmoid=True) and DiceLoss(naive_dice=True) on sampled points for the masks, MaskHungarianAssigner with
+ClassificationCost / CrossEntropyLossCost / DiceCost(pred_act=True) and MaskPseudoSampler.  Anything else is a ValueError.
 
 The query decoder is mmcv's ``DetrTransformerDecoder`` of ``DetrTransformerDecoderLayer``s with
 ``operation_order=('cross_attn', 'norm', 'self_attn', 'norm', 'ffn', 'norm')`` around ``MultiheadAttention`` (a wrapper of
@@ -21,7 +25,17 @@ Differences from the reference's expression, none in the arithmetic it defines:
     head-repeated bool tensor; the layer hands them to ``fused.masked_cross_attention``, which excludes key j where the logit
     is < 0 and keeps every key of a row that would keep none - the reference's ``sigmoid() < 0.5`` and its
     ``attn_mask[torch.where(...)] = False``, without the copy per head and without the host synchronisation.  The sign test
-    differs from torch's rounded sigmoid in a thin band below zero (include/vitadapter_hip_masked_attn.h).
+    differs from torch's rounded sigmoid in a thin band below zero (include/vitadapter_hip_masked_attn.h);
+  * ``loss`` makes ONE host round trip per step where the reference makes one per (decoder output, image): the matching
+    points, sampled predictions and cost matrices of every decoder output and image are computed first
+    (fused.point_sample, fused.match_costs), all costs go to the host in one copy, scipy's linear_sum_assignment runs per
+    (output, image), and the assignments go back in one copy.  Ground-truth masks are concatenated once per step as uint8
+    and sampled at their own resolution without a float copy.  Every random draw goes through ``_draw``: the ORDER of the
+    draws therefore differs from the reference's (all 'match' draws come first, then per decoder output the 'oversample' and
+    the 'random' draw), their distribution does not;
+  * ``max(num_total_masks, 1)`` is a clamp on the device when a process group is initialised and host arithmetic
+    otherwise, not a comparison that synchronises.  The sampled BCE and dice of the matched masks
+    (fused.point_mask_losses) are torch's F.grid_sample and formulas, as in the reference: there are no kernels for them.
 """
 import copy
 import math
@@ -181,6 +195,7 @@ class Mask2FormerHead(nn.Module):
         self.class_weight = _get(loss_cls, 'class_weight')
         self.extra_cfg = kwargs                       # BaseDecodeHead's arguments (in_index, ...): kept, not used
         self._key_pos = {}
+        self._loss_settings()
 
     def init_weights(self):
         """:143-152, with mmcv's caffe2_xavier_init restated (Kaiming uniform, a = 1, fan_in, leaky_relu)"""
@@ -248,3 +263,189 @@ class Mask2FormerHead(nn.Module):
     def forward(self, feats, img_metas=None):
         mask_feature, multi_scale_memorys = self.pixel_decoder(feats)
         return self.decode(mask_feature, multi_scale_memorys)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # training losses (the reference's :154-402) and the two entry points of mmseg's decode heads (:527-579)
+    # ------------------------------------------------------------------------------------------------------------------
+    def _loss_settings(self):
+        """the loss / assigner configs this repository builds, read as mmseg's builders and the classes' defaults read them;
+        a config that is given and asks for anything else is a ValueError.  With ``train_cfg`` None the training settings
+        stay unset and ``loss`` raises."""
+        lc, lm, ld = self.loss_cls, self.loss_mask, self.loss_dice
+        if lc is not None and (lc.get('type', 'CrossEntropyLoss') != 'CrossEntropyLoss' or lc.get('use_sigmoid', False)
+                               or lc.get('use_mask', False) or lc.get('reduction', 'mean') != 'mean'):
+            raise ValueError("loss_cls must describe CrossEntropyLoss(use_sigmoid=False, reduction='mean'), got %r" % (lc,))
+        if lm is not None and (lm.get('type') != 'CrossEntropyLoss' or not lm.get('use_sigmoid', False)
+                               or lm.get('reduction', 'mean') != 'mean' or lm.get('class_weight') is not None):
+            raise ValueError("loss_mask must describe CrossEntropyLoss(use_sigmoid=True, reduction='mean'), got %r" % (lm,))
+        if ld is not None and (ld.get('type') != 'DiceLoss' or not ld.get('use_sigmoid', True) or not ld.get('activate', True)
+                               or not ld.get('naive_dice', False) or ld.get('reduction', 'mean') != 'mean'):
+            raise ValueError("loss_dice must describe DiceLoss(use_sigmoid=True, activate=True, naive_dice=True, "
+                             "reduction='mean'), got %r" % (ld,))
+        self.cls_loss_weight = _get(lc, 'loss_weight', 1.0)
+        self.mask_loss_weight = _get(lm, 'loss_weight', 1.0)
+        self.dice_loss_weight, self.dice_loss_eps = _get(ld, 'loss_weight', 1.0), _get(ld, 'eps', 1e-3)
+        self.num_points = self.oversample_ratio = self.importance_sample_ratio = self.match_weights = self.dice_cost_eps = None
+        tc = self.train_cfg
+        if not tc:
+            return
+        a = _get(tc, 'assigner') or {}
+        cc = a.get('cls_cost', dict(type='ClassificationCost', weight=1.0))
+        mc, dc = a.get('mask_cost'), a.get('dice_cost', dict(type='DiceCost', weight=1.0))
+        if (a.get('type') != 'MaskHungarianAssigner' or cc.get('type') != 'ClassificationCost' or mc is None
+                or mc.get('type') != 'CrossEntropyLossCost' or not mc.get('use_sigmoid', True) or dc.get('type') != 'DiceCost'
+                or not dc.get('pred_act', False)):
+            raise ValueError('train_cfg.assigner must describe MaskHungarianAssigner(ClassificationCost, CrossEntropyLossCost('
+                             'use_sigmoid=True), DiceCost(pred_act=True)), got %r' % (a,))
+        sampler = _get(tc, 'sampler') or {}
+        if sampler.get('type', 'MaskPseudoSampler') != 'MaskPseudoSampler':
+            raise ValueError('train_cfg.sampler must be a MaskPseudoSampler config, got %r' % (sampler,))
+        self.match_weights = (cc.get('weight', 1.0), mc.get('weight', 1.0), dc.get('weight', 1.0))
+        self.dice_cost_eps = dc.get('eps', 1e-3)
+        self.num_points = tc.get('num_points', 12544)
+        self.oversample_ratio = tc.get('oversample_ratio', 3.0)
+        self.importance_sample_ratio = tc.get('importance_sample_ratio', 0.75)
+        if self.oversample_ratio < 1 or not 0 <= self.importance_sample_ratio <= 1 or self.num_points < 1:
+            raise ValueError('train_cfg: num_points >= 1, oversample_ratio >= 1 and 0 <= importance_sample_ratio <= 1')
+
+    def _draw(self, kind, layer, image, shape, device):
+        """Every random draw of ``loss``: ``kind`` is 'match' (the matching points of decoder output ``layer`` and image
+        ``image``, :234), 'oversample' or 'random' (the two draws of get_uncertain_point_coords_with_randomness for decoder
+        output ``layer``, point_sample.py:61 and :84; ``image`` is None).  Uniform on [0, 1), as the reference's torch.rand.
+        Tests replace this method to replay recorded points."""
+        return torch.rand(shape, device=device)
+
+    def _gt_groups(self, gt_masks_list, device):
+        """the ground-truth masks as ([(masks (G, H, W) uint8, image index per mask, first global gt index)], counts): one
+        group when every image's masks share a size (the usual case: one concatenation per step), else one group per image"""
+        masks = [m if isinstance(m, torch.Tensor) else torch.as_tensor(m.to_ndarray() if hasattr(m, 'to_ndarray') else m)
+                 for m in gt_masks_list]
+        masks = [(m if m.dtype in (torch.uint8, torch.bool) else (m != 0)).to(device) for m in masks]
+        masks = [m.view(torch.uint8) if m.dtype == torch.bool else m for m in masks]
+        counts = [int(m.shape[0]) for m in masks]
+        image_of = [torch.full((c,), n, dtype=torch.int32, device=device) for n, c in enumerate(counts)]
+        if len({tuple(m.shape[1:]) for m in masks}) == 1:
+            return [(torch.cat(masks, 0), torch.cat(image_of), 0)], counts
+        firsts = [sum(counts[:n]) for n in range(len(counts))]
+        return [(m, i, f) for m, i, f in zip(masks, image_of, firsts)], counts
+
+    def loss(self, all_cls_scores, all_mask_preds, gt_labels_list, gt_masks_list, img_metas):
+        """The reference's ``loss`` (:360-402 over ``loss_single`` :269-358 and ``_get_target_single`` :199-267):
+        all_cls_scores / all_mask_preds per decoder output (N, Q, classes + 1) / (N, Q, h, w); gt_labels_list / gt_masks_list
+        per image (G_n,) / (G_n, H, W), masks 0 / 1.  -> {'loss_cls', 'loss_mask', 'loss_dice', 'd<i>.loss_*'}: the last
+        output's losses under the plain names.  One host synchronisation (see the module docstring).  ``last_assignment``
+        ([output][image] -> (queries, gts)) and ``last_points`` ([output] -> (K, P, 2) or None) keep what the step chose."""
+        if self.num_points is None or None in (self.loss_cls, self.loss_mask, self.loss_dice):
+            raise ValueError('loss needs train_cfg (num_points, ratios, assigner) and the loss_cls / loss_mask / loss_dice configs')
+        cls = [c.float() for c in all_cls_scores]                     # force_fp32
+        preds = [m.float() for m in all_mask_preds]
+        L = len(cls)
+        N, Q, h, w = preds[0].shape
+        dev = preds[0].device
+        P = self.num_points
+        groups, counts = self._gt_groups(gt_masks_list, dev)
+        G_total = sum(counts)
+        labels_all = torch.cat([torch.as_tensor(lab).to(dev).long().reshape(-1) for lab in gt_labels_list])
+        class_weight = cls[0].new_tensor(self.class_weight) if self.class_weight is not None else None
+
+        # 1. matching: points, sampled predictions and costs of every decoder output, then one trip to the host
+        none = torch.zeros(0, dtype=torch.long)
+        assign = [[(none, none) for _ in range(N)] for _ in range(L)]
+        if G_total > 0:
+            offsets = torch.tensor([sum(counts[:n]) for n in range(N + 1)], dtype=torch.int32, device=dev)
+            image_of_query = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(Q)
+            costs = []
+            with torch.no_grad():
+                for i in range(L):
+                    pts = torch.cat([self._draw('match', i, n, (1, P, 2), dev) for n in range(N)], 0)
+                    xs = fused.point_sample(preds[i].flatten(0, 1), pts, set_idx=image_of_query)
+                    ts = torch.cat([fused.point_sample(m, pts, set_idx=image_of) for m, image_of, _ in groups if m.shape[0]], 0)
+                    costs.append(fused.match_costs(xs, ts, cls[i], labels_all, counts, self.match_weights, self.dice_cost_eps,
+                                                   gt_offsets=offsets))
+                host = torch.stack(costs).cpu().numpy()                 # the step's one synchronisation
+            try:
+                from scipy.optimize import linear_sum_assignment
+            except ImportError:
+                raise ImportError('Please run "pip install scipy" to install scipy first.') from None
+            for i in range(L):
+                for n in range(N):
+                    if counts[n]:
+                        r, c = linear_sum_assignment(host[i, n, :, :counts[n]])
+                        order = r.argsort(kind='stable')                # MaskPseudoSampler: positives in query order
+                        assign[i][n] = (torch.from_numpy(r[order]).long(), torch.from_numpy(c[order]).long())
+        self.last_assignment = assign
+        K = sum(a[0].numel() for a in assign[0])
+        firsts = [sum(counts[:n]) for n in range(N)]
+        table = torch.stack([torch.stack([torch.cat([a[0] + n * Q for n, a in enumerate(assign[i])]),
+                                          torch.cat([a[1] + firsts[n] for n, a in enumerate(assign[i])])]) for i in range(L)])
+        table = table.to(dev)                                           # (L, 2, K): query row, global gt index; one copy
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            total = cls[0].new_tensor([float(K)]) / torch.distributed.get_world_size()
+            torch.distributed.all_reduce(total)
+            num_total_masks = total.clamp(min=1)[0]
+        else:
+            num_total_masks = max(float(K), 1.0)
+
+        # 2. the losses of each decoder output
+        self.last_points = []
+        losses = []
+        for i in range(L):
+            rows, tgts = table[i, 0], table[i, 1]
+            target = torch.full((N * Q,), self.num_classes, dtype=torch.long, device=dev)
+            target[rows] = labels_all[tgts]
+            ce = F.cross_entropy(cls[i].flatten(0, 1), target, weight=class_weight, reduction='none')
+            avg = class_weight[target].sum() if class_weight is not None else float(N * Q)
+            loss_cls = self.cls_loss_weight * (ce.sum() / avg)
+            if K == 0:
+                zero = preds[i].flatten(0, 1)[:0].sum()                 # :327-331
+                self.last_points.append(None)
+                losses.append((loss_cls, zero, zero))
+                continue
+            with torch.no_grad():                                       # point_sample.py:32-87
+                n_over = int(P * self.oversample_ratio)
+                n_unc = int(self.importance_sample_ratio * P)
+                over = self._draw('oversample', i, None, (K, n_over, 2), dev)
+                logits = fused.point_sample(preds[i].flatten(0, 1), over, map_idx=rows)
+                idx = torch.topk(-logits.abs(), k=n_unc, dim=1)[1]
+                points = torch.gather(over, 1, idx[:, :, None].expand(-1, -1, 2))
+                if P - n_unc > 0:
+                    points = torch.cat((points, self._draw('random', i, None, (K, P - n_unc, 2), dev)), 1)
+            self.last_points.append(points)
+            bce, dice = [], []
+            for m, _, first in groups:
+                if len(groups) == 1:
+                    b, d = fused.point_mask_losses(preds[i], rows, m, tgts, points, self.dice_loss_eps)
+                else:
+                    # images of different mask sizes: one call per image; the boolean index synchronises
+                    sel = (tgts >= first) & (tgts < first + m.shape[0])
+                    if m.shape[0] == 0 or not bool(sel.any()):
+                        continue
+                    b, d = fused.point_mask_losses(preds[i], rows[sel], m, tgts[sel] - first, points[sel], self.dice_loss_eps)
+                bce.append(b)
+                dice.append(d)
+            loss_mask = self.mask_loss_weight * (torch.cat(bce).sum() / (num_total_masks * P))
+            loss_dice = self.dice_loss_weight * (torch.cat(dice).sum() / num_total_masks)
+            losses.append((loss_cls, loss_mask, loss_dice))
+        out = dict(loss_cls=losses[-1][0], loss_mask=losses[-1][1], loss_dice=losses[-1][2])
+        for i, (lc, lm, ld) in enumerate(losses[:-1]):
+            out['d%d.loss_cls' % i], out['d%d.loss_mask' % i], out['d%d.loss_dice' % i] = lc, lm, ld
+        return out
+
+    def forward_train(self, x, img_metas, gt_semantic_seg, gt_labels, gt_masks):
+        """:527-555: the loss dict of a training step; ``gt_semantic_seg`` is not used, as in the reference"""
+        all_cls_scores, all_mask_preds = self(x, img_metas)
+        return self.loss(all_cls_scores, all_mask_preds, gt_labels, gt_masks, img_metas)
+
+    def forward_test(self, inputs, img_metas, test_cfg):
+        """:557-579: semantic logits (N, classes, h, w) of the last decoder output, in fp32.  The reference also reads
+        ``img_metas[0]['ori_shape']`` into two names it never uses (and so raises without metas); that read is left out."""
+        all_cls_scores, all_mask_preds = self(inputs, img_metas)
+        return self.semantic_inference(all_cls_scores[-1], all_mask_preds[-1])
+
+    @staticmethod
+    def semantic_inference(cls_score, mask_pred):
+        """``einsum('bqc,bqhw->bchw', softmax(cls_score)[..., :-1], sigmoid(mask_pred))`` as one matmul, in fp32"""
+        with torch.autocast(mask_pred.device.type, enabled=False):
+            N, Q, h, w = mask_pred.shape
+            prob = F.softmax(cls_score.float(), dim=-1)[..., :-1]
+            return torch.matmul(prob.transpose(1, 2), mask_pred.float().sigmoid().flatten(2)).view(N, -1, h, w)
