@@ -236,6 +236,19 @@ for _name, (_res, _args) in POINTS_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_seg.h declares (the logit tail of the Mask2Former
+# segmentor, csrc/seg_logits.hip).  An fp32 NCHW operand is (pointer, image stride, plane stride, row stride), a label map
+# (pointer, image stride, row stride).  tests/test_seg_logits_abi_cpu.py holds each entry to its prototype.
+_pl = [_p, _i64, _i64, _i64]
+SEG_SIGNATURES = {
+    'vah_seg_resize_add': (_int, _pl + [_i64, _i64, _i64, _i64, _i64, _i64, _int] + _pl + [_i64, _i64, _i64, _i64, _int, _p]),
+    'vah_seg_finish': (_int, _pl + [_i64, _i64, _i64, _i64, _p, _p, _int, _i64, _i64, _int, _int] + _pl + [_int, _p, _i64, _i64, _p]),
+    'vah_seg_argmax': (_int, _pl + [_i64, _i64, _i64, _i64, _f, _p, _i64, _i64, _p]),
+}
+for _name, (_res, _args) in SEG_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

@@ -22,44 +22,12 @@
 #include "../../include/vitadapter_hip_resize.h"
 #include "common.h"
 #include "elem16.h"
+#include "resize_tap.h"           // Tap, Axis, tap_of(), axis_of(): shared with seg_logits.hip
 
 namespace vah {
 namespace {
 
 constexpr int kRsBlocks = 2048;         // per call
-
-struct Tap {
-    int i0, i1;
-    float l1, l0;
-};
-
-struct Axis {
-    int in, out;
-    float scale;
-    int align;
-};
-
-// a product that stays a value of its own: HIP's __fmul_rn / __fadd_rn are plain * and + inside the header and
-// `#pragma clang fp contract(off)` is not honoured under -ffp-contract=fast - either way the ISA showed v_fma_f32 for
-// scale * (dst + 0.5) - 0.5.  An empty asm that "rewrites" the register keeps the multiply apart from what consumes it.
-__device__ __forceinline__ float mul_rn(float a, float b) {
-    float p = a * b;
-    asm("" : "+v"(p));
-    return p;
-}
-
-// torch's area_pixel_compute_source_index + guard_index_and_lambda; every operation of src rounded on its own, so that a
-// restatement in fp32 gets the same indices and fractions whatever the contraction mode
-__device__ __forceinline__ Tap tap_of(const Axis a, int dst) {
-    const float d = (float)dst;
-    const float src = a.align ? mul_rn(a.scale, d) : fmaxf(mul_rn(a.scale, d + 0.5f) - 0.5f, 0.f);
-    Tap t;
-    t.i0 = min((int)src, a.in - 1);
-    t.i1 = t.i0 + (t.i0 < a.in - 1 ? 1 : 0);
-    t.l1 = fminf(fmaxf(src - (float)t.i0, 0.f), 1.f);
-    t.l0 = 1.f - t.l1;
-    return t;
-}
 
 // the weight with which the output position of tap t reads input position i (0 if it does not)
 __device__ __forceinline__ float weight_of(const Tap t, int i) { return (t.i0 == i ? t.l0 : 0.f) + (t.i1 == i ? t.l1 : 0.f); }
@@ -189,13 +157,6 @@ __global__ __launch_bounds__(256) void resize_rows_bwd_kernel(const TD *__restri
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-Axis axis_of(int64_t in, int64_t out, int align) {
-    Axis a;
-    a.in = (int)in, a.out = (int)out, a.align = align ? 1 : 0;
-    a.scale = align ? (out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f) : (float)in / (float)out;
-    return a;
-}
-
 int64_t rs_ws_bytes(int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo) {
     return (Ho + Wo) * (int64_t)sizeof(Tap) + (Hi + Wi) * (int64_t)sizeof(int2);
 }

@@ -27,6 +27,8 @@ masked_cross_attention (csrc/masked_attn.hip, ENABLED['masked_attn']) is the cro
 the mask packed to one bit per (image, query, key) by a sign test, heads of 32 channels, bf16 or fp16 autocast.
 point_sample and match_costs (csrc/point_loss.hip, ENABLED['point_loss']) are mmcv's point_sample without a gradient and the costs
 of MaskHungarianAssigner of Mask2Former's training head, in fp32; point_mask_losses, the sampled BCE / dice, is a torch expression.
+seg_resize_add, seg_finish and seg_argmax (csrc/seg_logits.hip, ENABLED['seg_logits']) are the logit tail of the Mask2Former segmentor
+(vitadapter/segmentor.py): window upsample-and-add, then count division, rescale, softmax, flip, view sum and argmax, fp32 NCHW.
 """
 import math
 import os
@@ -44,7 +46,8 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'group_norm': True,
            'bilinear_rows': True,
            'masked_attn': True,
-           'point_loss': True}
+           'point_loss': True,
+           'seg_logits': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -2065,3 +2068,121 @@ def point_mask_losses(mask_pred, rows, targets, tgt_rows, points, eps=1.0):
     s = x.sigmoid()
     dice = 1 - (2 * (s * t).sum(1) + eps) / (s.sum(1) + t.sum(1) + eps)
     return bce, dice
+
+
+_SEG_FLIPS = {None: 0, False: 0, 'horizontal': 1, 'vertical': 2}
+
+
+def _seg_on(t):
+    return ENABLED['seg_logits'] and t.is_cuda and t.dtype == torch.float32
+
+
+def _seg_planes(t):
+    """(N, C, H, W) fp32 as the segmentor kernels read it: column stride 1, planes that do not overlap"""
+    N, C, H, W = t.shape
+    si, sp, sr, sc = t.stride()
+    plane = (H - 1) * sr + W
+    if sc != 1 or sr < W or sp < plane or si < (C - 1) * sp + plane:
+        t = t.contiguous()
+    return t
+
+
+def seg_resize_add(src, dst, y0, x0, size, align_corners=False, accumulate=True):
+    """``dst[:, :, y0:y0 + Hc, x0:x0 + Wc] (= | +=) resize(src, size=(Hc, Wc), mode='bilinear', align_corners=...)`` in place,
+    -> dst: the ``resize`` of the reference's encode_decode (encoder_decoder_mask2former.py:75-79) and the
+    ``preds += F.pad(crop_seg_logit, ...)`` of its slide_inference (:181-183) without the upsampled or the padded tensor.
+    src (N, C, hs, ws), dst (N, C, Hd, Wd).  On the GPU in fp32 with ENABLED['seg_logits'] this is vah_seg_resize_add;
+    otherwise the reference's expression."""
+    Hc, Wc = int(size[0]), int(size[1])
+    y0, x0 = int(y0), int(x0)
+    N, C, Hd, Wd = dst.shape
+    if y0 < 0 or x0 < 0 or y0 + Hc > Hd or x0 + Wc > Wd or src.shape[:2] != dst.shape[:2]:
+        raise ValueError('seg_resize_add: a %d x %d window at (%d, %d) of %s from %s' % (Hc, Wc, y0, x0, tuple(dst.shape),
+                                                                                        tuple(src.shape)))
+    if _seg_on(dst) and _seg_on(src) and dst.stride(3) == 1 and dst.stride(2) >= Wd:
+        src = _seg_planes(src.detach())
+        with _vah.on(dst.device):
+            _vah.check(_vah.lib.vah_seg_resize_add(src.data_ptr(), src.stride(0), src.stride(1), src.stride(2), N, C, src.shape[2],
+                                                   src.shape[3], Hc, Wc, 1 if align_corners else 0, dst.data_ptr(), dst.stride(0),
+                                                   dst.stride(1), dst.stride(2), Hd, Wd, y0, x0, 1 if accumulate else 0,
+                                                   _stream(dst)), 'vah_seg_resize_add')
+        return dst
+    up = F.interpolate(src, size=(Hc, Wc), mode='bilinear', align_corners=align_corners).to(dst.dtype)
+    if accumulate:
+        dst += F.pad(up, (x0, Wd - x0 - Wc, y0, Hd - y0 - Hc))
+    else:
+        dst[:, :, y0:y0 + Hc, x0:x0 + Wc] = up
+    return dst
+
+
+def seg_finish(acc, counts=None, region=None, size=None, align_corners=False, flip=None, out=None, accumulate=False, prob=True,
+               labels=False):
+    """The rest of one view of the reference's slide_inference / whole_inference / inference / simple_test
+    (encoder_decoder_mask2former[_aug].py:191-258): ``acc / count_mat`` with count_mat = counts[0][:, None] * counts[1][None, :]
+    (int32 vectors; None: no division), the crop to ``region`` = (Hs, Ws) (the Aug class's un-padding; None: all of acc),
+    ``resize(..., size=size)`` (None: no resize), softmax over the classes, the flip ('horizontal', 'vertical' or None).
+    -> (probabilities or None, labels or None): with ``prob`` the (N, C, Ho, Wo) softmax output - stored into / with
+    ``accumulate`` added to ``out`` if that is given - and with ``labels`` its argmax(1), (N, Ho, Wo) int64.  Nothing that is
+    not returned is formed.  On the GPU in fp32 with ENABLED['seg_logits'] this is vah_seg_finish, one launch; otherwise the
+    reference's expression."""
+    N, C, H, W = acc.shape
+    Hs, Ws = (H, W) if region is None else (int(region[0]), int(region[1]))
+    Ho, Wo = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+    if flip not in _SEG_FLIPS:
+        raise ValueError("seg_finish: flip is None, 'horizontal' or 'vertical', not %r" % (flip,))
+    if Hs > H or Ws > W or (out is not None and tuple(out.shape) != (N, C, Ho, Wo)):
+        raise ValueError('seg_finish: region %s of %s, out %s' % ((Hs, Ws), tuple(acc.shape), None if out is None else tuple(out.shape)))
+    if _seg_on(acc) and (out is None or (_seg_on(out) and out.is_contiguous())) and N * C * Ho * Wo > 0:
+        acc = _seg_planes(acc.detach())
+        dev = acc.device
+        cy, cx = (None, None) if counts is None else (c.to(device=dev, dtype=torch.int32).contiguous() for c in counts)
+        p = None
+        if prob:
+            p = out if out is not None else torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=dev)
+        lab = torch.empty((N, Ho, Wo), dtype=torch.int64, device=dev) if labels else None
+        if p is None and lab is None:
+            return None, None
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_seg_finish(acc.data_ptr(), acc.stride(0), acc.stride(1), acc.stride(2), N, C, Hs, Ws,
+                                               None if cy is None else cy.data_ptr(), None if cx is None else cx.data_ptr(),
+                                               0 if size is None else 1, Ho, Wo, 1 if align_corners else 0, _SEG_FLIPS[flip],
+                                               None if p is None else p.data_ptr(), C * Ho * Wo, Ho * Wo, Wo,
+                                               1 if (accumulate and out is not None) else 0,
+                                               None if lab is None else lab.data_ptr(), Ho * Wo, Wo, _stream(acc)), 'vah_seg_finish')
+        return p, lab
+    v = acc
+    if counts is not None:
+        count_mat = (counts[0].to(acc.device)[:, None] * counts[1].to(acc.device)[None, :]).to(acc.dtype)
+        v = v / count_mat
+    v = v[:, :, :Hs, :Ws]
+    if size is not None:
+        v = F.interpolate(v, size=(Ho, Wo), mode='bilinear', align_corners=align_corners)
+    p = F.softmax(v, dim=1)
+    if flip == 'horizontal':
+        p = p.flip(dims=(3,))
+    elif flip == 'vertical':
+        p = p.flip(dims=(2,))
+    lab = p.argmax(dim=1) if labels else None
+    if not prob:
+        return None, lab
+    if out is not None:
+        if accumulate:
+            out += p
+        else:
+            out.copy_(p)
+        p = out
+    return p, lab
+
+
+def seg_argmax(total, divisor=1):
+    """``(total / divisor).argmax(dim=1)``: the last lines of the reference's aug_test (encoder_decoder_mask2former.py:280-281),
+    (N, C, H, W) -> (N, H, W) int64, without the quotient.  On the GPU in fp32 with ENABLED['seg_logits'] this is vah_seg_argmax."""
+    N, C, H, W = total.shape
+    if _seg_on(total) and total.numel() > 0:
+        total = _seg_planes(total.detach())
+        lab = torch.empty((N, H, W), dtype=torch.int64, device=total.device)
+        with _vah.on(total.device):
+            _vah.check(_vah.lib.vah_seg_argmax(total.data_ptr(), total.stride(0), total.stride(1), total.stride(2), N, C, H, W,
+                                               float(divisor), lab.data_ptr(), H * W, W, _stream(total)), 'vah_seg_argmax')
+        return lab
+    return (total / divisor).argmax(dim=1)
