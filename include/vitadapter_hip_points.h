@@ -7,7 +7,7 @@
  * Replaces, in the reference's Mask2FormerHead.loss (segmentation/mmseg_custom/models/decode_heads/mask2former_head.py:154-402),
  * mmcv's point_sample where it needs no gradient (matching, ground truth, the oversample step) and the three match costs of
  * MaskHungarianAssigner (models/losses/match_costs.py).  The sampled BCE and dice of the matched masks and their backward into
- * mask_pred are not part of this header: they are torch's in vitadapter/fused.py.
+ * mask_pred are not part of this header: they are vitadapter_hip_point_mask_loss.h's, from the same sampling function.
  *
  * All math is fp32 with the accurate expf / log1pf.  No atomics, no counters or flags between workgroups, nothing read back
  * to the host: launches are ordered by kernel boundaries on the stream only, and the same inputs give the same bits.

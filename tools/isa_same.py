@@ -5,7 +5,8 @@
 
 Each file of the revision and of the working tree is compiled with the flags of vit-adapter_amd/build.py plus
 --offload-device-only -S; the lines naming the source file (.file), the compiler (.ident) and the hash symbol of the
-compilation unit (__hip_cuid_) are dropped and the two texts compared as a whole.  Exit status 1 if any file differs.
+compilation unit (__hip_cuid_) are dropped and the two texts compared as a whole.  Exit status 1 if any file differs; a file
+that only one side has is listed as such and counts as different.
 """
 import concurrent.futures
 import hashlib
@@ -22,6 +23,8 @@ EXTRA = ['--offload-device-only', '-S']
 
 
 def asm_sha(src):
+    if not os.path.exists(src):
+        return '-' * 64                                  # a file only one side has (added or removed since the revision)
     cmd = [HIPCC] + FLAGS + PER_FILE_FLAGS.get(os.path.basename(src), []) + EXTRA + [os.path.basename(src), '-o', '-']
     text = subprocess.run(cmd, cwd=os.path.dirname(src), check=True, capture_output=True, text=True).stdout
     kept = [ln for ln in text.split('\n') if not ln.lstrip().startswith(('.file', '.ident')) and '__hip_cuid_' not in ln]
@@ -42,7 +45,9 @@ def main():
     print('# added per file: %s' % ', '.join('%s %s' % (f, ' '.join(PER_FILE_FLAGS[f])) for f in sorted(PER_FILE_FLAGS)))
     print('# file, SHA-256 of the filtered assembly at %s, SHA-256 of this tree\'s' % rev)
     for i, n in enumerate(names):
-        print('%-18s %s %s %s' % (n, shas[2 * i], shas[2 * i + 1], 'same' if shas[2 * i] == shas[2 * i + 1] else 'DIFFERENT'))
+        one_side = '-' * 64 in shas[2 * i:2 * i + 2]
+        print('%-18s %s %s %s' % (n, shas[2 * i], shas[2 * i + 1],
+                                  'ONE SIDE ONLY' if one_side else 'same' if shas[2 * i] == shas[2 * i + 1] else 'DIFFERENT'))
     return int(any(shas[2 * i] != shas[2 * i + 1] for i in range(len(names))))
 
 

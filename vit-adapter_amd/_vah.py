@@ -236,6 +236,20 @@ for _name, (_res, _args) in POINTS_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_point_mask_loss.h declares (the sampled BCE / dice
+# of the matched masks of Mask2Former's training head and their backward, csrc/point_mask_loss.hip).  A map operand is
+# (pointer[, dtype code], map stride, row stride, maps, height, width).  tests/test_point_mask_loss_abi_cpu.py holds each
+# entry to its prototype.
+PML_SIGNATURES = {
+    'vah_pml_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'vah_pml_forward': (_int, [_p, _i64, _i64, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _f,
+                               _p, _p, _p, _p, _p, _p, _i64, _p]),
+    'vah_pml_backward': (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f, _p, _p, _i64, _p]),
+}
+for _name, (_res, _args) in PML_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 # name -> (restype, argtypes) of every entry point include/vitadapter_hip_seg.h declares (the logit tail of the Mask2Former
 # segmentor, csrc/seg_logits.hip).  An fp32 NCHW operand is (pointer, image stride, plane stride, row stride), a label map
 # (pointer, image stride, row stride).  tests/test_seg_logits_abi_cpu.py holds each entry to its prototype.

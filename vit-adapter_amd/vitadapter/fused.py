@@ -26,7 +26,8 @@ rows, with a gather-form adjoint that has no atomics: the upsample of the pixel 
 masked_cross_attention (csrc/masked_attn.hip, ENABLED['masked_attn']) is the cross-attention of Mask2Former's query decoder:
 the mask packed to one bit per (image, query, key) by a sign test, heads of 32 channels, bf16 or fp16 autocast.
 point_sample and match_costs (csrc/point_loss.hip, ENABLED['point_loss']) are mmcv's point_sample without a gradient and the costs
-of MaskHungarianAssigner of Mask2Former's training head, in fp32; point_mask_losses, the sampled BCE / dice, is a torch expression.
+of MaskHungarianAssigner of Mask2Former's training head, in fp32; point_mask_losses (csrc/point_mask_loss.hip,
+ENABLED['point_mask_loss'] and ENABLED['point_loss']) is the sampled BCE / dice of the matched masks with an ordered backward into mask_pred.
 seg_resize_add, seg_finish and seg_argmax (csrc/seg_logits.hip, ENABLED['seg_logits']) are the logit tail of the Mask2Former segmentor
 (vitadapter/segmentor.py): window upsample-and-add, then count division, rescale, softmax, flip, view sum and argmax, fp32 NCHW.
 """
@@ -47,6 +48,7 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'bilinear_rows': True,
            'masked_attn': True,
            'point_loss': True,
+           'point_mask_loss': True,   # needs point_loss as well: the sampled BCE / dice of the matched masks on kernels
            'seg_logits': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
@@ -2047,21 +2049,81 @@ def match_costs(xs, ts, cls_scores, labels, gt_counts, weights, eps=1.0, gt_offs
     return cost
 
 
+class _PointMaskLosses(torch.autograd.Function):
+    """point_mask_losses on vah_pml_forward / vah_pml_backward: mask_pred (N, Q, h, w) fp32 on the GPU, rows / tgt_rows int32
+    (K,), targets as _pts_maps gives them, points (K, P, 2) fp32 contiguous.  Gradient into mask_pred only."""
+
+    @staticmethod
+    def forward(ctx, mask_pred, rows, targets, tgt_rows, points, eps):
+        dev = mask_pred.device
+        pred = mask_pred.detach().flatten(0, 1)
+        if pred.stride(2) != 1 or pred.stride(0) < 0 or pred.stride(1) < pred.shape[2]:
+            pred = pred.contiguous()
+        Mp, h, w = pred.shape
+        Mt, H, W = targets.shape
+        K, P, _ = points.shape
+        rows, tgt_rows = rows.contiguous(), tgt_rows.contiguous()
+        nbytes = _vah.lib.vah_pml_ws_bytes(K, P, h, w)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        bce, dice = torch.empty((K,), dtype=torch.float32, device=dev), torch.empty((K,), dtype=torch.float32, device=dev)
+        xs, ts = torch.empty((K, P), dtype=torch.float32, device=dev), torch.empty((K, P), dtype=torch.float32, device=dev)
+        sums = torch.empty((K, 4), dtype=torch.float32, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_pml_forward(pred.data_ptr(), pred.stride(0), pred.stride(1), Mp, h, w, targets.data_ptr(),
+                                                _PTS_CODES[targets.dtype], targets.stride(0), targets.stride(1), Mt, H, W,
+                                                points.data_ptr(), P, rows.data_ptr(), tgt_rows.data_ptr(), K, eps, bce.data_ptr(),
+                                                dice.data_ptr(), xs.data_ptr(), ts.data_ptr(), sums.data_ptr(), ws.data_ptr(), nbytes,
+                                                _stream(pred)), 'vah_pml_forward')
+        ctx.save_for_backward(points, xs, ts, sums, rows)
+        ctx.shape, ctx.eps, ctx.nbytes = tuple(mask_pred.shape), eps, nbytes
+        return bce, dice
+
+    @staticmethod
+    def backward(ctx, g_bce, g_dice):
+        points, xs, ts, sums, rows = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        dev = points.device
+        N, Q, h, w = ctx.shape
+        K, P, _ = points.shape
+        g_bce = (torch.zeros_like(xs[:, 0]) if g_bce is None else g_bce.float()).contiguous()
+        g_dice = (torch.zeros_like(xs[:, 0]) if g_dice is None else g_dice.float()).contiguous()
+        ws = torch.empty((ctx.nbytes,), dtype=torch.uint8, device=dev)
+        dmaps = torch.empty((K, h, w), dtype=torch.float32, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_pml_backward(points.data_ptr(), xs.data_ptr(), ts.data_ptr(), sums.data_ptr(), g_bce.data_ptr(),
+                                                 g_dice.data_ptr(), K, P, h, w, ctx.eps, dmaps.data_ptr(), ws.data_ptr(), ctx.nbytes,
+                                                 _stream(points)), 'vah_pml_backward')
+        grad = torch.zeros((N * Q, h, w), dtype=torch.float32, device=dev)
+        grad.index_put_((rows.long(),), dmaps, accumulate=True)
+        return grad.view(N, Q, h, w), None, None, None, None, None
+
+
 def point_mask_losses(mask_pred, rows, targets, tgt_rows, points, eps=1.0):
     """The mask losses of K matched queries before their reduction (the reference's mask2former_head.py:338-356 with
     CrossEntropyLoss(use_sigmoid=True) and DiceLoss(naive_dice=True)): row k samples ``mask_pred.flatten(0, 1)[rows[k]]``
     ((N, Q, h, w) logits, differentiable) and ``targets[tgt_rows[k]]`` ((Mt, H, W) masks, fp32 / uint8 / bool at their own
     resolution) at ``points[k]`` ((K, P, 2), as in point_sample) and returns
         bce_sum (K,) = sum_p binary_cross_entropy_with_logits(x, t),   dice (K,) = 1 - (2 sum s t + eps) / (sum s + sum t + eps)
-    with s = sigmoid(x).  The targets are sampled by point_sample (no gradient, no float copy of the masks on the kernel
-    path); the predictions, the two losses and their backward are torch's: F.grid_sample, whose backward into mask_pred
-    accumulates with float atomics.  There are no kernels for this part."""
+    with s = sigmoid(x).  Targets and points get no gradient.
+    On the GPU with ENABLED['point_mask_loss'] and ENABLED['point_loss'], for fp32 logits, this is vah_pml_forward /
+    vah_pml_backward (csrc/point_mask_loss.hip): mask_pred is read in place through ``rows``, the masks at their own dtype, and
+    the gradient into mask_pred is an ordered gather, so the same inputs give the same bits (``rows`` may repeat: the rows of
+    the dense (K, h, w) adjoint are added per map by a deterministic index_put_).  Otherwise the targets are sampled by
+    point_sample and the predictions, the two losses and their backward are torch's: F.grid_sample, whose backward into
+    mask_pred accumulates with float atomics."""
     dev = mask_pred.device
     rows_l, tgt_l = torch.as_tensor(rows, device=dev).long(), torch.as_tensor(tgt_rows, device=dev).long()
     points = points.detach().float()
     if rows_l.numel() == 0:
         z = mask_pred.flatten(0, 1)[:0].sum((1, 2)).float()
         return z, z
+    if (ENABLED['point_mask_loss'] and _pts_on(mask_pred) and mask_pred.dtype == torch.float32 and mask_pred.dim() == 4
+            and targets.is_cuda and targets.dim() == 3 and targets.numel() > 0 and points.dim() == 3 and points.shape[1] > 0
+            and targets.dtype in (torch.float32, torch.uint8, torch.bool)
+            and _vah.lib.vah_pml_ws_bytes(rows_l.numel(), points.shape[1], mask_pred.shape[2], mask_pred.shape[3]) > 0):
+        return _PointMaskLosses.apply(mask_pred, rows_l.to(torch.int32), _pts_maps(targets.detach()), tgt_l.to(torch.int32),
+                                      points.contiguous(), float(eps))
     x = _grid_sample_points(mask_pred.flatten(0, 1)[rows_l].float(), points)
     t = point_sample(targets, points, map_idx=tgt_l)
     bce = F.binary_cross_entropy_with_logits(x, t, reduction='none').sum(1)

@@ -35,7 +35,8 @@ Differences from the reference's expression, none in the arithmetic it defines:
     the 'random' draw), their distribution does not;
   * ``max(num_total_masks, 1)`` is a clamp on the device when a process group is initialised and host arithmetic
     otherwise, not a comparison that synchronises.  The sampled BCE and dice of the matched masks
-    (fused.point_mask_losses) are torch's F.grid_sample and formulas, as in the reference: there are no kernels for them.
+    (fused.point_mask_losses) are the kernels of csrc/point_mask_loss.hip on the GPU, with an ordered backward into mask_pred:
+    two backward passes of the same step give the same bits; on the CPU, or with the switch off, torch's F.grid_sample.
 """
 import copy
 import math
