@@ -263,6 +263,19 @@ for _name, (_res, _args) in SEG_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_seg_loss.h declares (the training loss of the
+# UperNet heads, csrc/seg_ce_loss.hip).  The logits are (pointer, dtype code, image stride, plane stride, row stride), the
+# gradient and the label map as above.  tests/test_seg_ce_loss_abi_cpu.py holds each entry to its prototype.
+_sce = [_p, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int, _i64, _p]
+SCE_SIGNATURES = {
+    'vah_sce_ws_bytes': (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    'vah_sce_forward': (_int, _sce + [_p, _p, _p, _p, _i64, _p]),
+    'vah_sce_backward': (_int, _sce + [_p, _p] + _pl + [_p, _i64, _p]),
+}
+for _name, (_res, _args) in SCE_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

@@ -22,28 +22,12 @@
 #include "../../include/vitadapter_hip_resize.h"
 #include "common.h"
 #include "elem16.h"
-#include "resize_tap.h"           // Tap, Axis, tap_of(), axis_of(): shared with seg_logits.hip
+#include "resize_tap.h"           // Tap, Axis, tap_of(), axis_of(), weight_of(), bisect(): shared with seg_logits.hip, seg_ce_loss.hip
 
 namespace vah {
 namespace {
 
 constexpr int kRsBlocks = 2048;         // per call
-
-// the weight with which the output position of tap t reads input position i (0 if it does not)
-__device__ __forceinline__ float weight_of(const Tap t, int i) { return (t.i0 == i ? t.l0 : 0.f) + (t.i1 == i ? t.l1 : 0.f); }
-
-// first output position in [0, out] whose i1 (UPPER = false) reaches i / whose i0 (UPPER = true) exceeds i
-template <bool UPPER>
-__device__ __forceinline__ int bisect(const Axis a, int i) {
-    int lo = 0, hi = a.out;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const Tap t = tap_of(a, mid);
-        if (UPPER ? t.i0 > i : t.i1 >= i) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
 
 // workspace: Tap ty[Ho], Tap tx[Wo], int2 ry[Hi], int2 rx[Wi]
 struct Tables {

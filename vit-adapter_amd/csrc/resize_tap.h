@@ -1,6 +1,7 @@
 // The bilinear tap rule of include/vitadapter_hip_resize.h, shared by the kernels that resize: csrc/resize_rows.hip
-// (channels-last rows) and csrc/seg_logits.hip (NCHW logit planes).  One function, so that every resize in the library
-// gets the same indices and fractions as torch's upsample_bilinear2d for size= (no scale factor).
+// (channels-last rows), csrc/seg_logits.hip (NCHW logit planes) and csrc/seg_ce_loss.hip (the loss on resized logits).
+// One function, so that every resize in the library gets the same indices and fractions as torch's
+// upsample_bilinear2d for size= (no scale factor).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -51,6 +52,23 @@ __device__ __forceinline__ float blend_rn(const Tap ty, const Tap tx, float v00,
     asm("" : "+v"(r0));
     asm("" : "+v"(r1));
     return mul_rn(ty.l0, r0) + mul_rn(ty.l1, r1);
+}
+
+// the weight with which the output position of tap t reads input position i (0 if it does not)
+__device__ __forceinline__ float weight_of(const Tap t, int i) { return (t.i0 == i ? t.l0 : 0.f) + (t.i1 == i ? t.l1 : 0.f); }
+
+// first output position in [0, out] whose i1 (UPPER = false) reaches i / whose i0 (UPPER = true) exceeds i: the tap
+// indices are monotone, so [bisect<false>, bisect<true>) are the output positions whose taps name input position i
+template <bool UPPER>
+__device__ __forceinline__ int bisect(const Axis a, int i) {
+    int lo = 0, hi = a.out;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const Tap t = tap_of(a, mid);
+        if (UPPER ? t.i0 > i : t.i1 >= i) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
 }
 
 inline Axis axis_of(int64_t in, int64_t out, int align) {

@@ -12,9 +12,9 @@ from .backbones import (BEiTAdapter, ViTAdapter, ViTAdapterDet, ViTAdapterSeg, r
 from .mmcv_attention import MultiScaleDeformableAttention, register_attention
 from .pixel_decoder import MSDeformAttnPixelDecoder, register_pixel_decoder
 from .mask2former_head import Mask2FormerHead
-from .segmentor import EncoderDecoderMask2Former, EncoderDecoderMask2FormerAug
+from .segmentor import EncoderDecoder, EncoderDecoderMask2Former, EncoderDecoderMask2FormerAug
 
 __all__ = ['ViTAdapter', 'ViTAdapterSeg', 'ViTAdapterDet', 'register_backbones', 'BEiTAdapter',
            'register_beit_adapter',
            'MultiScaleDeformableAttention', 'register_attention', 'MSDeformAttnPixelDecoder', 'register_pixel_decoder',
-           'Mask2FormerHead', 'EncoderDecoderMask2Former', 'EncoderDecoderMask2FormerAug']
+           'Mask2FormerHead', 'EncoderDecoderMask2Former', 'EncoderDecoderMask2FormerAug', 'EncoderDecoder']

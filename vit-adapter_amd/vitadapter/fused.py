@@ -30,6 +30,8 @@ of MaskHungarianAssigner of Mask2Former's training head, in fp32; point_mask_los
 ENABLED['point_mask_loss'] and ENABLED['point_loss']) is the sampled BCE / dice of the matched masks with an ordered backward into mask_pred.
 seg_resize_add, seg_finish and seg_argmax (csrc/seg_logits.hip, ENABLED['seg_logits']) are the logit tail of the Mask2Former segmentor
 (vitadapter/segmentor.py): window upsample-and-add, then count division, rescale, softmax, flip, view sum and argmax, fp32 NCHW.
+seg_cross_entropy (csrc/seg_ce_loss.hip, ENABLED['seg_ce_loss']) is the training loss of the UperNet heads (vitadapter/heads.py):
+bilinear resize to the label map, cross-entropy with an ignore index and the top-1 count, with an ordered backward into the logits.
 """
 import math
 import os
@@ -49,7 +51,8 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'masked_attn': True,
            'point_loss': True,
            'point_mask_loss': True,   # needs point_loss as well: the sampled BCE / dice of the matched masks on kernels
-           'seg_logits': True}
+           'seg_logits': True,
+           'seg_ce_loss': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -2248,3 +2251,87 @@ def seg_argmax(total, divisor=1):
                                                float(divisor), lab.data_ptr(), H * W, W, _stream(total)), 'vah_seg_argmax')
         return lab
     return (total / divisor).argmax(dim=1)
+
+
+_SCE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+class _SegCrossEntropy(torch.autograd.Function):
+    """seg_cross_entropy on vah_sce_forward / vah_sce_backward: seg_logit (N, C, h, w) fp32 / bf16 / fp16 on the GPU, label
+    (N, H, W) int64, class_weight fp32 (C,) or None.  -> (loss_sum (), counts (2,) int64); gradient into seg_logit only."""
+
+    @staticmethod
+    def forward(ctx, seg_logit, label, align_corners, ignore_index, class_weight):
+        x = _seg_planes(seg_logit.detach())
+        dev = x.device
+        N, C, h, w = x.shape
+        H, W = label.shape[1:]
+        nbytes = _vah.lib.vah_sce_ws_bytes(N, C, h, w, H, W)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        lse = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+        loss_sum = torch.empty((), dtype=torch.float32, device=dev)
+        counts = torch.empty((2,), dtype=torch.int64, device=dev)
+        ctx.head = (x.data_ptr(), _SCE_CODES[x.dtype], x.stride(0), x.stride(1), x.stride(2), N, C, h, w, label.data_ptr(),
+                    label.stride(0), label.stride(1), H, W, 1 if align_corners else 0, int(ignore_index),
+                    None if class_weight is None else class_weight.data_ptr())
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_sce_forward(*ctx.head, lse.data_ptr(), loss_sum.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                                nbytes, _stream(x)), 'vah_sce_forward')
+        ctx.save_for_backward(x, label, lse, class_weight)          # ctx.head's pointers are theirs
+        ctx.nbytes = nbytes
+        ctx.mark_non_differentiable(counts)
+        return loss_sum, counts
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_counts):
+        x, label, lse, class_weight = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        dev = x.device
+        scale = g_loss.detach().to(torch.float32).reshape(()).contiguous()      # stays on the device
+        ws = torch.empty((ctx.nbytes,), dtype=torch.uint8, device=dev)
+        dx = torch.empty(x.shape, dtype=x.dtype, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_sce_backward(*ctx.head, lse.data_ptr(), scale.data_ptr(), dx.data_ptr(), dx.stride(0),
+                                                 dx.stride(1), dx.stride(2), ws.data_ptr(), ctx.nbytes, _stream(x)),
+                       'vah_sce_backward')
+        return dx, None, None, None, None
+
+
+def seg_cross_entropy(seg_logit, seg_label, align_corners=False, ignore_index=255, class_weight=None):
+    """What mmseg's ``BaseDecodeHead.losses`` computes from a head's logits before its reductions: with
+    ``v = resize(seg_logit, size=seg_label.shape[-2:], mode='bilinear', align_corners=...)`` in fp32 (``@force_fp32``),
+        loss_sum  = F.cross_entropy(v, seg_label, weight=class_weight, reduction='none', ignore_index=ignore_index).sum()
+        n_valid   = the pixels whose label is not ``ignore_index``
+        n_correct = the pixels among them whose label is ``v.argmax(1)``
+    (the reference's segmentation/mmseg_custom/models/losses/cross_entropy_loss.py:11-62 and mmseg's ``accuracy``), as device
+    tensors: an fp32 scalar and two int64 scalars.  seg_logit (N, C, h, w), differentiable; seg_label (N, H, W) or (N, 1, H, W)
+    integer; class_weight a (C,) tensor or None.
+    On the GPU with ENABLED['seg_ce_loss'], for fp32 / bf16 / fp16 logits, this is vah_sce_forward / vah_sce_backward
+    (csrc/seg_ce_loss.hip): ``v`` is never formed, one fp32 log-sum-exp per pixel is kept for the backward, and the gradient
+    is an ordered gather in the logits' dtype, so the same inputs give the same bits.  There a label outside [0, C) that is
+    not ``ignore_index`` counts as ignored (torch: a device assert).  Otherwise - switch off, CPU, fp64 - the expression
+    above is evaluated as written.  Runs with autocast disabled."""
+    if seg_label.dim() == 4:
+        seg_label = seg_label.squeeze(1)
+    if seg_logit.dim() != 4 or seg_label.dim() != 3 or seg_label.shape[0] != seg_logit.shape[0]:
+        raise ValueError('seg_cross_entropy: logits %s, labels %s' % (tuple(seg_logit.shape), tuple(seg_label.shape)))
+    with torch.autocast(seg_logit.device.type, enabled=False):
+        if (ENABLED['seg_ce_loss'] and seg_logit.is_cuda and seg_logit.dtype in _SCE_CODES and seg_label.is_cuda
+                and seg_logit.numel() > 0 and seg_label.numel() > 0
+                and _vah.lib.vah_sce_ws_bytes(*seg_logit.shape, *seg_label.shape[1:]) > 0):
+            label = seg_label.detach().long()
+            if label.stride(2) != 1 or label.stride(1) < label.shape[2] or label.stride(0) < (label.shape[1] - 1) * label.stride(1) + label.shape[2]:
+                label = label.contiguous()
+            cw = None
+            if class_weight is not None:
+                cw = torch.as_tensor(class_weight, device=seg_logit.device).detach().float().contiguous()
+            loss_sum, counts = _SegCrossEntropy.apply(seg_logit, label, bool(align_corners), int(ignore_index), cw)
+            return loss_sum, counts[0], counts[1]
+        v = seg_logit if seg_logit.dtype == torch.float64 else seg_logit.float()
+        v = F.interpolate(v, size=seg_label.shape[1:], mode='bilinear', align_corners=align_corners)
+        label = seg_label.long()
+        cw = None if class_weight is None else torch.as_tensor(class_weight, device=v.device).to(v.dtype)
+        loss_sum = F.cross_entropy(v, label, weight=cw, reduction='none', ignore_index=ignore_index).sum()
+        valid = label != ignore_index
+        return loss_sum, valid.sum(), ((v.argmax(dim=1) == label) & valid).sum()

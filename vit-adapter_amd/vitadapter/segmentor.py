@@ -3,8 +3,10 @@
 The two segmentors of the reference's segmentation/mmseg_custom/models/segmentors/encoder_decoder_mask2former.py and
 encoder_decoder_mask2former_aug.py (cited by line below; the second file differs from the first in one place, the
 un-padding of slide_inference, :193-196 there), with the reference's method names, signatures and results.  mmseg's
-builders are not part of this project, so the constructor takes built modules instead of config dicts, and there is no
-auxiliary head (no ViT-Adapter Mask2Former config has one).
+builders are not part of this project, so the constructor takes built modules instead of config dicts, and the two
+Mask2Former classes have no auxiliary head (no ViT-Adapter Mask2Former config has one).  ``EncoderDecoder`` is mmseg's
+segmentor of that name as the reference's ``upernet_*`` configs use it - a decode head and auxiliary heads that bring their own
+losses (vitadapter.heads) - on the same inference tail.
 
 What differs from the reference is which tensors exist, not what is computed.  Everything after
 ``decode_head.forward_test`` runs on the three entry points of include/vitadapter_hip_seg.h (vitadapter.fused.seg_resize_add,
@@ -22,7 +24,7 @@ import torch.nn as nn
 
 from . import fused
 
-__all__ = ['EncoderDecoderMask2Former', 'EncoderDecoderMask2FormerAug']
+__all__ = ['EncoderDecoderMask2Former', 'EncoderDecoderMask2FormerAug', 'EncoderDecoder']
 
 
 def _cfg(cfg, name, default=None):
@@ -233,3 +235,31 @@ class EncoderDecoderMask2FormerAug(EncoderDecoderMask2Former):
     before the test pipeline padded it) before the rescale (:193-196)."""
 
     unpad = True
+
+
+class EncoderDecoder(EncoderDecoderMask2Former):
+    """mmseg's ``EncoderDecoder(backbone, decode_head, neck=None, auxiliary_head=None, train_cfg=None, test_cfg=None)`` over
+    built modules: the segmentor of the reference's UperNet configs (``UPerHead`` + auxiliary ``FCNHead``).  Inference -
+    slide / whole, ``simple_test``, ``aug_test`` - is the parent's, unchanged; ``forward_train`` adds the auxiliary heads'
+    loss dicts under mmseg's prefixes: ``aux.`` for one head, ``aux_0.``, ``aux_1.``, ... for a list."""
+
+    def __init__(self, backbone, decode_head, neck=None, auxiliary_head=None, train_cfg=None, test_cfg=None):
+        super().__init__(backbone, decode_head, neck=neck, train_cfg=train_cfg, test_cfg=test_cfg)
+        if auxiliary_head is not None:
+            self.auxiliary_head = nn.ModuleList(auxiliary_head) if isinstance(auxiliary_head, (list, tuple)) else auxiliary_head
+
+    @property
+    def with_auxiliary_head(self):
+        return getattr(self, 'auxiliary_head', None) is not None
+
+    def forward_train(self, img, img_metas, gt_semantic_seg, **kwargs):
+        x = self.extract_feat(img)
+        losses = {'decode.' + k: v for k, v in self.decode_head.forward_train(x, img_metas, gt_semantic_seg, self.train_cfg).items()}
+        if self.with_auxiliary_head:
+            if isinstance(self.auxiliary_head, nn.ModuleList):
+                heads = [('aux_%d.' % i, head) for i, head in enumerate(self.auxiliary_head)]
+            else:
+                heads = [('aux.', self.auxiliary_head)]
+            for prefix, head in heads:
+                losses.update((prefix + k, v) for k, v in head.forward_train(x, img_metas, gt_semantic_seg, self.train_cfg).items())
+        return losses
