@@ -276,6 +276,24 @@ for _name, (_res, _args) in SCE_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_epoch.h declares: the one-launch 16-bit parameter
+# copies of a forward epoch (csrc/epoch_copies.hip), the weight-gradient GEMM whose reduction launch stores through a row map
+# (csrc/gemm.hip; `applied` is a host int the call writes) and the BatchNorm finalize launch that also does the module's
+# bookkeeping (csrc/tail_ops.hip).  tests/test_epoch_abi_cpu.py holds each entry to its prototype.
+_pint = ctypes.POINTER(ctypes.c_int)
+_fin_rowmap = [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _int, _p, _i64, _p, _i64, _i64, _p, _p, _pint, _p]
+EPOCH_SIGNATURES = {
+    'vah_epoch_job_bytes': (_i64, []),
+    'vah_epoch_chunk_elems': (_i64, []),
+    'vah_epoch_copies': (_int, [_p, _i64, _p, _i64, _int, _p, _i64, _p, _i64, _p]),
+    'vah_gemm_bf16_fin_rowmap': (_int, _fin_rowmap),
+    'vah_gemm_f16_fin_rowmap': (_int, _fin_rowmap),
+    'vah_bn_finalize_stats_book': (_int, [_p, _i64, _f, _f, _f, _p, _p, _p, _p, _p, _p]),
+}
+for _name, (_res, _args) in EPOCH_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/vitadapter_hip.h"
+#include "../../include/vitadapter_hip_epoch.h"
 #include "common.h"
 
 namespace vah {
@@ -116,7 +117,8 @@ struct Call {
     const float *fin_part = nullptr;
     int fin_nparts = 0, fin_C = 0;
     float *fin_out = nullptr;
-    const float *ref = nullptr;      // tuning: the reference product (M x N fp32) every candidate is held to
+    const int32_t *row_map = nullptr;      // reduction launch only (split > 1): see reduce_splits_body<, MAPPED>
+    const float *ref = nullptr;     // tuning: the reference product (M x N fp32) every candidate is held to
 };
 
 // split > 1: a strided batch over `split` equal slices of the K rows; the fp32 partial products
@@ -195,11 +197,14 @@ __device__ __forceinline__ void add_slices(const float *__restrict__ p, int64_t 
 
 // vec (decided by the host): N, ldd and the output pointer allow one 16-byte (fp32) or 8-byte (16-bit) store per
 // position; otherwise four scalar stores.
-template <typename OT>
-__global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ part, int split, int64_t MN, int N,
-                                                     int64_t ldd, int vec, OT *__restrict__ out, int reduce_blocks,
-                                                     const float *__restrict__ fin_part, int fin_nparts, int fin_C,
-                                                     float *__restrict__ fin_out) {
+// MAPPED: row r of the product goes to row row_map[r] of D and the finalize job's sum k to fin_out[row_map[k]] (the
+// head-interleaved rows of the MSDeformAttn pair GEMM back in parameter order, without an index_select behind the launch);
+// an entry outside the rows of D drops its row.  The loads and the add chain do not know about the map.
+template <typename OT, bool MAPPED>
+__device__ __forceinline__ void reduce_splits_body(const float *__restrict__ part, int split, int64_t MN, int N,
+                                                   int64_t ldd, int vec, OT *__restrict__ out, int reduce_blocks,
+                                                   const float *__restrict__ fin_part, int fin_nparts, int fin_C,
+                                                   float *__restrict__ fin_out, const int32_t *__restrict__ row_map) {
     if ((int)blockIdx.x >= reduce_blocks) {
         // finalize job: 32 columns x 8 partial-row lanes per workgroup
         __shared__ float s_acc[8][32];
@@ -220,7 +225,12 @@ __global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ p
             float t = 0.f;
 #pragma unroll
             for (int u = 0; u < 8; ++u) t += s_acc[u][col];
-            fin_out[k] = t;
+            if constexpr (MAPPED) {
+                const unsigned kk = (unsigned)row_map[k];
+                if (kk < (unsigned)fin_C) fin_out[kk] = t;
+            } else {
+                fin_out[k] = t;
+            }
         }
         return;
     }
@@ -258,6 +268,12 @@ __global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ p
             const int64_t row = i / N;
             o = row * ldd + (i - row * N);
         }
+        if constexpr (MAPPED) {
+            const int64_t row = i / N;                  // N % 4 == 0 (split_candidates): a position lies in one row
+            const unsigned to = (unsigned)row_map[row];
+            if ((int64_t)to >= MN / N) continue;
+            o = (int64_t)to * ldd + (i - row * N);
+        }
         typedef OT ov4 __attribute__((ext_vector_type(4)));
         ov4 r;
         r[0] = (OT)acc.x;
@@ -273,6 +289,22 @@ __global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ p
             out[o + 3] = r[3];
         }
     }
+}
+
+template <typename OT>
+__global__ __launch_bounds__(256) void reduce_splits(const float *__restrict__ part, int split, int64_t MN, int N,
+                                                     int64_t ldd, int vec, OT *__restrict__ out, int reduce_blocks,
+                                                     const float *__restrict__ fin_part, int fin_nparts, int fin_C,
+                                                     float *__restrict__ fin_out) {
+    reduce_splits_body<OT, false>(part, split, MN, N, ldd, vec, out, reduce_blocks, fin_part, fin_nparts, fin_C, fin_out, nullptr);
+}
+
+template <typename OT>
+__global__ __launch_bounds__(256) void reduce_splits_mapped(const float *__restrict__ part, int split, int64_t MN, int N,
+                                                            int64_t ldd, int vec, OT *__restrict__ out, int reduce_blocks,
+                                                            const float *__restrict__ fin_part, int fin_nparts, int fin_C,
+                                                            float *__restrict__ fin_out, const int32_t *__restrict__ row_map) {
+    reduce_splits_body<OT, true>(part, split, MN, N, ldd, vec, out, reduce_blocks, fin_part, fin_nparts, fin_C, fin_out, row_map);
 }
 
 // ---- numerical check of a tuning candidate: its WHOLE output against a plain fp32-accumulating product of the same
@@ -420,6 +452,19 @@ hipblasStatus_t run(State &S, const Call &c, Problem &p, const hipblasLtMatmulAl
     const unsigned fblocks = fin ? (unsigned)((c.fin_C + 31) / 32) : 0u;
     // a position is 4 consecutive elements of one row (N % 4 == 0): it leaves as one store where every row starts aligned
     const int vec = c.k.N % 4 == 0 && c.k.ldd % 4 == 0 && (uintptr_t)c.D % (c.k.d32 ? 16 : 8) == 0;
+    if (c.row_map && split > 1) {
+        const dim3 grid(rblocks + fblocks);
+        if (c.k.d32)
+            hipLaunchKernelGGL(reduce_splits_mapped<float>, grid, dim3(256), 0, c.st, (const float *)c.ws, split, MN, (int)c.k.N,
+                               c.k.ldd, vec, (float *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out, c.row_map);
+        else if (c.k.f16)
+            hipLaunchKernelGGL(reduce_splits_mapped<_Float16>, grid, dim3(256), 0, c.st, (const float *)c.ws, split, MN, (int)c.k.N,
+                               c.k.ldd, vec, (_Float16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out, c.row_map);
+        else
+            hipLaunchKernelGGL(reduce_splits_mapped<__bf16>, grid, dim3(256), 0, c.st, (const float *)c.ws, split, MN, (int)c.k.N,
+                               c.k.ldd, vec, (__bf16 *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out, c.row_map);
+        return HIPBLAS_STATUS_SUCCESS;
+    }
     if (c.k.d32)
         hipLaunchKernelGGL(reduce_splits<float>, dim3(rblocks + fblocks), dim3(256), 0, c.st, (const float *)c.ws, split, MN,
                            (int)c.k.N, c.k.ldd, vec, (float *)c.D, (int)rblocks, c.fin_part, c.fin_nparts, c.fin_C, c.fin_out);
@@ -628,7 +673,7 @@ int vah_gemm_set_tuning(int mode, int candidates) {
 static int gemm_impl(const char *fn, int f16, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
                      const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue, const void *bias,
                      int bias_is_f32, void *workspace, int64_t workspace_bytes, void *stream, const float *fin_part,
-                     int64_t fin_nparts, int64_t fin_C, float *fin_out);
+                     int64_t fin_nparts, int64_t fin_C, float *fin_out, const int32_t *row_map = nullptr, int *applied = nullptr);
 
 int vah_gemm_bf16(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
                   const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue, const void *bias,
@@ -674,10 +719,51 @@ int vah_gemm_f16_fin(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, 
                      0, workspace, workspace_bytes, stream, fin_part, fin_nparts, fin_C, fin_out);
 }
 
+// vah_gemm_bf16_fin / vah_gemm_f16_fin with a row map on the reduction launch (include/vitadapter_hip_epoch.h): D's row r
+// lands in row row_map[r], the finalize sum k in fin_out[row_map[k]].  *applied = 0 where the product runs with split 1
+// (hipBLASLt writes D itself): D and fin_out are then in the product's own order.
+static int gemm_fin_rowmap(const char *fn, int f16, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A,
+                           int64_t lda, const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, void *workspace,
+                           int64_t workspace_bytes, const float *fin_part, int64_t fin_nparts, int64_t fin_C, float *fin_out,
+                           const int32_t *row_map, int *applied, void *stream) {
+    using namespace vah;
+    if (applied) *applied = 0;
+    if (!fin_part || !fin_out || fin_nparts < 1 || fin_C < 1 || fin_nparts > (1 << 20) || fin_C > (1 << 24)) {
+        clear_error();
+        return fail(VAH_E_SHAPE, "%s: bad finalize job", fn);
+    }
+    if (!row_map) {
+        clear_error();
+        return fail(VAH_E_NULL, "%s: null pointer (row_map)", fn);
+    }
+    if (fin_C != M || (uintptr_t)row_map % 4) {
+        clear_error();
+        return fail(VAH_E_SHAPE, "%s: the row map serves D's rows and the finalize sums alike (fin_C == M), 4-byte aligned", fn);
+    }
+    return gemm_impl(fn, f16, trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, VAH_GEMM_EPI_NONE, nullptr, 0, workspace,
+                     workspace_bytes, stream, fin_part, fin_nparts, fin_C, fin_out, row_map, applied);
+}
+
+int vah_gemm_bf16_fin_rowmap(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+                             const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, void *workspace,
+                             int64_t workspace_bytes, const float *fin_part, int64_t fin_nparts, int64_t fin_C,
+                             float *fin_out, const int32_t *row_map, int *applied, void *stream) {
+    return gemm_fin_rowmap("vah_gemm_bf16_fin_rowmap", 0, trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, workspace,
+                           workspace_bytes, fin_part, fin_nparts, fin_C, fin_out, row_map, applied, stream);
+}
+
+int vah_gemm_f16_fin_rowmap(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+                            const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, void *workspace,
+                            int64_t workspace_bytes, const float *fin_part, int64_t fin_nparts, int64_t fin_C,
+                            float *fin_out, const int32_t *row_map, int *applied, void *stream) {
+    return gemm_fin_rowmap("vah_gemm_f16_fin_rowmap", 1, trans_a, trans_b, M, N, K, A, lda, B, ldb, D, ldd, d_is_f32, workspace,
+                           workspace_bytes, fin_part, fin_nparts, fin_C, fin_out, row_map, applied, stream);
+}
+
 static int gemm_impl(const char *fn, int f16, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
                      const void *B, int64_t ldb, void *D, int64_t ldd, int d_is_f32, int epilogue, const void *bias,
                      int bias_is_f32, void *workspace, int64_t workspace_bytes, void *stream, const float *fin_part,
-                     int64_t fin_nparts, int64_t fin_C, float *fin_out) {
+                     int64_t fin_nparts, int64_t fin_C, float *fin_out, const int32_t *row_map, int *applied) {
     using namespace vah;
     clear_error();
     if (M < 0 || N < 0 || K < 0) return fail(VAH_E_SHAPE, "%s: negative dimension", fn);
@@ -742,6 +828,9 @@ static int gemm_impl(const char *fn, int f16, int trans_a, int trans_b, int64_t 
         hipblasLtMatmulDescSetAttribute(pp->desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &c.bias, sizeof(c.bias));
     }
     Problem &p = *pp;
+    // the map rides on the reduction launch only; tuning and validation above ran without it
+    c.row_map = it->second.split > 1 ? row_map : nullptr;
+    if (applied) *applied = c.row_map != nullptr;
     s = run(S, c, p, it->second.algo, it->second.workspace, it->second.split);
     if (s != HIPBLAS_STATUS_SUCCESS) return fail(VAH_E_UNSUPPORTED, "%s: hipblasLtMatmul: %s", fn, status_name(s));
     return check_launch(fn);

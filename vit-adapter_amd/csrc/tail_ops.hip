@@ -27,6 +27,7 @@
 #include <cstring>
 
 #include "../../include/vitadapter_hip.h"
+#include "../../include/vitadapter_hip_epoch.h"
 #include "common.h"
 #include "elem16.h"
 
@@ -789,13 +790,10 @@ __global__ __launch_bounds__(256) void tail_finalize(const float *__restrict__ p
 // sums = [sum t (C) | sum t^2 (C) | count (1)]  ->  mean, rstd (biased variance, as the normalisation
 // uses) and the running statistics (unbiased variance, momentum) in ONE small launch; done with
 // separate torch ops this bookkeeping was ~10 kernel launches per BatchNorm call.
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float *__restrict__ sums, int C, float eps, float momentum,
-                                                          float *__restrict__ running_mean,
-                                                          float *__restrict__ running_var, float *__restrict__ mean,
-                                                          float *__restrict__ rstd) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const float count = sums[2 * C];
+__device__ __forceinline__ void bn_finalize_channel(const float *__restrict__ sums, int C, int c, float count, float eps,
+                                                    float momentum, float *__restrict__ running_mean,
+                                                    float *__restrict__ running_var, float *__restrict__ mean,
+                                                    float *__restrict__ rstd) {
     const float mu = sums[c] / count;
     // nanmax: an inf or NaN in the channel gives a NaN variance, and BatchNorm then a NaN channel (as torch's)
     const float var = nanmax(sums[C + c] / count - mu * mu, 0.f);
@@ -804,6 +802,32 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float *__restric
     if (running_mean) {
         running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
         running_var[c] = (1.f - momentum) * running_var[c] + momentum * var * (count / fmaxf(count - 1.f, 1.f));
+    }
+}
+
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float *__restrict__ sums, int C, float eps, float momentum,
+                                                          float *__restrict__ running_mean,
+                                                          float *__restrict__ running_var, float *__restrict__ mean,
+                                                          float *__restrict__ rstd) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    bn_finalize_channel(sums, C, c, sums[2 * C], eps, momentum, running_mean, running_var, mean, rstd);
+}
+
+// The same with BatchNorm's bookkeeping: the count comes as an argument (no thread reads sums[2 * C], so the thread
+// that stores it there for the backward races with nobody) and num_batches_tracked advances by one.  Saves the fill and
+// the int64 add that torch ran as launches of their own (2 x 11 per step).
+__global__ __launch_bounds__(256) void bn_finalize_book_kernel(float *__restrict__ sums, int C, float count, float eps,
+                                                               float momentum, float *__restrict__ running_mean,
+                                                               float *__restrict__ running_var, float *__restrict__ mean,
+                                                               float *__restrict__ rstd,
+                                                               int64_t *__restrict__ num_batches_tracked) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    bn_finalize_channel(sums, C, c, count, eps, momentum, running_mean, running_var, mean, rstd);
+    if (c == 0) {
+        sums[2 * C] = count;
+        if (num_batches_tracked) *num_batches_tracked += 1;
     }
 }
 
@@ -1355,6 +1379,20 @@ int vah_bn_finalize_stats(const float *sums, int64_t C, float eps, float momentu
     if (!sums || !mean || !rstd || ((running_mean != nullptr) != (running_var != nullptr))) return fail(VAH_E_NULL, "%s: null pointer", fn);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sums, (int)C, eps,
                        momentum, running_mean, running_var, mean, rstd);
+    return check_launch(fn);
+}
+
+// vah_bn_finalize_stats with the bookkeeping of a BatchNorm that has no process group in the same launch
+// (include/vitadapter_hip_epoch.h): count -> sums[2 * C], num_batches_tracked += 1 (null: nothing tracked).
+int vah_bn_finalize_stats_book(float *sums, int64_t C, float count, float eps, float momentum, float *running_mean,
+                               float *running_var, float *mean, float *rstd, int64_t *num_batches_tracked, void *stream) {
+    using namespace vah;
+    clear_error();
+    const char *fn = "vah_bn_finalize_stats_book";
+    if (C < 1 || C > (1 << 24)) return fail(VAH_E_SHAPE, "%s: bad C", fn);
+    if (!sums || !mean || !rstd || ((running_mean != nullptr) != (running_var != nullptr))) return fail(VAH_E_NULL, "%s: null pointer", fn);
+    hipLaunchKernelGGL(bn_finalize_book_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sums, (int)C,
+                       count, eps, momentum, running_mean, running_var, mean, rstd, num_batches_tracked);
     return check_launch(fn);
 }
 

@@ -52,7 +52,11 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'point_loss': True,
            'point_mask_loss': True,   # needs point_loss as well: the sampled BCE / dice of the matched masks on kernels
            'seg_logits': True,
-           'seg_ce_loss': True}
+           'seg_ce_loss': True,
+           # the per-step parameter work on kernels of its own (include/vitadapter_hip_epoch.h): one launch for all 16-bit
+           # parameter copies and layouts of a forward (_EpochCopies), pair-core weight gradients stored in parameter
+           # order by the reduction launch, BatchNorm bookkeeping inside the finalize launch.  Off: the torch expressions
+           'epoch_copies': True}
 for _k in os.environ.get('VAH_FUSED_DISABLE', '').split(','):      # e.g. VAH_FUSED_DISABLE=residual_ln,bn_tail (A/B runs)
     if _k:
         ENABLED[_k.strip()] = False
@@ -246,18 +250,40 @@ class _Bf16Copies:
 
     def __init__(self):
         self.entries = {}          # (id(param), dtype) -> (weakref(param), copy, epoch)
+        self.layouts = {}          # (kind, id(param), dtype) -> (weakref(param), re-laid-out copies, epoch): _EpochCopies
         self.epoch = 0             # even: no forward open; odd: the open forward's epoch
 
-    def get(self, p, dtype=torch.bfloat16):
+    def _hit(self, p, dtype):
         e = self.entries.get((id(p), dtype))
         if (e is not None and e[2] == self.epoch and (self.epoch & 1) and e[0]() is p and e[1].device == p.device
                 and e[1].dtype == dtype):
             return e[1]
+        return None
+
+    def get(self, p, dtype=torch.bfloat16):
+        c = self._hit(p, dtype)
+        if c is not None:
+            return c
+        base = p._base             # a reshaping view of a parameter (a conv weight as a matrix): the parameter's copy, viewed alike
+        if base is not None and base.numel() == p.numel() and p.is_contiguous() and p.storage_offset() == base.storage_offset():
+            c = self._hit(base, dtype)
+            if c is not None:
+                return c.view(p.shape)
         return p.detach().to(dtype)
+
+    def layout(self, kind, p, dtype):
+        """The copy of ``p`` in the layout ``kind`` that this epoch's launch made (_EpochCopies), or None."""
+        e = self.layouts.get((kind, id(p), dtype))
+        if e is not None and e[2] == self.epoch and (self.epoch & 1) and e[0]() is p:
+            return e[1]
+        return None
+
+    def open(self):
+        self.epoch += 1 if (self.epoch & 1) == 0 else 2          # a nested / aborted forward just opens a new epoch
 
     def begin(self, params, dtype=torch.bfloat16):
         import weakref
-        self.epoch += 1 if (self.epoch & 1) == 0 else 2          # a nested / aborted forward just opens a new epoch
+        self.open()
         if not params:
             return
         flat = torch.empty(sum(p.numel() for p in params), dtype=dtype, device=params[0].device)
@@ -331,8 +357,9 @@ DROP_POOL = _DropPool()
 
 
 class forward_epoch:
-    """``with fused.forward_epoch(model): ...`` around a model's forward: on entry ONE multi-tensor cast
-    makes the 16-bit copies (the autocast's type) of all its fp32 nn.Linear parameters, which then serve every fused Linear of
+    """``with fused.forward_epoch(model): ...`` around a model's forward: on entry ONE launch (_EpochCopies; with
+    ENABLED['epoch_copies'] off, or without a usable job table, one multi-tensor cast of the nn.Linear parameters alone)
+    makes the 16-bit copies (the autocast's type) of its fp32 parameters, which then serve every fused operator of
     this forward; on exit (also by an exception) the epoch closes and later uses cast on their own, so
     a parameter written between two forwards - by any means, `.data` included - is always seen."""
 
@@ -353,7 +380,10 @@ class forward_epoch:
             module.__dict__['_vah_linear_params'] = params
         live = [p for p in params if p.dtype == torch.float32 and p.is_cuda]
         if live:
-            BF16_COPIES.begin(live, t16)
+            # one launch for every copy and layout of this forward (_EpochCopies), or the multi-tensor cast of the Linear
+            # parameters with every other copy made on use
+            if not (ENABLED['epoch_copies'] and EPOCH_COPIES.begin(module, t16, live[0].device)):
+                BF16_COPIES.begin(live, t16)
             SIDE.begin_epoch()
             BIAS_PARTIALS.begin_epoch()
             if module.training:
@@ -442,12 +472,12 @@ def gemm_16(a, b, trans_a=False, trans_b=False, out_dtype=None, bias=None, out=N
 gemm_bf16 = gemm_16         # the name from before the dispatcher took fp16 operands: for callers outside this module
 
 
-def _wgrad_bgrad(g2, x2, partials=None):
+def _wgrad_bgrad(g2, x2, partials=None, row_map=None):
     """(dW, db) = (g2^T x2 in fp32, column sums of g2) of a Linear backward: column-sum partials, the
     (split-K) GEMM and ONE launch that both reduces the GEMM's slices and sums the partials.  g2, x2: one 16-bit type
     (bf16 or fp16), which picks the entry points.  ``partials``:
     (rows of partial column sums of g2, their number) left by the kernel that wrote g2 (_BiasPartials) - no
-    column-sum launch and no second read of g2 then."""
+    column-sum launch and no second read of g2 then.  ``row_map``: see _wgrad_bgrad_mapped (a third result then)."""
     import ctypes
     R, N = g2.shape
     K = x2.shape[1]
@@ -467,9 +497,23 @@ def _wgrad_bgrad(g2, x2, partials=None):
         else:
             cws, nparts = _scratch(N, dev), ctypes.c_int64(0)
             _vah.call('vah_colsum_bf16_partials', t16, g2.data_ptr(), R, N, cws.data_ptr(), ctypes.byref(nparts), st)
+        if row_map is not None:
+            applied = ctypes.c_int(0)
+            fn = _vah.lib.vah_gemm_bf16_fin_rowmap if t16 == torch.bfloat16 else _vah.lib.vah_gemm_f16_fin_rowmap
+            _vah.check(fn(1, 0, N, K, R, g2.data_ptr(), N, x2.data_ptr(), K, gw.data_ptr(), K, 1, ws.data_ptr(), ws_bytes,
+                          cws.data_ptr(), nparts.value, N, gb.data_ptr(), row_map.data_ptr(), ctypes.byref(applied), st), fn.__name__)
+            return gw, gb, bool(applied.value)
         _vah.call('vah_gemm_bf16_fin', t16, 1, 0, N, K, R, g2.data_ptr(), N, x2.data_ptr(), K, gw.data_ptr(), K, 1, ws.data_ptr(), ws_bytes,
                   cws.data_ptr(), nparts.value, N, gb.data_ptr(), st)
     return gw, gb
+
+
+def _wgrad_bgrad_mapped(g2, x2, row_map):
+    """_wgrad_bgrad with dW's row r stored to row ``row_map[r]`` and db's sum k to element ``row_map[k]`` (int32, N entries,
+    a permutation) by the reduction launch itself -> (dW, db, applied).  applied False: the dispatcher ran the product
+    without a reduction launch (split 1) and dW, db are in the product's own row order."""
+    assert row_map.dtype == torch.int32 and row_map.numel() == g2.shape[1] and row_map.is_contiguous() and row_map.device == g2.device
+    return _wgrad_bgrad(g2, x2, None, row_map)
 
 
 class _SideStream:
@@ -829,6 +873,27 @@ class _PairCoreCopies:
     def __init__(self):
         self.entries = {}
 
+    def perm(self, a, b, M):
+        """(permutation, its inverse, the permutation as the int32 row map of the weight-gradient reduction): made once
+        per module and device, not per call."""
+        e = self.entries.get((id(a.weight), id(b.weight)))
+        na, nb = a.weight.shape[0], b.weight.shape[0]
+        po, pl = na // M, nb // M
+        dev = a.weight.device
+        if e is not None and e[4]() is a.weight and e[3][0].device == dev and e[3][0].numel() == na + nb:
+            return e[3]     # of this very module: id() of a collected module's weights comes back for another module's
+        fw = torch.cat([torch.cat((torch.arange(m * po, (m + 1) * po), na + torch.arange(m * pl, (m + 1) * pl))) for m in range(M)])
+        inv = torch.empty_like(fw)
+        inv[fw] = torch.arange(fw.numel())
+        return (fw.to(dev), inv.to(dev), fw.to(torch.int32).to(dev))
+
+    def put(self, a, b, epoch, w, bias, perm):
+        """The copies this epoch's launch made (_EpochCopies)."""
+        import weakref
+        if len(self.entries) > 1024:
+            self.entries.clear()
+        self.entries[(id(a.weight), id(b.weight))] = (epoch, w, bias, perm, weakref.ref(a.weight))
+
     def get(self, a, b, M):
         key = (id(a.weight), id(b.weight))
         epoch = BF16_COPIES.epoch
@@ -836,16 +901,7 @@ class _PairCoreCopies:
         if e is not None and e[0] == epoch and (epoch & 1) and e[1].device == a.weight.device and e[4]() is a.weight:
             return e[1], e[2], e[3]
         import weakref
-        na, nb = a.weight.shape[0], b.weight.shape[0]
-        po, pl = na // M, nb // M
-        dev = a.weight.device
-        if e is not None and e[4]() is a.weight and e[3][0].device == dev and e[3][0].numel() == na + nb:
-            perm = e[3]     # of this very module: id() of a collected module's weights comes back for another module's
-        else:               # (permutation, its inverse): made once per module and device, not per call
-            fw = torch.cat([torch.cat((torch.arange(m * po, (m + 1) * po), na + torch.arange(m * pl, (m + 1) * pl))) for m in range(M)])
-            inv = torch.empty_like(fw)
-            inv[fw] = torch.arange(fw.numel())
-            perm = (fw.to(dev), inv.to(dev))
+        perm = self.perm(a, b, M)
         with torch.no_grad():
             w = torch.cat([a.weight.detach(), b.weight.detach()], 0).index_select(0, perm[0]).to(torch.bfloat16)
             bias = torch.cat([a.bias.detach(), b.bias.detach()], 0).float().index_select(0, perm[0])
@@ -856,6 +912,188 @@ class _PairCoreCopies:
 
 
 PAIR_CORE_COPIES = _PairCoreCopies()
+
+
+class _EpochTable:
+    """The job table of one model and 16-bit type (see _EpochCopies): device tensors ``jobs`` / ``chunks``, the sizes of
+    the two destination buffers, what every parameter looked like when the table was built (``sig``) and how the
+    buffers are handed out (``serve``)."""
+
+    def __init__(self, dtype, device):
+        self.dtype, self.device = dtype, device
+        self.rows, self.params, self.sig, self.serve = [], [], [], []
+        self.n16 = self.n32 = 0
+        self.jobs = self.chunks = None
+        self.nchunks = 0
+
+    def valid(self):
+        for p, (ptr, shape, dtype) in zip(self.params, self.sig):
+            if p.data_ptr() != ptr or p.shape != shape or p.dtype != dtype:
+                return False
+        return True
+
+    def uses(self, p):
+        if not any(q is p for q in self.params):
+            self.params.append(p)
+            self.sig.append((p.data_ptr(), p.shape, p.dtype))
+
+    def alloc(self, n, f32=False):
+        """Offset of ``n`` elements in the 16-bit (fp32) destination buffer, starting on a 16-byte (32-byte) boundary."""
+        if f32:
+            off, self.n32 = self.n32, self.n32 + (n + 7) // 8 * 8
+        else:
+            off, self.n16 = self.n16, self.n16 + (n + 7) // 8 * 8
+        return off
+
+    def job(self, p, src_off, dst, dims, strides, lims=None, f32=False):
+        """Gather ``dims`` (destination order, up to 4) from parameter ``p`` at element offset ``src_off`` with element
+        ``strides``; ``lims``: the source's extents (an index beyond reads as zero)."""
+        dims, strides = (1,) * (4 - len(dims)) + tuple(dims), (0,) * (4 - len(strides)) + tuple(strides)
+        lims = dims if lims is None else (1,) * (4 - len(lims)) + tuple(lims)
+        n = dims[0] * dims[1] * dims[2] * dims[3]
+        assert 0 < n < 2 ** 31 and p.dtype == torch.float32 and p.is_contiguous() and 0 <= src_off < p.numel()
+        last = sum((min(d, l) - 1) * s for d, l, s in zip(dims, lims, strides))
+        assert min(strides) >= 0 and src_off + last < p.numel(), 'a job reads past its parameter'
+        packed = (dims[1] * dims[2] * dims[3], dims[2] * dims[3], dims[3], 1)
+        dense = all(d == 1 or s == c for d, s, c in zip(dims, strides, packed)) and all(l >= d for l, d in zip(lims, dims))
+        self.uses(p)
+        self.rows.append([p.data_ptr() + 4 * src_off, dst, n, dims[1], dims[2], dims[3], *strides, *lims,
+                          (1 if dense else 0) | (2 if f32 else 0), p.numel() - src_off])
+
+    def finish(self):
+        chunk = int(_vah.lib.vah_epoch_chunk_elems())
+        assert _vah.lib.vah_epoch_job_bytes() == 16 * 8
+        if not self.rows:
+            return self
+        jobs = torch.tensor(self.rows, dtype=torch.int64)
+        counts = (jobs[:, 2] + chunk - 1) // chunk
+        job_of = torch.repeat_interleave(torch.arange(len(self.rows)), counts)
+        first = torch.cumsum(counts, 0) - counts
+        k = torch.arange(job_of.numel()) - first[job_of]
+        self.chunks = torch.stack([job_of, k], 1).to(torch.int32).contiguous().to(self.device)
+        self.jobs = jobs.to(self.device)
+        self.nchunks = int(job_of.numel())
+        return self
+
+
+class _EpochCopies:
+    """ONE launch (csrc/epoch_copies.hip) makes every 16-bit copy of fp32 parameters that a forward epoch serves: the plain
+    copies of the nn.Linear parameters and of the 1x1 / patch-embedding convolution weights (_Bf16Copies.get), the
+    head-interleaved [offsets of head m | logits of head m] rows and fp32 bias of every MSDeformAttn pair
+    (_PairCoreCopies; 2 * M contiguous row-block jobs each, no permutation array), the tap-major (Cout, 9, Cin) and
+    (Cin, 9, Cout) layouts of the bias-free 3x3 convolutions (spm_nhwc._Conv3x3; a 3-channel stem weight zero-padded to the
+    16-channel image) and the (dy, dx, co)-row matrix of a 2x2 / stride 2 transposed convolution (_UpFromTokens).
+
+    The table is built once per model and 16-bit type, cached on the module, and checked at every epoch against the
+    parameters' data_ptr(), shape and dtype (a mismatch rebuilds it: the jobs hold addresses).  The destination is a fresh
+    allocation per epoch - the kernel takes its base as an argument, jobs hold offsets - so a copy saved for a backward
+    keeps the values of its own forward.  Building a table copies it to the device: inside a graph capture an epoch
+    without a valid table takes the per-use path instead (begin returns False).  A parameter the table does not hold is
+    cast on use, as outside an epoch.  Modules are recognised by type and geometry alone; a model with other 3x3
+    convolutions gets copies nobody reads (they cost bandwidth, never correctness)."""
+
+    ATTR = '_vah_epoch_tables'
+
+    @staticmethod
+    def _ok(p, dev):
+        return (isinstance(p, torch.Tensor) and p.dtype == torch.float32 and p.device == dev and p.is_contiguous()
+                and 0 < p.numel() < 2 ** 31)
+
+    def build(self, module, t16, dev):
+        nn = torch.nn
+        tab = _EpochTable(t16, dev)
+        plain = set()
+
+        def add_plain(p):
+            if self._ok(p, dev) and id(p) not in plain:
+                plain.add(id(p))
+                off = tab.alloc(p.numel())
+                tab.job(p, 0, off, (p.numel(),), (1,))
+                tab.serve.append(('plain', p, off))
+
+        for m in module.modules():
+            if isinstance(m, nn.Linear):
+                add_plain(m.weight)
+                add_plain(m.bias)
+            elif isinstance(m, nn.ConvTranspose2d):
+                w = m.weight
+                if (m.kernel_size == (2, 2) and m.stride == (2, 2) and m.padding == (0, 0) and m.output_padding == (0, 0)
+                        and m.groups == 1 and m.dilation == (1, 1) and self._ok(w, dev)):
+                    C, Co = w.shape[0], w.shape[1]
+                    off = tab.alloc(w.numel())
+                    tab.job(w, 0, off, (2, 2, Co, C), (2, 1, 4, Co * 4))            # rows (dy, dx, co)
+                    tab.serve.append(('up', w, off, (4 * Co, C)))
+            elif isinstance(m, nn.Conv2d) and m.groups == 1 and m.dilation == (1, 1) and self._ok(m.weight, dev):
+                w, k = m.weight, m.kernel_size
+                Co, Ci = w.shape[0], w.shape[1]
+                if k == (3, 3) and m.padding == (1, 1) and m.bias is None:
+                    cin = (Ci + 15) // 16 * 16                       # the stem reads the image as 16 channels, 3..15 zero
+                    o9, ot9 = tab.alloc(Co * 9 * cin), tab.alloc(cin * 9 * Co)
+                    tab.job(w, 0, o9, (Co, 3, 3, cin), (Ci * 9, 3, 1, 9), (Co, 3, 3, Ci))
+                    tab.job(w, 0, ot9, (cin, 3, 3, Co), (9, 3, 1, Ci * 9), (Ci, 3, 3, Co))
+                    tab.serve.append(('conv9', w, o9, (Co, 9, cin), ot9, (cin, 9, Co)))
+                elif t16 == torch.bfloat16 and m.padding == (0, 0) and k == m.stride:
+                    add_plain(w)                                     # patch embedding / 1x1: a matrix as it lies (bf16 paths only)
+            a, b = getattr(m, 'sampling_offsets', None), getattr(m, 'attention_weights', None)
+            M = getattr(m, 'n_heads', None)
+            if (t16 == torch.bfloat16 and type(a) is nn.Linear and type(b) is nn.Linear and isinstance(M, int) and M > 0
+                    and all(self._ok(p, dev) for p in (a.weight, a.bias, b.weight, b.bias))
+                    and a.weight.shape[1] == b.weight.shape[1] and a.weight.shape[0] % M == 0 and b.weight.shape[0] % M == 0):
+                na, nb, K = a.weight.shape[0], b.weight.shape[0], a.weight.shape[1]
+                po, pl = na // M, nb // M
+                ow, ob = tab.alloc((na + nb) * K), tab.alloc(na + nb, f32=True)
+                for h in range(M):
+                    r = h * (po + pl)
+                    tab.job(a.weight, h * po * K, ow + r * K, (po * K,), (1,))
+                    tab.job(b.weight, h * pl * K, ow + (r + po) * K, (pl * K,), (1,))
+                    tab.job(a.bias, h * po, ob + r, (po,), (1,), f32=True)
+                    tab.job(b.bias, h * pl, ob + r + po, (pl,), (1,), f32=True)
+                tab.serve.append(('pair_core', a, b, ow, (na + nb, K), ob, PAIR_CORE_COPIES.perm(a, b, M)))
+        return tab.finish()
+
+    def begin(self, module, t16, dev):
+        """Open an epoch whose copies come from the table's one launch.  False (nothing opened): no usable table - the
+        caller makes the epoch's copies the multi-tensor way."""
+        tables = module.__dict__.setdefault(self.ATTR, {})
+        tab = tables.get((t16, dev))
+        if tab is None or not tab.valid():
+            if torch.cuda.is_current_stream_capturing():
+                return False                    # building copies the table to the device: not inside a capture
+            tab = tables[(t16, dev)] = self.build(module, t16, dev)
+        if tab.nchunks == 0:
+            return False
+        import weakref
+        out16 = torch.empty(tab.n16, dtype=t16, device=dev)
+        out32 = torch.empty(max(tab.n32, 8), dtype=torch.float32, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_epoch_copies(tab.jobs.data_ptr(), tab.jobs.shape[0], tab.chunks.data_ptr(), tab.nchunks,
+                                                 1 if t16 == torch.bfloat16 else 2, out16.data_ptr(), tab.n16, out32.data_ptr(),
+                                                 tab.n32, _vah.raw_stream(dev)), 'epoch_copies')
+        cp = BF16_COPIES
+        cp.open()
+        epoch = cp.epoch
+        if len(cp.entries) > 4096:               # drop entries of collected parameters
+            cp.entries = {k: v for k, v in cp.entries.items() if v[0]() is not None}
+        if len(cp.layouts) > 1024:
+            cp.layouts = {k: v for k, v in cp.layouts.items() if v[0]() is not None}
+        for s in tab.serve:
+            kind, p = s[0], s[1]
+            if kind == 'plain':
+                cp.entries[(id(p), t16)] = (weakref.ref(p), out16[s[2]:s[2] + p.numel()].view(p.shape), epoch)
+            elif kind == 'up':
+                n = s[3][0] * s[3][1]
+                cp.layouts[('up', id(p), t16)] = (weakref.ref(p), out16[s[2]:s[2] + n].view(s[3]), epoch)
+            elif kind == 'conv9':
+                n = s[3][0] * s[3][1] * s[3][2]
+                cp.layouts[('conv9', id(p), t16)] = (weakref.ref(p), (out16[s[2]:s[2] + n].view(s[3]), out16[s[4]:s[4] + n].view(s[5])),
+                                                     epoch)
+            else:
+                a, b, ow, wshape, ob, perm = s[1:]
+                PAIR_CORE_COPIES.put(a, b, epoch, out16[ow:ow + wshape[0] * wshape[1]].view(wshape), out32[ob:ob + wshape[0]], perm)
+        return True
+
+
+EPOCH_COPIES = _EpochCopies()
 
 
 class _MSDAPairCore(torch.autograd.Function):
@@ -889,7 +1127,7 @@ class _MSDAPairCore(torch.autograd.Function):
         # the window-forward schedule rides on a grid the batch shares; one grid per image has no such schedule
         out = mf.fused_forward(value, shapes, lsi, offsets, logits, PS, PS, refc, carrier=ref if refc.shape[0] == 1 else None,
                                token=BF16_COPIES.epoch)
-        ctx.save_for_backward(x2, w, y, value, shapes, lsi, refc, perm[1])
+        ctx.save_for_backward(x2, w, y, value, shapes, lsi, refc, perm[1], perm[2])
         ctx.dims = (N, Lq, M, L, P, wa.shape[0])
         ctx.in_shape, ctx.in_dtype = query.shape, query.dtype
         return out
@@ -897,7 +1135,7 @@ class _MSDAPairCore(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        x2, w, y, value, shapes, lsi, refc, inv = ctx.saved_tensors
+        x2, w, y, value, shapes, lsi, refc, inv, row_map = ctx.saved_tensors
         N, Lq, M, L, P, na = ctx.dims
         S, D = value.shape[1], value.shape[3]
         PS = 3 * L * P
@@ -921,8 +1159,14 @@ class _MSDAPairCore(torch.autograd.Function):
             if gx.dtype != ctx.in_dtype:
                 gx = gx.to(ctx.in_dtype)
         if any(ctx.needs_input_grad[5:9]):
-            gwp, gbp = _wgrad_bgrad(g, x2)
-            gw, gbias = gwp.index_select(0, inv), gbp.index_select(0, inv)
+            # the reduction launch of the weight-gradient GEMM stores rows and bias sums in parameter order; a product the
+            # dispatcher runs without a reduction launch (split 1) comes back head-interleaved and is reordered here
+            if ENABLED['epoch_copies']:
+                gw, gbias, mapped = _wgrad_bgrad_mapped(g, x2, row_map)
+            else:
+                (gw, gbias), mapped = _wgrad_bgrad(g, x2), False
+            if not mapped:
+                gw, gbias = gw.index_select(0, inv), gbias.index_select(0, inv)
         return (gx, grad_value if ctx.needs_input_grad[1] else None, None, None, None,
                 gw[:na] if gw is not None else None, gbias[:na] if gbias is not None else None,
                 gw[na:] if gw is not None else None, gbias[na:] if gbias is not None else None, None, None, None, None)
@@ -1005,13 +1249,16 @@ class _UpFromTokens(torch.autograd.Function):
         B, T, C = rows.shape
         Co = weight.shape[1]
         xb = rows.detach().to(t16).contiguous()
+        wc = BF16_COPIES.layout('up', weight, t16)              # rows (dy, dx, co): made by the epoch's launch, or here
         if t16 == torch.bfloat16:
-            wc = BF16_COPIES.get(weight).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()       # rows (dy, dx, co)
+            if wc is None:
+                wc = BF16_COPIES.get(weight).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()
             U = torch.empty((B, 4 * Co, T), dtype=torch.bfloat16, device=rows.device)
             for b in range(B):
                 gemm_16(wc, xb[b], trans_b=True, out=U[b])
         else:
-            wc = weight.detach().to(t16).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()
+            if wc is None:
+                wc = weight.detach().to(t16).permute(2, 3, 1, 0).reshape(4 * Co, C).contiguous()
             U = torch.bmm(wc.unsqueeze(0).expand(B, 4 * Co, C), xb.transpose(1, 2))
         out = torch.empty((B, Co, 2 * h, 2 * w), dtype=t16, device=rows.device)
         add = addend.contiguous() if addend is not None else None
@@ -1350,6 +1597,38 @@ def _sync_group(norm):
     return group if data_parallel.one_rank_group() else None        # one rank: the collectives run only on request
 
 
+def bn_finalize(norm, sums, C, count, group, st):
+    """Training-mode BatchNorm between its statistics pass and its normalise pass: ``sums`` = [sum (C) | sum of squares
+    (C) | slot for the element count] -> (mean, rstd, the count as the 1-element tensor the backward divides by), running
+    statistics and num_batches_tracked updated.  Without a process group this is ONE launch (vah_bn_finalize_stats_book:
+    the count is stored and the counter advanced by the kernel that makes mean and rstd); with one the count must be in
+    ``sums`` before the all-reduce, and fill, all-reduce, finalize and the counter's add are separate steps.  The caller
+    has made the tensors' device current."""
+    dev = sums.device
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    rstd = torch.empty(C, dtype=torch.float32, device=dev)
+    track = norm.running_mean is not None
+    rm = norm.running_mean.data_ptr() if track else None
+    rv = norm.running_var.data_ptr() if track else None
+    nbt = norm.num_batches_tracked if track else None
+    if (group is None and ENABLED['epoch_copies']
+            and (nbt is None or (nbt.dtype == torch.int64 and nbt.device == dev and nbt.numel() == 1))):
+        _vah.check(_vah.lib.vah_bn_finalize_stats_book(
+            sums.data_ptr(), C, float(count), float(norm.eps), float(norm.momentum), rm, rv, mean.data_ptr(), rstd.data_ptr(),
+            nbt.data_ptr() if nbt is not None else None, st), 'bn_finalize_stats_book')
+        return mean, rstd, sums[2 * C:]
+    sums[2 * C:].fill_(float(count))
+    if group is not None:
+        import torch.distributed as dist
+        dist.all_reduce(sums, group=group)
+    _vah.check(_vah.lib.vah_bn_finalize_stats(sums.data_ptr(), C, float(norm.eps), float(norm.momentum), rm, rv, mean.data_ptr(),
+                                              rstd.data_ptr(), st), 'bn_finalize_stats')
+    if nbt is not None:
+        with torch.no_grad():
+            norm.num_batches_tracked += 1
+    return mean, rstd, sums[2 * C:]
+
+
 class _BNTail(torch.autograd.Function):
     """y = [relu] BatchNorm(a + b + upsample(x)): statistics pass, one bookkeeping launch (mean, rstd,
     running statistics), normalise pass; SyncBatchNorm all-reduces the sums in between.  ``t16``: the 16-bit type of
@@ -1376,21 +1655,7 @@ class _BNTail(torch.autograd.Function):
                 sums = torch.empty(2 * C + 1, dtype=torch.float32, device=dev)
                 ws = torch.empty(_vah.lib.vah_bn_tail_ws_floats(C), dtype=torch.float32, device=dev)
                 _vah.call('vah_bn_tail_stats', t16, *ops, shp, sums.data_ptr(), ws.data_ptr(), st)
-                sums[2 * C:].fill_(float(N * H * W))
-                if group is not None:
-                    import torch.distributed as dist
-                    dist.all_reduce(sums, group=group)
-                mean = torch.empty(C, dtype=torch.float32, device=dev)
-                rstd = torch.empty(C, dtype=torch.float32, device=dev)
-                track = norm.running_mean is not None
-                _vah.check(_vah.lib.vah_bn_finalize_stats(
-                    sums.data_ptr(), C, float(norm.eps), float(norm.momentum),
-                    norm.running_mean.data_ptr() if track else None, norm.running_var.data_ptr() if track else None,
-                    mean.data_ptr(), rstd.data_ptr(), st), 'bn_finalize_stats')
-                if track:
-                    with torch.no_grad():
-                        norm.num_batches_tracked += 1
-                count = sums[2 * C:]
+                mean, rstd, count = bn_finalize(norm, sums, C, N * H * W, group, st)
             else:
                 count = None
                 mean = norm.running_mean.float().contiguous()

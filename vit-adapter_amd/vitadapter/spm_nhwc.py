@@ -42,12 +42,18 @@ class _Conv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, stride):
         cin = x.shape[-1]
+        ctx.stride, ctx.wcin = stride, weight.shape[1]
+        # both tap-major layouts from the forward epoch's one launch (fused._EpochCopies), the second kept for the backward
+        made = fused.BF16_COPIES.layout('conv9', weight, x.dtype)
+        ctx.dgrad_ready = made is not None and made[0].shape[2] == cin
+        if ctx.dgrad_ready:
+            ctx.save_for_backward(x, made[1])
+            return conv.conv3x3_forward(x, made[0], stride)
         w = weight.detach()
         if w.shape[1] != cin:
             w = F.pad(w, (0, 0, 0, 0, 0, cin - w.shape[1]))
         wb = w.to(x.dtype)
         ctx.save_for_backward(x, wb)
-        ctx.stride, ctx.wcin = stride, weight.shape[1]
         return conv.conv3x3_forward(x, conv.forward_weight(wb, x.dtype), stride)
 
     @staticmethod
@@ -56,7 +62,8 @@ class _Conv3x3(torch.autograd.Function):
         gy = gy.contiguous().to(x.dtype)
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            gx = conv.conv3x3_input_grad(gy, conv.dgrad_weight(wb, x.dtype), ctx.stride, x.shape[1:3])
+            wt9 = wb if ctx.dgrad_ready else conv.dgrad_weight(wb, x.dtype)
+            gx = conv.conv3x3_input_grad(gy, wt9, ctx.stride, x.shape[1:3])
         if ctx.needs_input_grad[1]:
             gw = conv.conv3x3_weight_grad(x, gy, ctx.stride).permute(0, 3, 1, 2)[:, :ctx.wcin].contiguous()
         return gx, gw, None
@@ -80,21 +87,7 @@ class _BNRelu(torch.autograd.Function):
                 sums = torch.empty(2 * C + 1, dtype=torch.float32, device=dev)
                 ws = torch.empty(_vah.lib.vah_bn_nhwc_ws_floats(C), dtype=torch.float32, device=dev)
                 _vah.call('vah_bn_nhwc_stats', x.dtype, x.data_ptr(), rows, C, sums.data_ptr(), ws.data_ptr(), st)
-                sums[2 * C:].fill_(float(rows))
-                if group is not None:
-                    import torch.distributed as dist
-                    dist.all_reduce(sums, group=group)
-                mean = torch.empty(C, dtype=torch.float32, device=dev)
-                rstd = torch.empty(C, dtype=torch.float32, device=dev)
-                track = norm.running_mean is not None
-                _vah.check(_vah.lib.vah_bn_finalize_stats(
-                    sums.data_ptr(), C, float(norm.eps), float(norm.momentum),
-                    norm.running_mean.data_ptr() if track else None, norm.running_var.data_ptr() if track else None,
-                    mean.data_ptr(), rstd.data_ptr(), st), 'bn_finalize_stats')
-                if track:
-                    with torch.no_grad():
-                        norm.num_batches_tracked += 1
-                count = sums[2 * C:]
+                mean, rstd, count = fused.bn_finalize(norm, sums, C, rows, group, st)
             else:
                 count = None
                 mean = norm.running_mean.float().contiguous()
