@@ -294,6 +294,17 @@ for _name, (_res, _args) in EPOCH_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_seg_eval.h declares (the class counts of the mIoU
+# evaluation, csrc/seg_eval.hip).  A label map is (pointer[, dtype code], image stride, row stride).
+# tests/test_seg_eval_abi_cpu.py holds each entry to its prototype.
+SEGEVAL_SIGNATURES = {
+    'vah_segeval_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'vah_segeval_update': (_int, [_p, _i64, _i64, _p, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p, _i64, _p, _p, _i64, _p]),
+}
+for _name, (_res, _args) in SEGEVAL_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

@@ -32,6 +32,8 @@ seg_resize_add, seg_finish and seg_argmax (csrc/seg_logits.hip, ENABLED['seg_log
 (vitadapter/segmentor.py): window upsample-and-add, then count division, rescale, softmax, flip, view sum and argmax, fp32 NCHW.
 seg_cross_entropy (csrc/seg_ce_loss.hip, ENABLED['seg_ce_loss']) is the training loss of the UperNet heads (vitadapter/heads.py):
 bilinear resize to the label map, cross-entropy with an ignore index and the top-1 count, with an ordered backward into the logits.
+seg_eval_update (csrc/seg_eval.hip, ENABLED['seg_eval']) is the counting pass of the mIoU evaluation (vitadapter/evaluation.py):
+predicted labels and ground truth in, 3 x num_classes int64 totals added to on the device, nothing read back.
 """
 import math
 import os
@@ -53,6 +55,7 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'point_mask_loss': True,   # needs point_loss as well: the sampled BCE / dice of the matched masks on kernels
            'seg_logits': True,
            'seg_ce_loss': True,
+           'seg_eval': True,
            # the per-step parameter work on kernels of its own (include/vitadapter_hip_epoch.h): one launch for all 16-bit
            # parameter copies and layouts of a forward (_EpochCopies), pair-core weight gradients stored in parameter
            # order by the reduction launch, BatchNorm bookkeeping inside the finalize launch.  Off: the torch expressions
@@ -2600,3 +2603,83 @@ def seg_cross_entropy(seg_logit, seg_label, align_corners=False, ignore_index=25
         loss_sum = F.cross_entropy(v, label, weight=cw, reduction='none', ignore_index=ignore_index).sum()
         valid = label != ignore_index
         return loss_sum, valid.sum(), ((v.argmax(dim=1) == label) & valid).sum()
+
+
+_SEG_EVAL_CODES = {torch.int64: 0, torch.uint8: 1}
+_SEG_EVAL_MAPS = {}
+
+
+def _seg_eval_map(x):
+    """(N, H, W) label map as the counting kernel reads it: column stride 1, rows and images that do not overlap"""
+    N, H, W = x.shape
+    si, sr, sc = x.stride()
+    if sc != 1 or sr < W or si < (H - 1) * sr + W:
+        x = x.contiguous()
+    return x
+
+
+def _seg_eval_table(label_map, device):
+    """label_map {old: new} as the int64 device table of vah_segeval_update (identity outside the keys), built once per
+    mapping and device; None for a mapping the table cannot hold (a key outside [0, 256))"""
+    items = tuple(sorted((int(k), int(v)) for k, v in label_map.items()))
+    if not items or items[0][0] < 0 or items[-1][0] > 255:
+        return None
+    key = (items, str(device))
+    if key not in _SEG_EVAL_MAPS:
+        table = list(range(items[-1][0] + 1))
+        for old, new in items:
+            table[old] = new
+        _SEG_EVAL_MAPS[key] = torch.tensor(table, dtype=torch.int64, device=device)
+    return _SEG_EVAL_MAPS[key]
+
+
+def seg_eval_update(pred, label, totals, num_classes, ignore_index=255, reduce_zero_label=False, label_map=None):
+    """``totals += (area_intersect, area_pred_label, area_label)`` of mmseg's ``intersect_and_union`` for a batch, in place,
+    -> totals.  pred (N, H, W) predicted labels, label (N, H, W) or (N, 1, H, W) ground truth, totals (3, num_classes) int64
+    on their device.  Per pixel, in mmseg's order: ``g = label``; ``g = label_map[g]`` for the keys of ``label_map`` (a dict,
+    every entry applied to the original value); with ``reduce_zero_label`` ``g = 255 if g in (0, 255) else g - 1``; a pixel
+    with ``g == ignore_index`` counts for nothing; otherwise ``area_pred[pred]``, ``area_label[g]`` and - where they agree -
+    ``area_intersect[pred]`` grow by one, a value outside [0, num_classes) growing nothing.
+    On the GPU with ENABLED['seg_eval'], for int64 predictions and uint8 or int64 ground truth, this is vah_segeval_update
+    (csrc/seg_eval.hip): one counting launch and one merge launch, no host synchronisation, integer counts in any order.
+    Otherwise - switch off, CPU, other dtypes, more than 4096 classes - the same rule with masks and torch.bincount, integer
+    throughout (on a device torch.bincount synchronises)."""
+    if label.dim() == 4:
+        label = label.squeeze(1)
+    C = int(num_classes)
+    if pred.dim() != 3 or tuple(label.shape) != tuple(pred.shape) or tuple(totals.shape) != (3, C) or totals.dtype != torch.int64:
+        raise ValueError('seg_eval_update: pred %s, label %s, totals %s %s for %d classes'
+                         % (tuple(pred.shape), tuple(label.shape), tuple(totals.shape), totals.dtype, C))
+    if pred.numel() == 0:
+        return totals
+    dev = pred.device
+    table = None if not label_map else _seg_eval_table(label_map, dev)
+    if (ENABLED['seg_eval'] and pred.is_cuda and label.device == dev and totals.device == dev and totals.is_contiguous()
+            and pred.dtype == torch.int64 and label.dtype in _SEG_EVAL_CODES and (not label_map or table is not None)
+            and _vah.lib.vah_segeval_ws_bytes(*pred.shape, C) > 0):
+        p, g = _seg_eval_map(pred.detach()), _seg_eval_map(label.detach())
+        N, H, W = p.shape
+        nbytes = _vah.lib.vah_segeval_ws_bytes(N, H, W, C)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_segeval_update(p.data_ptr(), p.stride(0), p.stride(1), g.data_ptr(), _SEG_EVAL_CODES[g.dtype],
+                                                   g.stride(0), g.stride(1), N, H, W, C, int(ignore_index),
+                                                   1 if reduce_zero_label else 0, None if table is None else table.data_ptr(),
+                                                   0 if table is None else table.numel(), totals.data_ptr(), ws.data_ptr(), nbytes,
+                                                   _stream(p)), 'vah_segeval_update')
+        return totals
+    p, g0 = pred.long(), label.to(dev).long()
+    g = g0
+    if label_map:
+        g = g0.clone()
+        for old, new in label_map.items():
+            g[g0 == old] = new
+    if reduce_zero_label:
+        g = torch.where((g == 0) | (g == 255), torch.full_like(g, 255), g - 1)
+    keep = g != ignore_index
+    p_in, g_in = keep & (p >= 0) & (p < C), keep & (g >= 0) & (g < C)
+    spill = torch.full_like(p, C)                       # a bin past the classes for what counts for nothing
+    rows = [torch.bincount(torch.where(m, v, spill).reshape(-1), minlength=C + 1)[:C]
+            for m, v in ((p_in & (p == g), p), (p_in, p), (g_in, g))]
+    totals += torch.stack(rows).to(totals.device)
+    return totals

@@ -17,6 +17,9 @@ reference's own expressions):
   * division, un-padding, rescale to ``ori_shape``, softmax and flip are one pass that adds into the probability sum of
     ``aug_test`` or - for ``simple_test``, which returns labels only - writes the labels and no probabilities at all.
 The logit tail runs in fp32 with autocast disabled, as Mask2FormerHead.semantic_inference does.
+
+``simple_test_labels`` / ``aug_test_labels`` are ``simple_test`` / ``aug_test`` without the copy to the host, and
+``evaluate_batch`` hands their label map to a vitadapter.SegEvaluator (vitadapter/evaluation.py) on the device.
 """
 import numpy as np
 import torch
@@ -213,21 +216,47 @@ class EncoderDecoderMask2Former(nn.Module):
         """:220-253: the softmax output (N, C, H, W) with the flip undone"""
         return self._finish(img, img_meta, rescale, True)[0]
 
-    def simple_test(self, img, img_meta, rescale=True):
-        """:255-266: one (H, W) int64 array per image; the probabilities are never formed"""
-        seg_pred = self._finish(img, img_meta, rescale, True, prob=False, labels=True)[1]
-        return list(seg_pred.cpu().numpy())
+    def simple_test_labels(self, img, img_meta, rescale=True):
+        """simple_test up to the label map: (N, H, W) int64 on the device; the probabilities are never formed"""
+        return self._finish(img, img_meta, rescale, True, prob=False, labels=True)[1]
 
-    def aug_test(self, imgs, img_metas, rescale=True):
-        """:268-285: the views' probabilities added into one sum, then argmax of sum / views"""
+    def simple_test(self, img, img_meta, rescale=True):
+        """:255-266: one (H, W) int64 array per image"""
+        return list(self.simple_test_labels(img, img_meta, rescale).cpu().numpy())
+
+    def aug_test_labels(self, imgs, img_metas, rescale=True):
+        """aug_test up to the label map, (N, H, W) int64 on the device: the views' probabilities added into one sum, then
+        argmax of sum / views"""
         if not rescale:                                                # :274
             raise ValueError('aug_test supports rescale=True only')
         total = None
         for img, meta in zip(imgs, img_metas):
             total = self._finish(img, meta, rescale, True, out=total, accumulate=total is not None)[0]
         with torch.autocast(total.device.type, enabled=False):
-            seg_pred = fused.seg_argmax(total, len(imgs))
-        return list(seg_pred.cpu().numpy())
+            return fused.seg_argmax(total, len(imgs))
+
+    def aug_test(self, imgs, img_metas, rescale=True):
+        """:268-285"""
+        return list(self.aug_test_labels(imgs, img_metas, rescale).cpu().numpy())
+
+    def evaluate_batch(self, img_or_imgs, img_metas, gt_semantic_seg, evaluator, rescale=True):
+        """One step of a validation loop without leaving the device: the label map of ``simple_test_labels`` - or, for a
+        list of views with their list of metas, of ``aug_test_labels`` - goes with ``gt_semantic_seg`` ((N, H, W) or
+        (N, 1, H, W), uint8 or int64, a tensor on any device or an array) into ``evaluator`` (vitadapter.SegEvaluator).
+        What mmseg's ``single_gpu_test(pre_eval=True)`` does per batch with a copy to the host and three ``histc`` calls.
+        -> the (N, H, W) int64 label map, on the device.  A ground truth of another (H, W) than the prediction raises."""
+        if isinstance(img_or_imgs, (list, tuple)):
+            seg_pred = self.aug_test_labels(img_or_imgs, img_metas, rescale)
+        else:
+            seg_pred = self.simple_test_labels(img_or_imgs, img_metas, rescale)
+        gt = gt_semantic_seg if torch.is_tensor(gt_semantic_seg) else torch.from_numpy(np.ascontiguousarray(gt_semantic_seg))
+        if gt.dim() == 4 and gt.shape[1] == 1:
+            gt = gt[:, 0]
+        if gt.dim() != 3 or tuple(gt.shape) != tuple(seg_pred.shape):
+            raise ValueError('ground truth %s for a prediction %s: evaluate against the map the prediction was rescaled to'
+                             % (tuple(gt_semantic_seg.shape), tuple(seg_pred.shape)))
+        evaluator.update(seg_pred, gt.to(seg_pred.device, non_blocking=True))
+        return seg_pred
 
 
 class EncoderDecoderMask2FormerAug(EncoderDecoderMask2Former):
