@@ -305,6 +305,19 @@ for _name, (_res, _args) in SEGEVAL_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_seg_target.h declares (Mask2Former's training
+# targets from a label map, csrc/seg_target.hip).  The label map is (pointer, dtype code, image stride, row stride).
+# tests/test_seg_targets_abi_cpu.py holds each entry to its prototype.
+_lm = [_p, _int, _i64, _i64]
+SEGTGT_SIGNATURES = {
+    'vah_segtgt_ws_bytes': (_i64, [_i64, _i64, _i64]),
+    'vah_segtgt_scan': (_int, _lm + [_i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p]),
+    'vah_segtgt_masks': (_int, _lm + [_i64, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
+}
+for _name, (_res, _args) in SEGTGT_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

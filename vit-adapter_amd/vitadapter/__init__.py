@@ -15,10 +15,11 @@ from .mask2former_head import Mask2FormerHead
 from .segmentor import EncoderDecoder, EncoderDecoderMask2Former, EncoderDecoderMask2FormerAug
 from .evaluation import (SegEvaluator, eval_metrics, intersect_and_union, mean_dice, mean_fscore, mean_iou, pre_eval_to_metrics,
                          total_area_to_metrics, total_intersect_and_union)
+from .pipelines import ToMask
 
 __all__ = ['ViTAdapter', 'ViTAdapterSeg', 'ViTAdapterDet', 'register_backbones', 'BEiTAdapter',
            'register_beit_adapter',
            'MultiScaleDeformableAttention', 'register_attention', 'MSDeformAttnPixelDecoder', 'register_pixel_decoder',
            'Mask2FormerHead', 'EncoderDecoderMask2Former', 'EncoderDecoderMask2FormerAug', 'EncoderDecoder',
            'SegEvaluator', 'intersect_and_union', 'total_intersect_and_union', 'total_area_to_metrics', 'pre_eval_to_metrics',
-           'eval_metrics', 'mean_iou', 'mean_dice', 'mean_fscore']
+           'eval_metrics', 'mean_iou', 'mean_dice', 'mean_fscore', 'ToMask']

@@ -34,6 +34,8 @@ seg_cross_entropy (csrc/seg_ce_loss.hip, ENABLED['seg_ce_loss']) is the training
 bilinear resize to the label map, cross-entropy with an ignore index and the top-1 count, with an ordered backward into the logits.
 seg_eval_update (csrc/seg_eval.hip, ENABLED['seg_eval']) is the counting pass of the mIoU evaluation (vitadapter/evaluation.py):
 predicted labels and ground truth in, 3 x num_classes int64 totals added to on the device, nothing read back.
+seg_targets / seg_targets_begin (csrc/seg_target.hip, ENABLED['seg_targets']) are the training targets of Mask2Former from the label
+map: the reference's ToMask step (labels and binary masks per image) on the device, the counts reaching the host in one small copy.
 """
 import math
 import os
@@ -56,6 +58,7 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'seg_logits': True,
            'seg_ce_loss': True,
            'seg_eval': True,
+           'seg_targets': True,
            # the per-step parameter work on kernels of its own (include/vitadapter_hip_epoch.h): one launch for all 16-bit
            # parameter copies and layouts of a forward (_EpochCopies), pair-core weight gradients stored in parameter
            # order by the reduction launch, BatchNorm bookkeeping inside the finalize launch.  Off: the torch expressions
@@ -2683,3 +2686,170 @@ def seg_eval_update(pred, label, totals, num_classes, ignore_index=255, reduce_z
             for m, v in ((p_in & (p == g), p), (p_in, p), (g_in, g))]
     totals += torch.stack(rows).to(totals.device)
     return totals
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Mask2Former's training targets from a label map (include/vitadapter_hip_seg_target.h, csrc/seg_target.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+class SegTargets:
+    """The targets of a batch, as the reference's ToMask step defines them per image (formatting.py:58-77), for all images
+    at once: ``masks`` (G_total, H, W) uint8, ``labels`` (G_total,) int64, ``image_of`` (G_total,) int32 - the image of
+    each target -, ``counts`` a list of N Python ints and ``offsets`` (N + 1,) int32 on the masks' device, the exclusive
+    prefix sums of the counts.  The targets of image n are ``[offsets[n], offsets[n + 1])``, labels ascending."""
+
+    __slots__ = ('masks', 'labels', 'image_of', 'counts', 'offsets')
+
+    def __init__(self, masks, labels, image_of, counts, offsets):
+        self.masks, self.labels, self.image_of, self.counts, self.offsets = masks, labels, image_of, counts, offsets
+
+    def finish(self):
+        """itself: a finished result stands wherever a pending handle does"""
+        return self
+
+
+_SEG_TARGET_TABLES = {}
+_SEG_TARGET_PINNED = {}         # N -> free pinned int32 (N + 2,) buffers; a pending handle holds one from begin to finish
+
+
+def seg_remap_table(reduce_zero_label=False, label_map=None):
+    """The 256-entry uint8 table (a CPU tensor) that ``seg_targets`` applies to the original label value, in the order of
+    ``seg_eval_update``: ``label_map`` ({old: new}, every entry on the original value), then ``reduce_zero_label``
+    (0 and 255 -> 255, else v - 1).  An entry that does not fit 8 bits is a ValueError."""
+    table = list(range(256))
+    for old, new in (label_map or {}).items():
+        if not 0 <= int(old) < 256:
+            raise ValueError('seg_remap_table: label_map key %r is no 8-bit label' % (old,))
+        table[int(old)] = int(new)
+    if reduce_zero_label:
+        table = [255 if v in (0, 255) else v - 1 for v in table]
+    for old, new in enumerate(table):
+        if not 0 <= new < 256:
+            raise ValueError('seg_remap_table: %d -> %d does not fit 8 bits' % (old, new))
+    return torch.tensor(table, dtype=torch.uint8)
+
+
+def _seg_target_table(remap, device):
+    """``remap`` as the device table of vah_segtgt_*: a 256-entry uint8 tensor or array (cached per content and device), else None"""
+    if not isinstance(remap, torch.Tensor):
+        try:
+            remap = torch.as_tensor(remap)
+        except (TypeError, ValueError, RuntimeError):
+            return None
+    if remap.dtype != torch.uint8 or tuple(remap.shape) != (256,):
+        return None
+    if remap.device == device:
+        return remap.contiguous()
+    key = (bytes(remap.cpu().contiguous().numpy().tobytes()), str(device))
+    if key not in _SEG_TARGET_TABLES:
+        _SEG_TARGET_TABLES[key] = remap.to(device).contiguous()
+    return _SEG_TARGET_TABLES[key]
+
+
+def _seg_targets_torch(g, ignore_index, remap):
+    """the rule with torch.unique and a broadcast comparison per image, on ``g``'s device; labels of any value"""
+    N, H, W = g.shape
+    dev = g.device
+    if remap is not None:
+        v = g.long()                                        # a table of any length: values outside it stay what they are
+        table = torch.as_tensor(remap).to(dev).long().reshape(-1)
+        inside = (v >= 0) & (v < table.numel())
+        g = torch.where(inside, table[v.clamp(0, max(table.numel() - 1, 0))], v) if table.numel() else v
+    labels, masks, counts = [], [], []
+    for n in range(N):
+        lab = torch.unique(g[n]).long()                     # int64 before the test: an ignore_index outside the map's dtype
+        lab = lab[lab != ignore_index]
+        labels.append(lab)
+        masks.append((g[n][None] == lab.to(g.dtype)[:, None, None]).to(torch.uint8))
+        counts.append(int(lab.numel()))
+    offsets = torch.tensor([sum(counts[:n]) for n in range(N + 1)], dtype=torch.int32, device=dev)
+    image_of = torch.cat([torch.full((c,), n, dtype=torch.int32, device=dev) for n, c in enumerate(counts)]
+                         + [torch.zeros(0, dtype=torch.int32, device=dev)])
+    return SegTargets(torch.cat(masks + [torch.zeros((0, H, W), dtype=torch.uint8, device=dev)]),
+                      torch.cat(labels + [torch.zeros(0, dtype=torch.int64, device=dev)]), image_of, counts, offsets)
+
+
+class _PendingSegTargets:
+    """What ``seg_targets_begin`` returns: ``finish()`` -> SegTargets.  On the kernel route the scan and the copy of the
+    counts to the host are under way; ``finish`` waits for that copy's event only."""
+
+    def __init__(self, g, ignore_index, remap, route=None):
+        self.g, self.ignore_index, self.remap, self.route, self.done = g, ignore_index, remap, route, None
+
+    def finish(self):
+        if self.done is None:
+            self.done = self._finish()
+            self.g = self.remap = self.route = None
+        return self.done
+
+    def _finish(self):
+        if self.route is None:
+            return _seg_targets_torch(self.g, self.ignore_index, self.remap)
+        g, table, labels, slot, meta, host, event, stream = self.route
+        N, H, W = g.shape
+        dev = g.device
+        event.synchronize()                                 # the copy of meta; not the device, not the stream
+        offsets = host[:N + 1].tolist()
+        flagged = int(host[N + 1]) != 0
+        _SEG_TARGET_PINNED.setdefault(N, []).append(host)
+        if flagged:                                         # an int64 value outside [0, 256): the whole call by the rule in torch
+            return _seg_targets_torch(g, self.ignore_index, self.remap)
+        G = int(offsets[N])
+        masks = torch.empty((G, H, W), dtype=torch.uint8, device=dev)
+        out_labels = torch.empty((G,), dtype=torch.int64, device=dev)
+        image_of = torch.empty((G,), dtype=torch.int32, device=dev)
+        with _vah.on(dev):
+            now = torch.cuda.current_stream(dev)
+            if now != stream:
+                now.wait_event(event)
+            _vah.check(_vah.lib.vah_segtgt_masks(g.data_ptr(), _SEG_EVAL_CODES[g.dtype], g.stride(0), g.stride(1), N, H, W,
+                                                 None if table is None else table.data_ptr(), slot.data_ptr(), labels.data_ptr(),
+                                                 meta.data_ptr(), G, masks.data_ptr(), image_of.data_ptr(), out_labels.data_ptr(),
+                                                 now.cuda_stream), 'vah_segtgt_masks')
+        return SegTargets(masks, out_labels, image_of, [b - a for a, b in zip(offsets, offsets[1:])], meta[:N + 1])
+
+
+def seg_targets_begin(gt_semantic_seg, ignore_index=255, remap=None):
+    """Start building the targets of ``gt_semantic_seg`` ((N, H, W) or (N, 1, H, W) labels); -> a handle whose ``finish()``
+    returns the ``SegTargets``.  Per image: the labels are the distinct values of the map - after ``remap``, a 256-entry
+    uint8 table (``seg_remap_table``) applied to the original value - ascending, without ``ignore_index``; mask g is 1 where
+    the map equals label g.
+    On the GPU with ENABLED['seg_targets'], for uint8 or int64 maps with column stride 1, this runs the scan and finish
+    launches of csrc/seg_target.hip, starts a non-blocking copy of the N + 2 counts into a pinned buffer and records an event:
+    nothing waits here.  ``finish()`` waits for that event, allocates the outputs and runs the mask launch.  An int64 value
+    outside [0, 256) comes back as a flag and the call is redone in torch.  Otherwise - switch off, CPU, other dtypes or
+    strides, a ``remap`` table of another length or dtype - ``finish()`` evaluates the rule
+    with torch.unique and a comparison per image on the input's device, with no limit on the label values."""
+    g = gt_semantic_seg
+    if g.dim() == 4 and g.shape[1] == 1:
+        g = g[:, 0]
+    if g.dim() != 3:
+        raise ValueError('seg_targets: a label map of shape (N, H, W) or (N, 1, H, W), got %s' % (tuple(gt_semantic_seg.shape),))
+    g = g.detach()
+    N, H, W = g.shape
+    dev = g.device
+    table = None if remap is None else (_seg_target_table(remap, dev) if g.is_cuda else None)
+    if not (ENABLED['seg_targets'] and g.is_cuda and g.dtype in _SEG_EVAL_CODES and g.numel() > 0 and g.stride(2) == 1
+            and g.stride(1) >= W and g.stride(0) >= (H - 1) * g.stride(1) + W and (remap is None or table is not None)
+            and _vah.lib.vah_segtgt_ws_bytes(N, H, W) > 0):
+        return _PendingSegTargets(g, int(ignore_index), remap)
+    nbytes = _vah.lib.vah_segtgt_ws_bytes(N, H, W)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    labels = torch.empty((N, 256), dtype=torch.int64, device=dev)
+    slot = torch.empty((N, 256), dtype=torch.int32, device=dev)
+    meta = torch.empty((N + 2,), dtype=torch.int32, device=dev)
+    free = _SEG_TARGET_PINNED.setdefault(N, [])
+    host = free.pop() if free else torch.empty((N + 2,), dtype=torch.int32, pin_memory=True)
+    with _vah.on(dev):
+        stream = torch.cuda.current_stream(dev)
+        _vah.check(_vah.lib.vah_segtgt_scan(g.data_ptr(), _SEG_EVAL_CODES[g.dtype], g.stride(0), g.stride(1), N, H, W, int(ignore_index),
+                                            None if table is None else table.data_ptr(), labels.data_ptr(), slot.data_ptr(),
+                                            meta.data_ptr(), ws.data_ptr(), nbytes, stream.cuda_stream), 'vah_segtgt_scan')
+        host.copy_(meta, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record(stream)
+    return _PendingSegTargets(g, int(ignore_index), remap, (g, table, labels, slot, meta, host, event, stream))
+
+
+def seg_targets(gt_semantic_seg, ignore_index=255, remap=None):
+    """``seg_targets_begin(...).finish()``"""
+    return seg_targets_begin(gt_semantic_seg, ignore_index, remap).finish()

@@ -333,7 +333,8 @@ class Mask2FormerHead(nn.Module):
     def loss(self, all_cls_scores, all_mask_preds, gt_labels_list, gt_masks_list, img_metas):
         """The reference's ``loss`` (:360-402 over ``loss_single`` :269-358 and ``_get_target_single`` :199-267):
         all_cls_scores / all_mask_preds per decoder output (N, Q, classes + 1) / (N, Q, h, w); gt_labels_list / gt_masks_list
-        per image (G_n,) / (G_n, H, W), masks 0 / 1.  -> {'loss_cls', 'loss_mask', 'loss_dice', 'd<i>.loss_*'}: the last
+        per image (G_n,) / (G_n, H, W), masks 0 / 1 - or a fused.SegTargets in place of the first list (the second is then
+        not read): its masks, image_of, labels, counts and offsets are the single group, used as they are.  -> {'loss_cls', 'loss_mask', 'loss_dice', 'd<i>.loss_*'}: the last
         output's losses under the plain names.  One host synchronisation (see the module docstring).  ``last_assignment``
         ([output][image] -> (queries, gts)) and ``last_points`` ([output] -> (K, P, 2) or None) keep what the step chose."""
         if self.num_points is None or None in (self.loss_cls, self.loss_mask, self.loss_dice):
@@ -344,16 +345,22 @@ class Mask2FormerHead(nn.Module):
         N, Q, h, w = preds[0].shape
         dev = preds[0].device
         P = self.num_points
-        groups, counts = self._gt_groups(gt_masks_list, dev)
+        targets = gt_labels_list if isinstance(gt_labels_list, fused.SegTargets) else None
+        if targets is not None:                                         # built on the device: the one group, as it is
+            groups, counts = [(targets.masks, targets.image_of, 0)], targets.counts
+            labels_all = targets.labels
+        else:
+            groups, counts = self._gt_groups(gt_masks_list, dev)
+            labels_all = torch.cat([torch.as_tensor(lab).to(dev).long().reshape(-1) for lab in gt_labels_list])
         G_total = sum(counts)
-        labels_all = torch.cat([torch.as_tensor(lab).to(dev).long().reshape(-1) for lab in gt_labels_list])
         class_weight = cls[0].new_tensor(self.class_weight) if self.class_weight is not None else None
 
         # 1. matching: points, sampled predictions and costs of every decoder output, then one trip to the host
         none = torch.zeros(0, dtype=torch.long)
         assign = [[(none, none) for _ in range(N)] for _ in range(L)]
         if G_total > 0:
-            offsets = torch.tensor([sum(counts[:n]) for n in range(N + 1)], dtype=torch.int32, device=dev)
+            offsets = (targets.offsets if targets is not None
+                       else torch.tensor([sum(counts[:n]) for n in range(N + 1)], dtype=torch.int32, device=dev))
             image_of_query = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(Q)
             costs = []
             with torch.no_grad():
@@ -432,10 +439,29 @@ class Mask2FormerHead(nn.Module):
             out['d%d.loss_cls' % i], out['d%d.loss_mask' % i], out['d%d.loss_dice' % i] = lc, lm, ld
         return out
 
-    def forward_train(self, x, img_metas, gt_semantic_seg, gt_labels, gt_masks):
-        """:527-555: the loss dict of a training step; ``gt_semantic_seg`` is not used, as in the reference"""
+    def prepare_targets(self, gt_semantic_seg):
+        """Start building the step's targets from the label map ((N, H, W) or (N, 1, H, W)): the reference's ToMask step
+        with the head's ``ignore_index`` (255 where it has none), fused.seg_targets_begin.  -> the pending handle that
+        ``forward_train`` takes as ``gt_targets``; called before the backbone, its launches and its small copy to the host
+        are done when the head asks for the result."""
+        ignore = getattr(self, 'ignore_index', None)
+        return fused.seg_targets_begin(gt_semantic_seg, 255 if ignore is None else ignore)
+
+    def forward_train(self, x, img_metas, gt_semantic_seg, gt_labels=None, gt_masks=None, gt_targets=None):
+        """:527-555: the loss dict of a training step.  The targets come, in this order, from ``gt_labels`` / ``gt_masks``
+        (per-image lists, what the reference's pipeline delivers; ``gt_semantic_seg`` is then not used, as in the reference),
+        from ``gt_targets`` (a fused.SegTargets or the handle of ``prepare_targets``), or from ``gt_semantic_seg`` itself."""
+        if (gt_labels is None) != (gt_masks is None):
+            raise ValueError('forward_train: gt_labels and gt_masks go together')
+        if gt_masks is None and gt_targets is None and gt_semantic_seg is None:
+            raise ValueError('forward_train needs the targets: gt_labels and gt_masks (per-image lists), gt_targets (a SegTargets '
+                             'or the handle of prepare_targets), or gt_semantic_seg (the label map to derive them from)')
+        if gt_masks is None and gt_targets is None:
+            gt_targets = self.prepare_targets(gt_semantic_seg)
         all_cls_scores, all_mask_preds = self(x, img_metas)
-        return self.loss(all_cls_scores, all_mask_preds, gt_labels, gt_masks, img_metas)
+        if gt_masks is not None:
+            return self.loss(all_cls_scores, all_mask_preds, gt_labels, gt_masks, img_metas)
+        return self.loss(all_cls_scores, all_mask_preds, gt_targets.finish(), None, img_metas)
 
     def forward_test(self, inputs, img_metas, test_cfg):
         """:557-579: semantic logits (N, classes, h, w) of the last decoder output, in fp32.  The reference also reads

@@ -126,7 +126,14 @@ class EncoderDecoderMask2Former(nn.Module):
         return self.encode_decode(img, None)
 
     def forward_train(self, img, img_metas, gt_semantic_seg, **kwargs):
-        """:122-153: the head's loss dict under the prefix ``decode.``"""
+        """:122-153: the head's loss dict under the prefix ``decode.``.  A head with ``prepare_targets`` that is given the
+        label map and neither ``gt_masks`` nor ``gt_targets`` has its targets started here, BEFORE the backbone: the scan of
+        the label map and the copy of its counts to the host complete while the backbone's launches queue, and the head's
+        ``finish()`` finds its event done."""
+        head = self.decode_head
+        if (hasattr(head, 'prepare_targets') and gt_semantic_seg is not None and kwargs.get('gt_masks') is None
+                and kwargs.get('gt_targets') is None):
+            kwargs = dict(kwargs, gt_targets=head.prepare_targets(gt_semantic_seg))
         x = self.extract_feat(img)
         loss_decode = self.decode_head.forward_train(x, img_metas, gt_semantic_seg, **kwargs)
         return {'decode.' + k: v for k, v in loss_decode.items()}
