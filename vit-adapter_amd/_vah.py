@@ -318,6 +318,16 @@ for _name, (_res, _args) in SEGTGT_SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
+# name -> (restype, argtypes) of every entry point include/vitadapter_hip_assign.h declares (the assignment step of
+# Mask2Former's matching, csrc/assign.hip): cost, gt_offsets, L, N, Q, Gmax, table, status, stream.
+# tests/test_hungarian_abi_cpu.py holds the entry to its prototype.
+ASSIGN_SIGNATURES = {
+    'vah_assign_solve': (_int, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+}
+for _name, (_res, _args) in ASSIGN_SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 if lib.vah_abi_version() != ABI_VERSION:
     raise ImportError('libvitadapter_hip.so ABI %d != binding ABI %d: rebuild the library'
                       % (lib.vah_abi_version(), ABI_VERSION))

@@ -36,6 +36,8 @@ seg_eval_update (csrc/seg_eval.hip, ENABLED['seg_eval']) is the counting pass of
 predicted labels and ground truth in, 3 x num_classes int64 totals added to on the device, nothing read back.
 seg_targets / seg_targets_begin (csrc/seg_target.hip, ENABLED['seg_targets']) are the training targets of Mask2Former from the label
 map: the reference's ToMask step (labels and binary masks per image) on the device, the counts reaching the host in one small copy.
+hungarian_match (csrc/assign.hip, ENABLED['hungarian']) is the assignment step of the matching: every (decoder output, image) cost block
+of a step solved exactly in one launch, the matched pairs left on the device as the table the losses index with; off, scipy on the host.
 """
 import math
 import os
@@ -59,6 +61,7 @@ ENABLED = {'pair_core': True, 'layer_norm': True, 'residual': True, 'residual_ln
            'seg_ce_loss': True,
            'seg_eval': True,
            'seg_targets': True,
+           'hungarian': True,         # the matching's assignment step on the device (csrc/assign.hip); off: scipy on the host
            # the per-step parameter work on kernels of its own (include/vitadapter_hip_epoch.h): one launch for all 16-bit
            # parameter copies and layouts of a forward (_EpochCopies), pair-core weight gradients stored in parameter
            # order by the reduction launch, BatchNorm bookkeeping inside the finalize launch.  Off: the torch expressions
@@ -2404,6 +2407,73 @@ def point_mask_losses(mask_pred, rows, targets, tgt_rows, points, eps=1.0):
     s = x.sigmoid()
     dice = 1 - (2 * (s * t).sum(1) + eps) / (s.sum(1) + t.sum(1) + eps)
     return bce, dice
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the assignment step of Mask2Former's matching (include/vitadapter_hip_assign.h, csrc/assign.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+ASSIGN_MAX_DIM, ASSIGN_MAX_CELLS, ASSIGN_MAX_IMAGES = 256, 32768, 4096
+ASSIGN_ERRORS = {1: 'matrix contains invalid numeric entries', 2: 'cost matrix is infeasible'}       # scipy's two messages
+
+
+def _hungarian_host(stacked, counts):
+    """the path before the kernel: one copy to the host, scipy per problem, -> the (L, 2, K) int64 table on the host"""
+    L, N, Q, _ = stacked.shape
+    host = stacked.detach().cpu().numpy()                         # the synchronisation of this path
+    try:
+        from scipy.optimize import linear_sum_assignment
+    except ImportError:
+        raise ImportError('Please run "pip install scipy" to install scipy first.') from None
+    firsts = [sum(counts[:n]) for n in range(N)]
+    none = torch.zeros(0, dtype=torch.long)
+    table = []
+    for i in range(L):
+        rows, tgts = [none], [none]
+        for n in range(N):
+            if counts[n]:
+                r, c = linear_sum_assignment(host[i, n, :, :counts[n]])
+                order = r.argsort(kind='stable')                    # MaskPseudoSampler: positives in query order
+                rows.append(torch.from_numpy(r[order]).long() + n * Q)
+                tgts.append(torch.from_numpy(c[order]).long() + firsts[n])
+        table.append(torch.stack([torch.cat(rows), torch.cat(tgts)]))
+    return torch.stack(table) if table else torch.zeros((0, 2, 0), dtype=torch.long)
+
+
+def hungarian_match(costs, gt_counts, gt_offsets=None):
+    """The assignment of the reference's MaskHungarianAssigner (models/utils/assigner.py:147-160, scipy's
+    linear_sum_assignment per cost matrix) and the order of its MaskPseudoSampler for every (decoder output, image) of a step:
+    ``costs`` the list of per-output (N, Q, Gmax) matrices of ``match_costs`` or their stack (L, N, Q, Gmax), ``gt_counts`` the N
+    counts (columns past an image's count are not read), ``gt_offsets`` the int32 (N + 1,) running sum on the device if the
+    caller keeps one.  -> (table, status): table (L, 2, K) int64 on the costs' device with K = sum_n min(Q, G_n), per output
+    the matched (query row n * Q + q, global target index) pairs, images in order, queries ascending within an image.
+    On the GPU with ENABLED['hungarian'], for fp32 costs with Q <= 256, Gmax <= 256 and Q * Gmax <= 32768, this is one launch of
+    vah_assign_solve and nothing reaches the host: status is the (L, N) int32 tensor of the header (0 solved, 1 invalid
+    entries, 2 infeasible; the pairs of such a problem are the identity pairing).  Otherwise - switch off, CPU, larger
+    problems - the costs go to the host in one copy, scipy solves each problem (and raises for the two cases), the table goes
+    back in one copy, and status is None."""
+    stacked = costs if isinstance(costs, torch.Tensor) else torch.stack(list(costs))
+    if stacked.dim() != 4:
+        raise ValueError('hungarian_match: costs of shape (L, N, Q, Gmax) or a list of (N, Q, Gmax), got %s' % (tuple(stacked.shape),))
+    L, N, Q, Gmax = stacked.shape
+    counts = [int(c) for c in gt_counts]
+    if len(counts) != N or any(c < 0 or c > Gmax for c in counts):
+        raise ValueError('hungarian_match: %d counts in [0, %d] expected, got %r' % (N, Gmax, counts))
+    dev = stacked.device
+    if (ENABLED['hungarian'] and stacked.is_cuda and stacked.dtype == torch.float32 and 1 <= Q <= ASSIGN_MAX_DIM and Gmax <= ASSIGN_MAX_DIM
+            and Q * Gmax <= ASSIGN_MAX_CELLS and N <= ASSIGN_MAX_IMAGES):
+        K = sum(min(Q, c) for c in counts)
+        stacked = stacked.detach().contiguous()
+        if L * N * Gmax == 0 or K == 0:                             # nothing to solve, and no table to point the kernel at
+            return torch.zeros((L, 2, 0), dtype=torch.int64, device=dev), torch.zeros((L, N), dtype=torch.int32, device=dev)
+        if gt_offsets is None:
+            gt_offsets = torch.tensor([sum(counts[:i]) for i in range(N + 1)], dtype=torch.int32, device=dev)
+        table = torch.empty((L, 2, K), dtype=torch.int64, device=dev)
+        status = torch.empty((L, N), dtype=torch.int32, device=dev)
+        with _vah.on(dev):
+            _vah.check(_vah.lib.vah_assign_solve(stacked.data_ptr(), gt_offsets.data_ptr(), L, N, Q, Gmax, table.data_ptr(),
+                                                 status.data_ptr(), _stream(stacked)), 'vah_assign_solve')
+        return table, status
+    return _hungarian_host(stacked, counts).to(dev), None
 
 
 _SEG_FLIPS = {None: 0, False: 0, 'horizontal': 1, 'vertical': 2}

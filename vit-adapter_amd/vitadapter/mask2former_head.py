@@ -26,10 +26,18 @@ Differences from the reference's expression, none in the arithmetic it defines:
     is < 0 and keeps every key of a row that would keep none - the reference's ``sigmoid() < 0.5`` and its
     ``attn_mask[torch.where(...)] = False``, without the copy per head and without the host synchronisation.  The sign test
     differs from torch's rounded sigmoid in a thin band below zero (include/vitadapter_hip_masked_attn.h);
-  * ``loss`` makes ONE host round trip per step where the reference makes one per (decoder output, image): the matching
-    points, sampled predictions and cost matrices of every decoder output and image are computed first
-    (fused.point_sample, fused.match_costs), all costs go to the host in one copy, scipy's linear_sum_assignment runs per
-    (output, image), and the assignments go back in one copy.  Ground-truth masks are concatenated once per step as uint8
+  * ``loss`` makes NO host round trip for the matching on the device path, where the reference makes one per (decoder
+    output, image): the matching points, sampled predictions and cost matrices of every decoder output and image are computed
+    first (fused.point_sample, fused.match_costs), then fused.hungarian_match solves every problem in one launch of
+    csrc/assign.hip - scipy's method, fp64 duals - and leaves the table of matched pairs on the device.  With the targets a
+    fused.SegTargets, ``loss`` contains no host synchronisation at all after a first call (small constants are cached per
+    device); with per-image lists the upload of the offsets remains.  On the CPU, with ENABLED['hungarian'] off or beyond the
+    kernel's limits it is ONE round trip: all costs go to the host in one copy, scipy's linear_sum_assignment runs per
+    (output, image), and the table goes back in one copy.  The one difference in behaviour: where the reference's assigner
+    raises at once (a cost matrix with a NaN or -inf, or an infeasible one), the device path adds NaN to every loss of the step,
+    on the device - a GradScaler skips such a step - and ``check_last_match()`` raises scipy's error on request.
+    ``last_assignment`` keeps its meaning and type; on the device path it is built, with a copy to the host, when it is read.
+    Ground-truth masks are concatenated once per step as uint8
     and sampled at their own resolution without a float copy.  Every random draw goes through ``_draw``: the ORDER of the
     draws therefore differs from the reference's (all 'match' draws come first, then per decoder output the 'oversample' and
     the 'random' draw), their distribution does not;
@@ -316,6 +324,56 @@ class Mask2FormerHead(nn.Module):
         Tests replace this method to replay recorded points."""
         return torch.rand(shape, device=device)
 
+    def _constant(self, key, device, make):
+        """a small device tensor that ``loss`` would otherwise upload on every call (an upload waits for the device): built
+        once per (key, device) by ``make``; the key carries everything the value depends on"""
+        cache = self.__dict__.setdefault('_constants', {})
+        key = key + (str(device),)
+        if key not in cache:
+            if len(cache) > 32:
+                cache.clear()
+            cache[key] = make()
+        return cache[key]
+
+    @property
+    def last_assignment(self):
+        """[output][image] -> (queries, gts), int64 tensors on the host, queries ascending: what the last ``loss`` matched.
+        Built on first read from the step's table; on the device path that read copies the table to the host and so
+        synchronises - a step that never reads it never waits."""
+        if self.__dict__.get('_last_assignment') is None:
+            match = self.__dict__.get('_last_match')
+            if match is None:
+                raise AttributeError('last_assignment: no loss has run yet')
+            table, _, counts, Q = match
+            host = table.detach().cpu()
+            sizes = [min(Q, c) for c in counts]
+            firsts = [sum(counts[:n]) for n in range(len(counts))]
+            assign = []
+            for i in range(host.shape[0]):
+                rows, tgts = host[i, 0].split(sizes), host[i, 1].split(sizes)
+                assign.append([(r - n * Q, t - firsts[n]) for n, (r, t) in enumerate(zip(rows, tgts))])
+            self._last_assignment = assign
+        return self._last_assignment
+
+    @last_assignment.setter
+    def last_assignment(self, value):
+        self._last_assignment = value
+
+    def check_last_match(self):
+        """Raise what the reference raises inside its assigner, for the last ``loss``: ValueError with scipy's message when a
+        cost matrix of that step held a NaN or -inf ('matrix contains invalid numeric entries') or allowed no complete
+        assignment ('cost matrix is infeasible').  Reads the step's status from the device, so it synchronises; the step itself
+        does not - its losses are NaN in that case.  Silent after a clean step, and on the host path, where scipy raised
+        already."""
+        match = self.__dict__.get('_last_match')
+        if match is None or match[1] is None:
+            return
+        status = match[1].cpu()
+        for code, message in fused.ASSIGN_ERRORS.items():
+            hit = (status == code).nonzero()
+            if hit.numel():
+                raise ValueError('%s (decoder output %d, image %d)' % (message, int(hit[0, 0]), int(hit[0, 1])))
+
     def _gt_groups(self, gt_masks_list, device):
         """the ground-truth masks as ([(masks (G, H, W) uint8, image index per mask, first global gt index)], counts): one
         group when every image's masks share a size (the usual case: one concatenation per step), else one group per image"""
@@ -335,7 +393,8 @@ class Mask2FormerHead(nn.Module):
         all_cls_scores / all_mask_preds per decoder output (N, Q, classes + 1) / (N, Q, h, w); gt_labels_list / gt_masks_list
         per image (G_n,) / (G_n, H, W), masks 0 / 1 - or a fused.SegTargets in place of the first list (the second is then
         not read): its masks, image_of, labels, counts and offsets are the single group, used as they are.  -> {'loss_cls', 'loss_mask', 'loss_dice', 'd<i>.loss_*'}: the last
-        output's losses under the plain names.  One host synchronisation (see the module docstring).  ``last_assignment``
+        output's losses under the plain names.  No host synchronisation for the matching on the device path, one on the
+        fallback (see the module docstring; ``check_last_match`` for a step whose match was invalid).  ``last_assignment``
         ([output][image] -> (queries, gts)) and ``last_points`` ([output] -> (K, P, 2) or None) keep what the step chose."""
         if self.num_points is None or None in (self.loss_cls, self.loss_mask, self.loss_dice):
             raise ValueError('loss needs train_cfg (num_points, ratios, assigner) and the loss_cls / loss_mask / loss_dice configs')
@@ -352,16 +411,21 @@ class Mask2FormerHead(nn.Module):
         else:
             groups, counts = self._gt_groups(gt_masks_list, dev)
             labels_all = torch.cat([torch.as_tensor(lab).to(dev).long().reshape(-1) for lab in gt_labels_list])
+        counts = [int(c) for c in counts]
         G_total = sum(counts)
-        class_weight = cls[0].new_tensor(self.class_weight) if self.class_weight is not None else None
+        class_weight = None
+        if self.class_weight is not None:
+            class_weight = self._constant(('class_weight', tuple(float(v) for v in self.class_weight)), dev,
+                                          lambda: torch.tensor([float(v) for v in self.class_weight], dtype=torch.float32, device=dev))
 
-        # 1. matching: points, sampled predictions and costs of every decoder output, then one trip to the host
-        none = torch.zeros(0, dtype=torch.long)
-        assign = [[(none, none) for _ in range(N)] for _ in range(L)]
+        # 1. matching: points, sampled predictions and costs of every decoder output, then the assignment of all of them
+        K = sum(min(Q, c) for c in counts)
+        status = None
         if G_total > 0:
             offsets = (targets.offsets if targets is not None
                        else torch.tensor([sum(counts[:n]) for n in range(N + 1)], dtype=torch.int32, device=dev))
-            image_of_query = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(Q)
+            image_of_query = self._constant(('image_of_query', N, Q), dev,
+                                            lambda: torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(Q))
             costs = []
             with torch.no_grad():
                 for i in range(L):
@@ -370,23 +434,12 @@ class Mask2FormerHead(nn.Module):
                     ts = torch.cat([fused.point_sample(m, pts, set_idx=image_of) for m, image_of, _ in groups if m.shape[0]], 0)
                     costs.append(fused.match_costs(xs, ts, cls[i], labels_all, counts, self.match_weights, self.dice_cost_eps,
                                                    gt_offsets=offsets))
-                host = torch.stack(costs).cpu().numpy()                 # the step's one synchronisation
-            try:
-                from scipy.optimize import linear_sum_assignment
-            except ImportError:
-                raise ImportError('Please run "pip install scipy" to install scipy first.') from None
-            for i in range(L):
-                for n in range(N):
-                    if counts[n]:
-                        r, c = linear_sum_assignment(host[i, n, :, :counts[n]])
-                        order = r.argsort(kind='stable')                # MaskPseudoSampler: positives in query order
-                        assign[i][n] = (torch.from_numpy(r[order]).long(), torch.from_numpy(c[order]).long())
-        self.last_assignment = assign
-        K = sum(a[0].numel() for a in assign[0])
-        firsts = [sum(counts[:n]) for n in range(N)]
-        table = torch.stack([torch.stack([torch.cat([a[0] + n * Q for n, a in enumerate(assign[i])]),
-                                          torch.cat([a[1] + firsts[n] for n, a in enumerate(assign[i])])]) for i in range(L)])
-        table = table.to(dev)                                           # (L, 2, K): query row, global gt index; one copy
+                # (L, 2, K): query row, global gt index.  On the device path nothing comes back; else the step's one round trip
+                table, status = fused.hungarian_match(costs, counts, gt_offsets=offsets)
+        else:
+            table = torch.zeros((L, 2, 0), dtype=torch.long, device=dev)
+        self._last_match = (table, status, counts, Q)
+        self._last_assignment = None
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             total = cls[0].new_tensor([float(K)]) / torch.distributed.get_world_size()
             torch.distributed.all_reduce(total)
@@ -434,6 +487,11 @@ class Mask2FormerHead(nn.Module):
             loss_mask = self.mask_loss_weight * (torch.cat(bce).sum() / (num_total_masks * P))
             loss_dice = self.dice_loss_weight * (torch.cat(dice).sum() / num_total_masks)
             losses.append((loss_cls, loss_mask, loss_dice))
+        if status is not None:
+            # a problem the solver could not solve (its pairs are then the identity pairing): NaN into every loss, on the
+            # device, where the reference raises at once - see check_last_match
+            poison = torch.where(status.ne(0).any(), float('nan'), 0.0)
+            losses = [tuple(v + poison for v in three) for three in losses]
         out = dict(loss_cls=losses[-1][0], loss_mask=losses[-1][1], loss_dice=losses[-1][2])
         for i, (lc, lm, ld) in enumerate(losses[:-1]):
             out['d%d.loss_cls' % i], out['d%d.loss_mask' % i], out['d%d.loss_dice' % i] = lc, lm, ld
